@@ -98,6 +98,35 @@ class Traffic:
         return (v["bytes"], v["file"]) if v else (None, self.why)
 
 
+DUMP_SAMPLE = 1 << 21       # entries kept per dumped array (16 MB of float64): every dump stays well under 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_sample(a, cap):
+    """`a` itself when it holds at most `cap` entries, otherwise a fixed, seeded sample of `cap` of them in index order (the
+    same entries for the same argument list, whatever build computed them)"""
+    if a.size <= cap:
+        return a
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=cap, replace=False))
+    return a[idx]
+
+
+def dump_outputs(out_dir, ctx, A, vx, info, rank, nranks):
+    """What the timed step hands its caller, from the LAST timed step: the assembled matrix values (block-CSR storage order of
+    include/pynama_hip.h), the CG iterate after the fixed iteration count, and the solver's scalar report.  N > 1: every rank
+    writes its own rows with a `_rank<r>` suffix."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if nranks > 1 else ""
+    cap = DUMP_SAMPLE // nranks
+    arrays = {"matrix_values": dump_sample(ctx.mat_values(A, 1, 1), cap),
+              "solution": dump_sample(ctx.vec_get(vx, 1), cap),
+              # [iterations, converged reason, final residual norm, initial residual norm]
+              "solve_info": np.array([info.iters, info.reason, info.rnorm, info.rnorm0], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return sorted(arrays)
+
+
 def cpu_baseline(dom, rp, ci, bmask, b, budget_s=8.0):
     """C/OpenMP restatement of the same path (oracle/c/fem_oracle.c) on the host cores, on a bounded
     sample of the SAME workload: whole-mesh assembly passes and Jacobi-PCG iterations on the
@@ -532,7 +561,12 @@ def main():
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--no-matfree", action="store_true", help="skip the matrix-free CG leg (reported alongside, not the headline)")
     ap.add_argument("--no-extra", action="store_true", help="skip the general-geometry leg and the other BASELINE configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64; arrays over "
+                         f"{DUMP_SAMPLE} entries as a fixed seeded sample): matrix_values, solution, solve_info")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from pynama_amd import _lib
     from pynama_amd.common.comm import get_world
@@ -573,11 +607,14 @@ def main():
     # element layer it shares with each neighbour; only globally distinct elements are counted)
     elem_dofs_per_step = n_elem_global * 8
 
+    last = {}
+
     def step(profile):
         ctx.assemble_scalar(_lib.FORM_LAPLACE, A, -1, variant=args.variant)
         t_asm = ctx.timers()["assemble_ms"]
         info = ctx.solve(A, vb, vx, method=_lib.KSP_CG, pc=_lib.PC_JACOBI, fixed_iters=args.cg_iters,
                          norm_type=_lib.NORM_UNPRECONDITIONED, profile=1 if profile else 0)
+        last["info"] = info
         return t_asm, info.solve_ms, info.spmv_ms, info.reduce_ms, info.halo_ms
 
     for k in range(args.warmup):
@@ -605,6 +642,11 @@ def main():
     loc = [wall, np.mean(asm_ms), np.mean(cg_ms), np.mean(spmv_ms), np.mean(red_ms), np.mean(halo_ms)]
     red = ctx.allreduce(loc, op="max") if world.size > 1 else np.array(loc)
     wall, asm_mean, cg_mean, spmv_mean, red_mean, halo_mean = [float(v) for v in red]
+
+    # ---- the last timed step's outputs, before anything below reuses A or x
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, ctx, A, vx, last["info"], world.rank, world.size)
 
     # ---- correctness on the SAME workload (outside the timed region): solve to 1e-10
     check = None
@@ -754,6 +796,7 @@ def main():
                                       # per entry that the dictionary product never streams, so this is the fraction to steer by
                                       "on_measured_traffic": cg_traffic},
             "check": check,
+            "dumped_outputs": dumped,
             "selftest": selftest,
             "matrix_free": mfree,
             "configs": extra,

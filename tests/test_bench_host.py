@@ -58,6 +58,48 @@ def test_roofline_record():
     assert r["achieved"] == 4000.0 and r["frac"] == 0.5 and r["peak"] == 8000.0 and r["bound"] == "hbm" and r["unit"] == "GB/s"
 
 
+class _FakeCtx:
+    """the two read-backs dump_outputs uses, served from host arrays"""
+
+    def __init__(self, vals, x):
+        self.vals, self.x = vals, x
+
+    def mat_values(self, mid, br, bc):
+        return self.vals.copy()
+
+    def vec_get(self, vid, bs):
+        return self.x.copy()
+
+
+class _FakeInfo:
+    iters, reason, rnorm, rnorm0 = 100, 0, 1.5e-3, 2.0
+
+
+def test_dump_outputs_writes_float64_within_budget_and_samples_repeatably(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    rng = np.random.default_rng(3)
+    small_x, big_vals = rng.standard_normal(700), rng.standard_normal(5000)
+    ctx = _FakeCtx(big_vals, small_x)
+    names = bench.dump_outputs(str(tmp_path / "a"), ctx, 0, 1, _FakeInfo(), 0, 1)
+    assert names == ["matrix_values", "solution", "solve_info"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["solution"], small_x)                               # small enough: whole
+    assert got["matrix_values"].size == 1000 and np.isin(got["matrix_values"], big_vals).all()
+    assert got["solve_info"].tolist() == [100.0, 0.0, 1.5e-3, 2.0]
+    # same arguments -> same entries
+    bench.dump_outputs(str(tmp_path / "b"), ctx, 0, 1, _FakeInfo(), 0, 1)
+    assert np.array_equal(np.load(tmp_path / "b" / "matrix_values.npy"), got["matrix_values"])
+    # N > 1: one file per rank, the budget split over the ranks
+    bench.dump_outputs(str(tmp_path / "c"), ctx, 0, 1, _FakeInfo(), 1, 2)
+    assert sorted(os.listdir(tmp_path / "c")) == ["matrix_values_rank1.npy", "solution_rank1.npy", "solve_info_rank1.npy"]
+    assert np.load(tmp_path / "c" / "matrix_values_rank1.npy").size == 500
+
+
+def test_dump_budget_is_under_64_mb():
+    assert 2 * bench.DUMP_SAMPLE * 8 + 4 * 8 < 64 * 2 ** 20
+
+
 def test_kuhn_box_is_a_conforming_positive_tet_mesh():
     xyz, conn = bench.kuhn_box(3)
     assert conn.shape == (6 * 27, 4) and xyz.shape == (64, 3)
