@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the Pynama hot path on MI355X (contract: see the driver's prompt).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json metric): 3-D Poisson, Q1 hexahedra, 215^3 elements = 216^3 =
@@ -15,15 +15,17 @@ N > 1: the SAME mesh is row-partitioned in z-slabs over the ranks ("scaling": "s
 planes and dot products go over RCCL inside libpynama_hip.so; a start-up self-test of the
 communicator runs first under a bounded wait (pynama_amd/common/comm.py).
 
-Next to the headline the same run reports, outside the timed region (N = 1 only):
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the headline line; the rooflines in it are
+priced on the timed steps.  With `--full` the same run also solves the headline system to 1e-10 (`check`) and reports, outside
+the timed region, the CPU baseline (`cpu_baseline`, N = 1 only), `matrix_free` (the same CG with the operator recomputed from
+the mesh) and (N = 1 only):
   * `roofline_assembly_general`: the assembly of the SAME mesh with jittered nodes -- the
     quadrature path (the reference integrates every cell, spectral.py:117-156), not the
     parallelepiped closed form the uniform box admits;
   * `configs`: the other single-GPU configurations of BASELINE.json (C1 2-D plumbing case, C2
     128^3 Poisson, C3 128^3 KLE with 3 DOFs per node, C5 5 M tetrahedra with GMRES(30)+Jacobi)
     and the reference's own element order (HO3_2D: 1024^2, HO3_3D: 64^3 second-order cells, KLE),
-    each with its residual check;
-  * `matrix_free`: the same CG with the operator recomputed from the mesh.
+    each with its residual check.
 
 The product path is torch-free: ranks/LOCAL_RANK come from the launcher's environment, the RCCL
 id is exchanged through a node-local file (pynama_amd/common/comm.py).
@@ -546,7 +548,7 @@ def config_tets(_lib, DMPlexDom, n, gmres_iters):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -557,16 +559,26 @@ def main():
                     "2 patch-plan kernel on 7x7x7 tiles")
     ap.add_argument("--jitter", type=float, default=0.0, help="perturb interior nodes of the HEADLINE mesh by jitter*h (diagnostics; the "
                     "general-geometry leg always runs on its own jittered mesh)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--no-matfree", action="store_true", help="skip the matrix-free CG leg (reported alongside, not the headline)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the general-geometry leg and the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs outside it: the check solve to 1e-10, the matrix-free CG, the CPU "
+                         "baseline, the general-geometry leg and the other BASELINE configurations (the --no-* switches drop single legs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the solves to 1e-10")
+    ap.add_argument("--no-matfree", action="store_true", help="with --full: skip the matrix-free CG leg (reported alongside, not the headline)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the general-geometry leg and the other BASELINE configurations")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64; arrays over "
                          f"{DUMP_SAMPLE} entries as a fixed seeded sample): matrix_values, solution, solve_info")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:       # a plain run does what its headline line needs and nothing else
+        args.no_cpu_baseline = args.no_check = args.no_matfree = args.no_extra = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     from pynama_amd import _lib
     from pynama_amd.common.comm import get_world

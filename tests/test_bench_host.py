@@ -1,10 +1,12 @@
 """bench.py's host-side pieces (no GPU): the byte models of SURVEY.md 8(d), the SELL entry count, the rule that PMC traffic is only
-quoted for the kernel sources it was measured on, and the tetrahedral test mesh of configuration C5."""
+quoted for the kernel sources it was measured on, the legs a plain and a --full run take, and the tetrahedral test mesh of
+configuration C5."""
 import json
 import os
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -94,6 +96,18 @@ def test_dump_outputs_writes_float64_within_budget_and_samples_repeatably(tmp_pa
     bench.dump_outputs(str(tmp_path / "c"), ctx, 0, 1, _FakeInfo(), 1, 2)
     assert sorted(os.listdir(tmp_path / "c")) == ["matrix_values_rank1.npy", "solution_rank1.npy", "solve_info_rank1.npy"]
     assert np.load(tmp_path / "c" / "matrix_values_rank1.npy").size == 500
+
+
+def test_plain_run_is_the_headline_alone_and_full_runs_every_leg():
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert (plain.gpus, plain.steps, plain.warmup, plain.full) == (1, 3, 2, False)
+    assert plain.no_check and plain.no_matfree and plain.no_cpu_baseline and plain.no_extra
+    full = bench.parse_args(["--full"])
+    assert not (full.no_check or full.no_matfree or full.no_cpu_baseline or full.no_extra)
+    some = bench.parse_args(["--full", "--no-cpu-baseline", "--no-extra"])
+    assert some.no_cpu_baseline and some.no_extra and not (some.no_check or some.no_matfree)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
 
 
 def test_dump_budget_is_under_64_mb():

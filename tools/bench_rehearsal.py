@@ -20,6 +20,6 @@ with tempfile.NamedTemporaryFile(dir="/dev/shm", prefix="pynama_bench_") as f:
     procs = []
     for r in range(n):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(n), LOCAL_RANK="0", PYNAMA_SHM_TRANSPORT=f.name, PYNAMA_SHM_CAP=str(cap))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + sys.argv[2:], env=env))
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--full"] + sys.argv[2:], env=env))
     rc = [p.wait() for p in procs]
 sys.exit(max(rc))

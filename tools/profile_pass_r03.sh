@@ -29,9 +29,9 @@ sq() {      # sq <tag> <kernel substring> <command...>
 PART=${PART:-all}     # gpurun calls are limited to 20 minutes: PART=a (bench, headline traffic), b (second-order legs), c (C3, C5)
 if [ "$PART" = all ] || [ "$PART" = a ]; then
 # headline alone, then the whole default run
-rocprofv3 --kernel-trace --stats -d $O/p_s -o s -- python3 bench.py --no-cpu-baseline --no-extra > $O/${TAG}_bench_10Mdof.json 2> $O/${TAG}_bench.err
+rocprofv3 --kernel-trace --stats -d $O/p_s -o s -- python3 bench.py --full --no-cpu-baseline --no-extra > $O/${TAG}_bench_10Mdof.json 2> $O/${TAG}_bench.err
 $S stats $(db $O/p_s) $O/${TAG}_bench_10Mdof_kernel_stats.csv $O/${TAG}_bench_10Mdof_summary.md; rm -rf $O/p_s
-rocprofv3 --kernel-trace --stats -d $O/p_s -o s -- python3 bench.py --no-cpu-baseline > $O/${TAG}_bench_all_configs.json 2> $O/${TAG}_bench_all.err
+rocprofv3 --kernel-trace --stats -d $O/p_s -o s -- python3 bench.py --full --no-cpu-baseline > $O/${TAG}_bench_all_configs.json 2> $O/${TAG}_bench_all.err
 $S stats $(db $O/p_s) $O/${TAG}_bench_all_configs_kernel_stats.csv $O/${TAG}_bench_all_configs_summary.md; rm -rf $O/p_s
 echo "bench stats done"
 traffic traffic 1 python3 tools/prof_case.py cg 215 3
