@@ -258,11 +258,13 @@ int pyn_elem_operator_local(pyn_ctx* ctx, int rule, int br, int bc, int nterms, 
  * base_problem.py:481 "Rw*vort + Krhs*vel"). */
 int pyn_spmv(pyn_ctx* ctx, int mat_id, int x_vec, int y_vec);
 /* Matrix-free operators: y = A x WITHOUT an assembled matrix (PETSc analogue: a MATSHELL).  Element matrices are recomputed
- * on the fly (Spectral.getElemKLEMatrices, spectral.py:120-153) and applied per element; needs a Q1 hexahedral mesh with
- * structured topology (pyn_mesh_topology == lattice), errors otherwise.
+ * on the fly (Spectral.getElemKLEMatrices, spectral.py:120-153) and applied per element; needs a structured mesh, errors otherwise:
+ *   Q1 hexahedra (pyn_mesh_topology == lattice)            both operators
+ *   second-order lattices (lattice-ngl3), 2-D and 3-D      PYN_MATFREE_KLE only, and only when every cell is affine
+ *                                                          (parallelograms / parallelepipeds; sum-factorised, pyn_matfree_ho3.hip)
  *   PYN_MATFREE_LAPLACE  the scalar Laplacian pyn_assemble_scalar(PYN_FORM_LAPLACE) builds (1 DOF per node)
- *   PYN_MATFREE_KLE      the K of pyn_assemble_kle (3 DOFs per node); alpha_d / alpha_w are that call's penalty weights
- *                        (1e3 / 1e2 in the reference, spectral.py:152-153)
+ *   PYN_MATFREE_KLE      the K of pyn_assemble_kle (dim DOFs per node: 3 on Q1 hexahedra, 2 / 3 on second-order meshes);
+ *                        alpha_d / alpha_w are that call's penalty weights (1e3 / 1e2 in the reference, spectral.py:152-153)
  * pyn_matfree_set defines the operator from the mesh, the element tables and a SNAPSHOT of the current Dirichlet mask
  * (imposed rows identity, imposed columns eliminated, base_problem.py:531-549): call it next to the assembly it mirrors;
  * later pyn_bc_set calls do not change it. */

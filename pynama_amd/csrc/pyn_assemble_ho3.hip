@@ -1171,6 +1171,24 @@ int ho3_prepare(pyn_ctx* c, bool* ok) {
 
 }  // namespace
 
+// For the matrix-free KLE operator (pyn_matfree_ho3.hip): is every cell a parallelogram / parallelepiped, and axis-aligned?  hc[r][bits]:
+// derivative along reference axis r of the Q1 function of the corner at lattice offsets 2 * bit d (HrsCoo at the first full-rule point)
+int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]) {
+  *affine = *diag = false;
+  const Ho3Lattice& L = c->ho3;
+  if (!L.valid || L.ngl != 3 || c->quad[0].ngp < 1 || !c->quad[0].HrsCoo) return PYN_OK;
+  bool ok = false;
+  PYN_TRY(ho3_prepare(c, &ok));
+  *affine = L.affine == 1;
+  *diag = L.diag == 1;
+  const int dim = L.dim, nc = 1 << dim;
+  double h[3 * 8];
+  PYN_HIP(hipMemcpy(h, c->quad[0].HrsCoo, (size_t)dim * nc * sizeof(double), hipMemcpyDeviceToHost));
+  for (int r = 0; r < dim; ++r)
+    for (int cn = 0; cn < nc; ++cn) hc[r][dim == 2 ? CB2[cn] : CB3[cn]] = h[r * nc + cn];
+  return PYN_OK;
+}
+
 void pyn_ho3_release(pyn_ctx* c) {
   Ho3Lattice& L = c->ho3;
   (void)hipFree(L.d_P);

@@ -162,6 +162,17 @@ struct Ho3Lattice {
   int runflag_R = 0;            // ... and this run length
 };
 
+// Matrix-free KLE on second-order lattices (pyn_matfree_ho3.hip): the 1-D factors of a rule (M = sum w h h, D = sum w h' h,
+// S = sum w h' h') written as B^T B, G^T B, G^T G with B, G [points][3] -- values and derivatives of the 3 nodal functions at the
+// rule's points, the square root of the weight folded in -- and C with J[r] = sum_d C[r][d] E_d on an affine cell (E_d = the cell's
+// edge along lattice axis d; C = the Q1 corner derivatives at a point, summed over the corners at offset 2 along d)
+struct Ho3MfBasis {
+  double Bf[3][3], Gf[3][3];   // full rule (Gauss 3)
+  double Br[2][3], Gr[2][3];   // reduced rule (Gauss 2)
+  double C[3][3];              // [reference axis][lattice axis]
+  int diag = 0;                // every cell's J^-1 is diagonal (axis-aligned boxes)
+};
+
 struct SellShape {
   int br = 0, bc = 0, maxw = 0;
   int64_t ns = 0, total = 0;
@@ -224,6 +235,7 @@ struct pyn_ctx {
   bool mf_set[3] = {false, false, false};
   uint8_t* mf_mask[3] = {nullptr, nullptr, nullptr};   // null = no imposed DOF
   double mf_alpha_d = 0.0, mf_alpha_w = 0.0;
+  Ho3MfBasis mf_ho3;     // the KLE operator on a second-order lattice (pyn_matfree_ho3.hip): its 1-D point bases, set with mf_set[KLE]
   int64_t bc_stamp = 0;  // bumped by every pyn_bc_set
   uint8_t* d_bcmask = nullptr;
 
@@ -336,5 +348,10 @@ int pyn_ho3_detect(pyn_ctx* c, const ConnAt& at);
 void pyn_ho3_release(pyn_ctx* c);
 int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double* H, const double* Hrs);
 int pyn_ho3_symbolic(pyn_ctx* c, bool* done);
+int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]);   // every cell affine / axis-aligned; corner derivatives
+// matrix-free KLE operator on second-order lattices (pyn_matfree_ho3.hip)
+inline bool pyn_ho3_matfree_mesh(const pyn_ctx* c) { return c->ho3.valid && c->ho3.ngl == 3; }
+int pyn_ho3_matfree_set(pyn_ctx* c, int op);   // checks the mesh and tables, fills c->mf_ho3
+int pyn_ho3_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);
 int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
 int pyn_assemble_ho3_operator(pyn_ctx* c, int rule, int br, int bc, int nterms, const int32_t* terms, const double* coef, double* M, bool* handled);

@@ -695,15 +695,25 @@ extern "C" int pyn_spmv(pyn_ctx* c, int mat_id, int xv, int yv) {
 
 // -----------------------------------------------------------------------------------------------
 static int matfree_product(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
+  if (op == PYN_MATFREE_KLE && pyn_ho3_matfree_mesh(c)) return pyn_ho3_matfree_spmv(c, x, y, dot, grid_out);
   return op == PYN_MATFREE_KLE ? pyn_lattice_matfree_kle_spmv(c, x, y, dot, grid_out) : pyn_lattice_matfree_spmv(c, x, y, dot, grid_out);
+}
+
+// DOFs per node of a matrix-free operator: the KLE operator has dim of them (3 on Q1 hexahedra, 2 or 3 on second-order lattices)
+static int matfree_bs(const pyn_ctx* c, int op) {
+  if (op != PYN_MATFREE_KLE) return 1;
+  return pyn_ho3_matfree_mesh(c) ? c->ho3.dim : 3;
 }
 
 extern "C" int pyn_matfree_set(pyn_ctx* c, int op, double alpha_d, double alpha_w) {
   PYN_CHECK(c, "NULL context");
   PYN_CHECK(op == PYN_MATFREE_LAPLACE || op == PYN_MATFREE_KLE, "unknown matrix-free operator %d", op);
-  PYN_CHECK(pyn_lattice_matfree_supported(c), "matrix-free operator: needs a Q1 hexahedral mesh with structured topology and the "
-                                               "full-rule tables");
-  const int bs = op == PYN_MATFREE_KLE ? 3 : 1;
+  if (pyn_ho3_matfree_mesh(c))   // second-order lattice: the KLE operator on affine cells (pyn_matfree_ho3.hip)
+    PYN_TRY(pyn_ho3_matfree_set(c, op));
+  else
+    PYN_CHECK(pyn_lattice_matfree_supported(c), "matrix-free operator: needs a Q1 hexahedral mesh with structured topology and the "
+                                                 "full-rule tables");
+  const int bs = matfree_bs(c, op);
   PYN_CHECK(!c->d_bcmask || c->bc_ndof == bs, "matrix-free operator %d: the current Dirichlet mask must have %d DOF(s) per node", op, bs);
   PYN_HIP(hipSetDevice(c->device));
   (void)hipFree(c->mf_mask[op]);
@@ -729,7 +739,7 @@ extern "C" int pyn_matfree_apply(pyn_ctx* c, int op, int xv, int yv) {
   PYN_TRY(pyn_check_vec(c, xv, "pyn_matfree_apply x"));
   PYN_TRY(pyn_check_vec(c, yv, "pyn_matfree_apply y"));
   PYN_CHECK(xv != yv, "x and y must differ");
-  const int bs = op == PYN_MATFREE_KLE ? 3 : 1;
+  const int bs = matfree_bs(c, op);
   PYN_CHECK(c->vecs[xv].bs == bs && c->vecs[yv].bs == bs, "this matrix-free operator acts on vectors of block size %d", bs);
   PYN_HIP(hipSetDevice(c->device));
   PYN_TRY(pyn_halo_exchange(c, c->vecs[xv].d, bs));
@@ -880,7 +890,9 @@ static int solve_cg_sr(pyn_ctx* c, DMat& A, const double* b, double* x, const py
   const int check = o.fixed_iters > 0 ? 0 : 1;
   const bool multi = pyn_has_comm(c);
   const SellShape* S = sell ? pyn_sell_shape(c, A) : nullptr;
-  const bool overlap = multi && !c->neigh.empty() && !c->detached && (mf || (S && S->int_begin >= 0)) && !getenv("PYNAMA_NO_OVERLAP");
+  // (the second-order matrix-free operator has no interior / boundary split: it takes the blocking exchange)
+  const bool overlap = multi && !c->neigh.empty() && !c->detached && (mf ? !pyn_ho3_matfree_mesh(c) : (S && S->int_begin >= 0)) &&
+                       !getenv("PYNAMA_NO_OVERLAP");
   if (getenv("PYNAMA_OVERLAP_REQUIRE")) PYN_CHECK(overlap, "halo/SpMV overlap not engaged (tests)");
   const bool no_fuse = getenv("PYNAMA_NO_SCALAR_FUSE") != nullptr;   // diagnostics: scalar step in its own launch
 
@@ -1369,7 +1381,7 @@ extern "C" int pyn_solve(pyn_ctx* c, int mat_id, int bv, int xv, const pyn_solve
   if (opts->matfree) {
     // the shell operator must BE the assembled matrix (which keeps supplying the Jacobi diagonal and the exit check):
     // compare both products on b before iterating
-    PYN_CHECK(A.br == (opts->matfree == PYN_MATFREE_KLE ? 3 : 1), "matrix-free operator: block size of the matrix does not match");
+    PYN_CHECK(A.br == matfree_bs(c, opts->matfree), "matrix-free operator: block size of the matrix does not match");
     const int64_t n1 = c->n_owned * A.br;
     PYN_TRY(pyn_ensure_work(c, (size_t)2 * n1 * sizeof(double)));
     double *w0 = c->d_work, *w1 = c->d_work + n1;

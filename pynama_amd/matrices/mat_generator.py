@@ -13,7 +13,13 @@ import numpy as np
 
 from pynama_amd import _lib
 from pynama_amd.common.comm import get_world
+from pynama_amd.common.options import Options
 from pynama_amd.vectors import Vec
+
+
+def _flag_set(o, key):
+    """a PETSc-style boolean option: present and not 0 / false / no"""
+    return o.hasName(key) and str(o.getString(key, '1')).lower() not in ('0', 'false', 'no')
 
 
 class DeviceMat:
@@ -197,11 +203,19 @@ class Mat:
         # (the library picks the kernel: plan-free on lattices of parallelepipeds, 3x3x3-node patch plans otherwise)
         self.ctx.assemble_kle(alpha_d, alpha_w, self.K.id, self.Krhs.id, self.Rw.id,
                               self.Rd.id if with_rd else -1, variant)
-        # K also exists in matrix-free form on structured Q1 hex meshes (KspSolver -pynama_mat_free)
+        # K also exists in matrix-free form on structured Q1 hex meshes (KspSolver -pynama_mat_free), and, opt-in with
+        # -pynama_mat_free_ngl3, on second-order structured meshes of affine cells
         self.K.matfree = None
-        if self.dim == 3 and elem.nnode == 8 and self.ctx.mesh_topology()[0] == "lattice":
+        topo = self.ctx.mesh_topology()[0]
+        if self.dim == 3 and elem.nnode == 8 and topo == "lattice":
             self.ctx.matfree_set(_lib.MATFREE_KLE, alpha_d, alpha_w)      # snapshot of THIS assembly's Dirichlet mask
             self.K.matfree = _lib.MATFREE_KLE
+        elif topo == "lattice-ngl3" and _flag_set(Options(), 'pynama_mat_free_ngl3'):
+            try:
+                self.ctx.matfree_set(_lib.MATFREE_KLE, alpha_d, alpha_w)
+                self.K.matfree = _lib.MATFREE_KLE
+            except _lib.PynamaHipError as e:                              # e.g. a cell that is not affine
+                logging.getLogger("Mat").info(f"-pynama_mat_free_ngl3: K stays assembled only ({e})")
 
     def createNonZeroIndex(self, d_nnz, o_nnz, dim1, dim2):
         di_nnz = [x * dim1 for x in d_nnz for d in range(dim2)]
