@@ -313,6 +313,16 @@ int pyn_solve(pyn_ctx* ctx, int mat_id, int b_vec, int x_vec, const pyn_solve_op
  * PYN_CONVERGED_ITS as PETSc reports for preonly; info->true_resid as in pyn_solve.  A zero pivot is PYN_EINVAL. */
 int pyn_direct_max_rows(void);
 int pyn_solve_direct(pyn_ctx* ctx, int mat_id, int b_vec, int x_vec, pyn_solve_info* info);
+/* Direct solve of a BANDED system above the dense limit: LU with partial pivoting in band storage (LAPACK gbtrf / gbtrs semantics),
+ * in the existing numbering (no reordering).  Stands for the same `-ksp_type preonly -pc_type lu` (src/solver/ksp_solver.py:13-16)
+ * on structured meshes, whose stiffness is narrowly banded in the lattice numbering.  pyn_direct_band_info: the scalar
+ * half-bandwidths kl, ku of the matrix (from the node graph: (max node distance) b + b - 1) and the bytes its factors would take;
+ * nothing is allocated.  pyn_solve_direct_band: factors cached in the matrix until its values change (refactored after), then
+ * permuted forward / backward banded substitution; info as pyn_solve_direct (iters = 1, PYN_CONVERGED_ITS, true_resid).  One rank,
+ * no ghost nodes, br == bc, not a compact pyn_mat_create_rhs matrix; factors above max_bytes or above the free device memory, and
+ * a zero pivot, are PYN_EINVAL. */
+int pyn_direct_band_info(pyn_ctx* ctx, int mat_id, int64_t* kl, int64_t* ku, int64_t* bytes);
+int pyn_solve_direct_band(pyn_ctx* ctx, int mat_id, int b_vec, int x_vec, int64_t max_bytes, pyn_solve_info* info);
 
 /* ---- timers -------------------------------------------------------------------------------
  * Device time (HIP events on the context stream) of the last call of each phase, in ms.

@@ -110,6 +110,8 @@ SIGNATURES = {
     "pyn_solve": [_P, _I, _I, _I, C.POINTER(SolveOpts), C.POINTER(SolveInfo)],
     "pyn_direct_max_rows": [],
     "pyn_solve_direct": [_P, _I, _I, _I, C.POINTER(SolveInfo)],
+    "pyn_direct_band_info": [_P, _I, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L)],
+    "pyn_solve_direct_band": [_P, _I, _I, _I, _L, C.POINTER(SolveInfo)],
     "pyn_timers_get": [_P, _pf64, _I],
 }
 
@@ -539,6 +541,18 @@ class Context:
         """dense LU with partial pivoting (small systems, one rank); the factors stay cached until the matrix changes"""
         info = SolveInfo()
         _check(self.lib.pyn_solve_direct(self.h, mid, b, x, C.byref(info)))
+        return info
+
+    def direct_band_info(self, mid):
+        """(kl, ku, bytes): half-bandwidths of the matrix in the current numbering and the bytes of its banded LU factors"""
+        kl, ku, nb = _L(0), _L(0), _L(0)
+        _check(self.lib.pyn_direct_band_info(self.h, mid, C.byref(kl), C.byref(ku), C.byref(nb)))
+        return kl.value, ku.value, nb.value
+
+    def solve_direct_band(self, mid, b, x, max_bytes=16 << 30) -> SolveInfo:
+        """banded LU with partial pivoting (one rank, factors of at most max_bytes); cached until the matrix changes"""
+        info = SolveInfo()
+        _check(self.lib.pyn_solve_direct_band(self.h, mid, b, x, int(max_bytes), C.byref(info)))
         return info
 
     def timers(self):

@@ -91,6 +91,10 @@ struct DMat {
   int* lu_piv = nullptr;       // [n] row interchanges + [1] singular-column flag + [n] the same as a gather
   int64_t lu_n = 0;            // order the two buffers were sized for
   bool lu_valid = false;
+  double* band = nullptr;      // banded LU factors (pyn_direct_band.hip): [n][2 kl + ku + 64] row-major, layout there
+  int* band_perm = nullptr;    // per panel of 64 columns: the window's row interchanges as a gather [64 + kl], + [1] singular-column flag
+  int64_t band_n = 0, band_kl = 0, band_ku = 0;   // shape the two buffers were sized for
+  bool band_valid = false;
   // "imposed-column" matrices (Krhs / Arhs of an assembly) are zero except in rows next to imposed nodes.  rhs_clean records for
   // which Dirichlet set (pyn_ctx::bc_stamp) the stored values are known to be exactly that matrix -- or all zero (PYN_RHS_ANY: a fresh
   // or zeroed matrix fits every set); the lattice kernels then leave the zero blocks of tiles without imposed nodes unwritten.
@@ -106,7 +110,7 @@ struct DMat {
   int32_t* c_cptr = nullptr;   // [c_nr + 1] first block of every stored row
   bool live = false;
   void touch() {               // the values are about to change
-    sell_valid = prod_ready = dinv_valid = lu_valid = false;
+    sell_valid = prod_ready = dinv_valid = lu_valid = band_valid = false;
     rhs_clean = -2;
   }
   void release_lu() {
@@ -116,6 +120,15 @@ struct DMat {
     lu_piv = nullptr;
     lu_n = 0;
     lu_valid = false;
+    release_band();
+  }
+  void release_band() {
+    (void)hipFree(band);
+    (void)hipFree(band_perm);
+    band = nullptr;
+    band_perm = nullptr;
+    band_n = band_kl = band_ku = 0;
+    band_valid = false;
   }
 };
 

@@ -28,6 +28,15 @@ GMRES(30)+Jacobi otherwise or when PCG breaks down (an indefinite operator, e.g.
 path -- a negative converged reason or a true residual above 1e-8 raises instead of returning
 garbage.  The substitution is logged; it satisfies the reference's own analytic assertions
 (src/tests/test_solver.py:20-62).
+
+``-pynama_direct_band`` (opt-in, off by default; PETSc's analogue is picking a factorisation package with
+``-pc_factor_mat_solver_type``): above the dense limit, ``preonly`` + ``lu``/``cholesky`` on one rank factors the matrix in band
+storage instead (``pyn_solve_direct_band``: LU with partial pivoting, gbtrf semantics, the existing numbering, factors cached per
+matrix version) -- a real direct solve for structured meshes, whose band grows with the mesh face, and for the indefinite
+``K + Kfs`` as well.  It is taken unless ``-pynama_mat_free`` was asked for explicitly (a matrix-free tag on ``Mat.K`` does not stop
+it: the factors replace the shell) and while the factors fit ``-pynama_direct_band_max_gb`` (default 16 GB).  When the band does not
+fit (the cap, the free device memory: e.g. imported meshes, whose numbering is not banded) the reason is logged and the Krylov
+substitute above runs; a zero pivot raises.
 """
 import logging
 
@@ -51,6 +60,8 @@ class KspSolver(object):
         self.norm_type = "preconditioned"
         self.mat_free = None             # None: automatic (the shell when the matrix carries one); True / False: -pynama_mat_free
         self.direct_max_rows = 8192      # preonly/lu: dense LU up to this many rows (the library's limit), the Krylov substitute above
+        self.direct_band = False         # -pynama_direct_band: preonly/lu above that limit as a banded LU (one rank)
+        self.direct_band_max_gb = 16.0   # -pynama_direct_band_max_gb: cap on the band factors' storage (1e9 bytes)
         self.info = None
         self._symmetric = None
 
@@ -84,6 +95,9 @@ class KspSolver(object):
         self.mat_free = (str(o.getString('pynama_mat_free', '1')).lower() not in ('0', 'false', 'no')
                          if o.hasName('pynama_mat_free') else None)
         self.direct_max_rows = o.getInt('pynama_direct_max_rows', self.direct_max_rows)
+        if o.hasName('pynama_direct_band'):
+            self.direct_band = str(o.getString('pynama_direct_band', '1')).lower() not in ('0', 'false', 'no')
+        self.direct_band_max_gb = o.getReal('pynama_direct_band_max_gb', self.direct_band_max_gb)
         if o.hasName('ksp_gmres_modifiedgramschmidt'):
             self.gmres_orthog = 2
         else:
@@ -157,6 +171,8 @@ class KspSolver(object):
             if info.reason < 0 or not (info.true_resid <= 1e-8):
                 raise RuntimeError(f"preonly/lu: dense LU of {n_rows} rows left a true residual of {info.true_resid:.3e} "
                                    "(the matrix is singular to working precision)")
+        elif self.ksp_type == 'preonly' and (info := self._solve_band(A, b, x, n_rows)) is not None:
+            self.shell_used = False
         elif self.ksp_type == 'preonly':
             if getattr(self, "_symmetric", None) is None:
                 self._symmetric = A.br == A.bc and self._probe_symmetry(A)
@@ -184,6 +200,38 @@ class KspSolver(object):
             if info.reason < 0 and self.logger:      # PETSc does not raise either (unless -ksp_error_if_not_converged)
                 self.logger.error(f"KSP did not converge: reason {info.reason} after {info.iters} iterations, residual {info.rnorm:.3e}")
         self.info = info
+        return info
+
+    def _solve_band(self, A, b, x, n_rows):
+        """-pynama_direct_band: the banded LU, or None (with the reason logged) when it does not apply or does not fit"""
+        ctx = A.ctx
+        if not self.direct_band or self.mat_free:
+            return None
+        why = None
+        if ctx.nranks != 1 or ctx.n_ghost != 0:
+            why = f"{ctx.nranks} ranks (the banded LU runs on one)"
+        elif A.br != A.bc:
+            why = f"a {A.br} x {A.bc} block matrix is not square"
+        else:
+            cap = int(self.direct_band_max_gb * 1e9)
+            kl, ku, nbytes = ctx.direct_band_info(A.id)
+            if nbytes > cap:
+                why = (f"its factors (kl {kl}, ku {ku}, {n_rows} rows) take {nbytes / 1e9:.3g} GB, above "
+                       f"-pynama_direct_band_max_gb {self.direct_band_max_gb:g}")
+            else:
+                try:
+                    info = ctx.solve_direct_band(A.id, b.id, x.id, max_bytes=cap)
+                except _lib.PynamaHipError as e:
+                    if "zero pivot" in str(e):
+                        raise
+                    why = str(e)
+        if why is not None:
+            self.logger and self.logger.warning(f"preonly/lu: no banded LU: {why}; Krylov substitute instead")
+            return None
+        if info.reason < 0 or not (info.true_resid <= 1e-8):
+            raise RuntimeError(f"preonly/lu: banded LU of {n_rows} rows left a true residual of {info.true_resid:.3e} "
+                               "(the matrix is singular to working precision)")
+        self.logger and self.logger.info(f"preonly/lu: banded LU of {n_rows} rows (kl {kl}, ku {ku})")
         return info
 
     __call__ = solve
