@@ -48,7 +48,7 @@ enum {
 
 /* Krylov method / preconditioner / norm (PETSc option names in comments) */
 enum { PYN_KSP_CG = 0, PYN_KSP_GMRES = 1 };                 /* -ksp_type cg | gmres            */
-enum { PYN_PC_NONE = 0, PYN_PC_JACOBI = 1 };                /* -pc_type none | jacobi          */
+enum { PYN_PC_NONE = 0, PYN_PC_JACOBI = 1, PYN_PC_MG = 2 };  /* -pc_type none | jacobi | mg     */
 enum { PYN_NORM_PRECONDITIONED = 0, PYN_NORM_UNPRECONDITIONED = 1, PYN_NORM_NATURAL = 2 };
 /* converged reasons, numbered as PETSc's KSPConvergedReason */
 enum { PYN_CONVERGED_RTOL = 2, PYN_CONVERGED_ATOL = 3, PYN_CONVERGED_ITS = 4,
@@ -323,6 +323,36 @@ int pyn_solve_direct(pyn_ctx* ctx, int mat_id, int b_vec, int x_vec, pyn_solve_i
  * a zero pivot, are PYN_EINVAL. */
 int pyn_direct_band_info(pyn_ctx* ctx, int mat_id, int64_t* kl, int64_t* ku, int64_t* bytes);
 int pyn_solve_direct_band(pyn_ctx* ctx, int mat_id, int b_vec, int x_vec, int64_t max_bytes, pyn_solve_info* info);
+
+/* Geometric multigrid preconditioner for CG (PETSc's -pc_type mg) on structured lattice meshes: pyn_solve with PYN_KSP_CG and
+ * PYN_PC_MG runs PCG with one V-cycle per iteration.  One rank, no ghost nodes, pyn_mesh_topology kinds 1 (Q1 hexahedra), 2 (ngl 3,
+ * 2-D / 3-D) and 3 (Q1 quadrilaterals), square blocks of 1..3 DOFs per node, not a compact pyn_mat_create_rhs matrix.  Level 0 is the
+ * matrix; every coarser level halves the cells of every axis (ngl 3 -> Q1 on the same node lattice first) while all cell counts are
+ * even, the level has more than coarse_max_rows rows and fewer than max_levels levels exist.  A_c = P^T A P with P the tensor-product
+ * linear interpolation per component, zero in decoupled fine rows (rows whose only non-zero is the diagonal: the Dirichlet rows) and
+ * in decoupled coarse columns (a coarse DOF is decoupled when its coincident fine DOF is; its row is that fine diagonal).  Smoother:
+ * Chebyshev of degree smooth_degree with Jacobi scaling on [esteig_min, esteig_max] x lambda, lambda estimating lambda_max(D^-1 A)
+ * from esteig_its seeded CG steps; the same polynomial before and after the coarse correction (symmetric V-cycle), decoupled rows
+ * z = r / a_ii.  Coarsest level: dense LU (at most pyn_direct_max_rows() rows).  The hierarchy is cached in the matrix until its
+ * values change; pyn_solve builds it with the last options (the defaults when there are none).  A zero field takes its default. */
+#define PYN_MG_MAX_LEVELS 16
+typedef struct pyn_mg_opts {
+  int max_levels;        /* -pc_mg_levels: levels including the matrix itself (default PYN_MG_MAX_LEVELS) */
+  int smooth_degree;     /* -mg_levels_ksp_max_it: Chebyshev degree (default 2) */
+  int coarse_max_rows;   /* stop coarsening at this many rows (default 4096) */
+  int esteig_its;        /* CG steps of the eigenvalue estimate (default 10) */
+  double esteig_min, esteig_max;   /* Chebyshev interval as factors of the estimate (defaults 0.1, 1.1) */
+} pyn_mg_opts;
+/* builds the hierarchy (again only when the options or the matrix values changed since the last build) */
+int pyn_mg_setup(pyn_ctx* ctx, int mat_id, const pyn_mg_opts* opts);
+/* levels; rows[PYN_MG_MAX_LEVELS] per level; lambda[PYN_MG_MAX_LEVELS] per smoothed level (0 on the coarsest); host time of the last
+ * build (ms); number of builds so far (any pointer may be NULL) */
+int pyn_mg_info(pyn_ctx* ctx, int mat_id, int* nlevels, int64_t* rows, double* lambda, double* setup_ms, int* builds);
+/* z = M^-1 r: one V-cycle with the assembled matrix at level 0 */
+int pyn_mg_apply(pyn_ctx* ctx, int mat_id, int r_vec, int z_vec);
+/* stencil of coarse level `level` (1 .. nlevels-1): [node][3^dim][b][b] doubles, nodes lexicographic (x fastest), stencil entry
+ * k = sum_a (o_a + 1) 3^a for the node offset o in {-1, 0, 1}^dim (x first) */
+int pyn_mg_level_get(pyn_ctx* ctx, int mat_id, int level, double* out);
 
 /* ---- timers -------------------------------------------------------------------------------
  * Device time (HIP events on the context stream) of the last call of each phase, in ms.

@@ -21,7 +21,8 @@ Q_FULL, Q_RED, Q_NODAL = 0, 1, 2
 FORM_LAPLACE, FORM_MASS_NODAL, FORM_MASS_FULL, FORM_KLE = 0, 1, 2, 3
 KSP_CG, KSP_GMRES = 0, 1
 MATFREE_OFF, MATFREE_LAPLACE, MATFREE_KLE = 0, 1, 2
-PC_NONE, PC_JACOBI = 0, 1
+PC_NONE, PC_JACOBI, PC_MG = 0, 1, 2
+MG_MAX_LEVELS = 16
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
 T_SYMBOLIC, T_ASSEMBLE, T_SPMV, T_SOLVE = 0, 1, 2, 3
 
@@ -34,6 +35,12 @@ class SolveOpts(C.Structure):
     _fields_ = [("method", C.c_int), ("pc", C.c_int), ("norm_type", C.c_int), ("maxit", C.c_int),
                 ("restart", C.c_int), ("fixed_iters", C.c_int), ("profile", C.c_int), ("cg_variant", C.c_int),
                 ("gmres_orthog", C.c_int), ("matfree", C.c_int), ("rtol", C.c_double), ("atol", C.c_double), ("dtol", C.c_double)]
+
+
+class MgOpts(C.Structure):
+    """pyn_mg_opts: a zero field takes the library's default"""
+    _fields_ = [("max_levels", C.c_int), ("smooth_degree", C.c_int), ("coarse_max_rows", C.c_int), ("esteig_its", C.c_int),
+                ("esteig_min", C.c_double), ("esteig_max", C.c_double)]
 
 
 class SolveInfo(C.Structure):
@@ -112,6 +119,10 @@ SIGNATURES = {
     "pyn_solve_direct": [_P, _I, _I, _I, C.POINTER(SolveInfo)],
     "pyn_direct_band_info": [_P, _I, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L)],
     "pyn_solve_direct_band": [_P, _I, _I, _I, _L, C.POINTER(SolveInfo)],
+    "pyn_mg_setup": [_P, _I, C.POINTER(MgOpts)],
+    "pyn_mg_info": [_P, _I, C.POINTER(_I), _pi64, _pf64, C.POINTER(_D), C.POINTER(_I)],
+    "pyn_mg_apply": [_P, _I, _I, _I],
+    "pyn_mg_level_get": [_P, _I, _I, _pf64],
     "pyn_timers_get": [_P, _pf64, _I],
 }
 
@@ -554,6 +565,31 @@ class Context:
         info = SolveInfo()
         _check(self.lib.pyn_solve_direct_band(self.h, mid, b, x, int(max_bytes), C.byref(info)))
         return info
+
+    def mg_setup(self, mid, max_levels=0, smooth_degree=0, coarse_max_rows=0, esteig_its=0, esteig_min=0.0, esteig_max=0.0):
+        """geometric multigrid hierarchy of the matrix (PC_MG); rebuilt only when the options or the values changed.  0 = default"""
+        o = MgOpts(max_levels, smooth_degree, coarse_max_rows, esteig_its, esteig_min, esteig_max)
+        _check(self.lib.pyn_mg_setup(self.h, mid, C.byref(o)))
+
+    def mg_info(self, mid):
+        """{'levels', 'rows' (per level), 'lambda' (lambda_max(D^-1 A) estimate per smoothed level), 'setup_ms', 'builds'}"""
+        n, ms, nb = _I(0), _D(0), _I(0)
+        rows, lam = np.zeros(MG_MAX_LEVELS, np.int64), np.zeros(MG_MAX_LEVELS)
+        _check(self.lib.pyn_mg_info(self.h, mid, C.byref(n), rows, lam, C.byref(ms), C.byref(nb)))
+        k = n.value
+        return {"levels": k, "rows": [int(r) for r in rows[:k]], "lambda": [float(v) for v in lam[:k]], "setup_ms": ms.value,
+                "builds": nb.value}
+
+    def mg_apply(self, mid, r, z):
+        """z = M^-1 r: one V-cycle (assembled matrix at level 0)"""
+        _check(self.lib.pyn_mg_apply(self.h, mid, r, z))
+
+    def mg_level_get(self, mid, level, b):
+        """stencil of coarse level `level`: [node][3^dim][b][b] (nodes lexicographic, offsets x fastest)"""
+        rows = self.mg_info(mid)["rows"][level]
+        out = np.empty(rows * 3 ** self.dim * b)
+        _check(self.lib.pyn_mg_level_get(self.h, mid, level, out))
+        return out.reshape(rows // b, 3 ** self.dim, b, b)
 
     def timers(self):
         t = np.zeros(8)

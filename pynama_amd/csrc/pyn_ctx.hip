@@ -145,6 +145,7 @@ extern "C" int pyn_ctx_destroy(pyn_ctx* c) {
     (void)hipFree(m.sell_val);
     (void)hipFree(m.dinv);
     m.release_lu();
+    m.release_mg();
     pyn_rhs_release(m);
   }
   (void)hipFree(c->d_esel);
@@ -899,6 +900,7 @@ extern "C" int pyn_mat_destroy(pyn_ctx* c, int id) {
   (void)hipFree(m.sell_val);
   (void)hipFree(m.dinv);
   m.release_lu();
+  m.release_mg();
   pyn_rhs_release(m);
   m = DMat();   // live = false: the handle is dead, its slot is not reused (handles stay stable)
   return PYN_OK;

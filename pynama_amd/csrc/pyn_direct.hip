@@ -258,6 +258,51 @@ __global__ void __launch_bounds__(1024) direct_resid_kernel(const double* __rest
 
 }  // namespace
 
+// blocked LU with partial pivoting of the dense n x n matrix D in place; piv: [n] interchanges, [1] singular-column flag, [n] the
+// interchanges as a gather.  Shared by the direct solve and the coarsest level of the multigrid hierarchy (pyn_mg.hip).
+int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n) {
+  hipStream_t s = c->stream;
+  int* flag = piv + n;
+  PYN_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+  for (int kb = 0; kb < (int)n; kb += LU_NB) {
+    const int nb = (int)std::min<int64_t>(LU_NB, n - kb), kend = kb + nb;
+    for (int k = kb; k < kend; ++k) {
+      lu_pivot_kernel<<<1, 256, 0, s>>>(D, n, k, piv, flag);
+      lu_swap_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(D, n, k, piv);
+      const int m = (int)(n - k - 1), w = kend - k - 1;
+      if (m > 0) lu_scale_kernel<<<(m + 255) / 256, 256, 0, s>>>(D, n, k);
+      if (m > 0 && w > 0) lu_update_kernel<<<dim3((w + 15) / 16, (m + 15) / 16), 256, 0, s>>>(D, n, k, kend);
+    }
+    const int64_t m2 = n - kend;
+    if (m2 > 0) {
+      lu_trsm_kernel<<<(int)((m2 + 255) / 256), 256, 0, s>>>(D, D + (int64_t)kb * n + kb, n, kb, nb);
+      const int g = (int)((m2 + 63) / 64);
+      lu_gemm_kernel<<<dim3(g, g), 256, 0, s>>>(D, n, kb, nb);
+    }
+  }
+  lu_perm_kernel<<<1, 1, 0, s>>>(piv, (int)n, piv + n + 1);
+  int h = 0;
+  PYN_HIP(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipStreamSynchronize(s));
+  PYN_HIP(hipGetLastError());
+  PYN_CHECK(h == 0, "direct solve: zero pivot in column %d of %lld (the matrix is singular)", h - 1, (long long)n);
+  return PYN_OK;
+}
+
+// x = U^-1 L^-1 P b with the factors of pyn_dense_lu_factor; z: n doubles of scratch (b is not modified)
+int pyn_dense_lu_solve(pyn_ctx* c, const double* D, const int* piv, int64_t n, const double* b, double* x, double* z) {
+  hipStream_t s = c->stream;
+  lu_gather_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(b, piv + n + 1, n, x);     // x = P b
+  for (int64_t kb = 0; kb < n; kb += 64) {       // forward: blocks of x solved into z, the rows below updated in x
+    const int64_t rows = std::max<int64_t>(n - kb - 64, 0);
+    lu_block_step_kernel<true><<<(int)std::max<int64_t>(1, std::min<int64_t>((rows + 15) / 16, 1024)), 256, 0, s>>>(D, n, kb, x, z);
+  }
+  for (int64_t kb = ((n - 1) / 64) * 64; kb >= 0; kb -= 64)   // backward: blocks of z solved into x, the rows above updated in z
+    lu_block_step_kernel<false><<<(int)std::max<int64_t>(1, std::min<int64_t>((kb + 15) / 16, 1024)), 256, 0, s>>>(D, n, kb, z, x);
+  PYN_HIP(hipGetLastError());
+  return PYN_OK;
+}
+
 // factors of A, cached in the matrix until its values change
 static int direct_factor(pyn_ctx* c, DMat& A) {
   const int64_t n = c->n_owned * A.br;
@@ -268,31 +313,8 @@ static int direct_factor(pyn_ctx* c, DMat& A) {
   A.lu_n = n;
   hipStream_t s = c->stream;
   PYN_HIP(hipMemsetAsync(A.lu, 0, (size_t)n * n * sizeof(double), s));
-  int* flag = A.lu_piv + n;
-  PYN_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
   dense_from_bcsr_kernel<<<(int)std::min<int64_t>(c->n_owned, 4096), 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, c->n_owned, A.br, A.lu, n);
-  for (int kb = 0; kb < (int)n; kb += LU_NB) {
-    const int nb = (int)std::min<int64_t>(LU_NB, n - kb), kend = kb + nb;
-    for (int k = kb; k < kend; ++k) {
-      lu_pivot_kernel<<<1, 256, 0, s>>>(A.lu, n, k, A.lu_piv, flag);
-      lu_swap_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(A.lu, n, k, A.lu_piv);
-      const int m = (int)(n - k - 1), w = kend - k - 1;
-      if (m > 0) lu_scale_kernel<<<(m + 255) / 256, 256, 0, s>>>(A.lu, n, k);
-      if (m > 0 && w > 0) lu_update_kernel<<<dim3((w + 15) / 16, (m + 15) / 16), 256, 0, s>>>(A.lu, n, k, kend);
-    }
-    const int64_t m2 = n - kend;
-    if (m2 > 0) {
-      lu_trsm_kernel<<<(int)((m2 + 255) / 256), 256, 0, s>>>(A.lu, A.lu + (int64_t)kb * n + kb, n, kb, nb);
-      const int g = (int)((m2 + 63) / 64);
-      lu_gemm_kernel<<<dim3(g, g), 256, 0, s>>>(A.lu, n, kb, nb);
-    }
-  }
-  lu_perm_kernel<<<1, 1, 0, s>>>(A.lu_piv, (int)n, A.lu_piv + n + 1);
-  int h = 0;
-  PYN_HIP(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s));
-  PYN_HIP(hipStreamSynchronize(s));
-  PYN_HIP(hipGetLastError());
-  PYN_CHECK(h == 0, "direct solve: zero pivot in column %d of %lld (the matrix is singular)", h - 1, (long long)n);
+  PYN_TRY(pyn_dense_lu_factor(c, A.lu, A.lu_piv, n));
   A.lu_valid = true;
   return PYN_OK;
 }
@@ -320,15 +342,8 @@ extern "C" int pyn_solve_direct(pyn_ctx* c, int mat_id, int bv, int xv, pyn_solv
   PYN_TRY(pyn_ensure_work(c, (size_t)2 * n * sizeof(double)));
   double* b = c->vecs[bv].d;
   double* x = c->vecs[xv].d;
-  hipStream_t s = c->stream;
   double* z = c->d_work;
-  lu_gather_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(b, A.lu_piv + n + 1, n, x);     // x = P b
-  for (int64_t kb = 0; kb < n; kb += 64) {       // forward: blocks of x solved into z, the rows below updated in x
-    const int64_t rows = std::max<int64_t>(n - kb - 64, 0);
-    lu_block_step_kernel<true><<<(int)std::max<int64_t>(1, std::min<int64_t>((rows + 15) / 16, 1024)), 256, 0, s>>>(A.lu, n, kb, x, z);
-  }
-  for (int64_t kb = ((n - 1) / 64) * 64; kb >= 0; kb -= 64)   // backward: blocks of z solved into x, the rows above updated in z
-    lu_block_step_kernel<false><<<(int)std::max<int64_t>(1, std::min<int64_t>((kb + 15) / 16, 1024)), 256, 0, s>>>(A.lu, n, kb, z, x);
+  PYN_TRY(pyn_dense_lu_solve(c, A.lu, A.lu_piv, n, b, x, z));
   PYN_HIP(hipEventRecord(c->ev1, c->stream));
   // true residual through the sparse matrix
   double* w = c->d_work + n;

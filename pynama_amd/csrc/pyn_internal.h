@@ -95,6 +95,8 @@ struct DMat {
   int* band_perm = nullptr;    // per panel of 64 columns: the window's row interchanges as a gather [64 + kl], + [1] singular-column flag
   int64_t band_n = 0, band_kl = 0, band_ku = 0;   // shape the two buffers were sized for
   bool band_valid = false;
+  struct MgHier* mg = nullptr; // geometric multigrid hierarchy (pyn_mg.hip): coarse stencils, diagonals, eigenvalue estimates, coarsest LU
+  bool mg_valid = false;
   // "imposed-column" matrices (Krhs / Arhs of an assembly) are zero except in rows next to imposed nodes.  rhs_clean records for
   // which Dirichlet set (pyn_ctx::bc_stamp) the stored values are known to be exactly that matrix -- or all zero (PYN_RHS_ANY: a fresh
   // or zeroed matrix fits every set); the lattice kernels then leave the zero blocks of tiles without imposed nodes unwritten.
@@ -110,7 +112,7 @@ struct DMat {
   int32_t* c_cptr = nullptr;   // [c_nr + 1] first block of every stored row
   bool live = false;
   void touch() {               // the values are about to change
-    sell_valid = prod_ready = dinv_valid = lu_valid = band_valid = false;
+    sell_valid = prod_ready = dinv_valid = lu_valid = band_valid = mg_valid = false;
     rhs_clean = -2;
   }
   void release_lu() {
@@ -130,6 +132,7 @@ struct DMat {
     band_n = band_kl = band_ku = 0;
     band_valid = false;
   }
+  void release_mg();           // pyn_mg.hip
 };
 
 struct PatchPlan {
@@ -367,4 +370,11 @@ inline bool pyn_ho3_matfree_mesh(const pyn_ctx* c) { return c->ho3.valid && c->h
 int pyn_ho3_matfree_set(pyn_ctx* c, int op);   // checks the mesh and tables, fills c->mf_ho3
 int pyn_ho3_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);
 int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
+// dense LU shared by the direct solve and the coarsest multigrid level (pyn_direct.hip): piv holds 2 n + 1 ints
+int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n);
+int pyn_dense_lu_solve(pyn_ctx* c, const double* D, const int* piv, int64_t n, const double* b, double* x, double* z);
+// geometric multigrid (pyn_mg.hip): the hierarchy for the current values (built with the last options, or the defaults), and one
+// V-cycle z = M^-1 r whose level-0 products are prod0 (the assembled product or the matrix-free shell)
+int pyn_mg_ensure(pyn_ctx* c, DMat& A);
+int pyn_mg_vcycle(pyn_ctx* c, DMat& A, const double* r, double* z, const std::function<int(const double*, double*)>& prod0);
 int pyn_assemble_ho3_operator(pyn_ctx* c, int rule, int br, int bc, int nterms, const int32_t* terms, const double* coef, double* M, bool* handled);

@@ -862,6 +862,123 @@ static int solve_cg(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_s
   return PYN_OK;
 }
 
+// ---- PCG with the geometric multigrid preconditioner (pyn_mg.hip): unfused, z = Vcycle(r) between the update and the dots --------
+// x = 0, r = b
+__global__ void mg_cg_init_kernel(const double* __restrict__ b, double* __restrict__ x, double* __restrict__ r, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    x[i] = 0.0;
+    r[i] = b[i];
+  }
+}
+
+// partials: [0] r.z  [1] norm^2 (by type); p = z when p is given (first iteration)
+__global__ void __launch_bounds__(256) mg_cg_dots_kernel(const double* __restrict__ r, const double* __restrict__ z, double* __restrict__ p,
+                                                         int64_t n, int norm_type, double* __restrict__ part) {
+  double rz = 0.0, nn = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const double ri = r[i], zi = z[i];
+    if (p) p[i] = zi;
+    rz += ri * zi;
+    nn += norm_type == PYN_NORM_PRECONDITIONED ? zi * zi : ri * ri;
+  }
+  block_partial(rz, part);
+  __syncthreads();
+  block_partial(nn, part + PYN_MAX_PARTIALS);
+}
+
+// x += alpha p ; r -= alpha Ap
+__global__ void __launch_bounds__(256) mg_cg_update_kernel(const double* __restrict__ scal, const int* __restrict__ flag,
+                                                           const double* __restrict__ p, const double* __restrict__ Ap, double* __restrict__ x,
+                                                           double* __restrict__ r, int64_t n) {
+  if (flag[F_DONE]) return;
+  const double alpha = scal[S_ALPHA];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    x[i] += alpha * p[i];
+    r[i] -= alpha * Ap[i];
+  }
+}
+
+// p = z + beta p
+__global__ void __launch_bounds__(256) mg_cg_p_kernel(const double* __restrict__ scal, const int* __restrict__ flag, const double* __restrict__ z,
+                                                      double* __restrict__ p, int64_t n) {
+  if (flag[F_DONE]) return;
+  const double beta = scal[S_BETA];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = z[i] + beta * p[i];
+}
+
+static int solve_cg_mg(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_solve_opts& o, pyn_solve_info* info) {
+  const bool mf = o.matfree != PYN_MATFREE_OFF;
+  const bool sell = !mf && pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL");
+  PYN_TRY(pyn_mg_ensure(c, A));
+  PYN_TRY(pyn_dinv_ensure(c, A));
+  if (sell) PYN_TRY(pyn_sell_ensure(c, A));
+  const int64_t n = c->n_owned * A.br;
+  // work: r[n] p[n] Ap[n] z[n]
+  PYN_TRY(pyn_ensure_work(c, (size_t)4 * n * sizeof(double)));
+  double* r = c->d_work;
+  double* p = r + n;
+  double* Ap = p + n;
+  double* z = Ap + n;
+  const int g = vgrid(n);
+  const int gs = (int)std::max<int64_t>(1, std::min<int64_t>((n * 32 + 255) / 256, PYN_MAX_PARTIALS));
+  hipStream_t s = c->stream;
+  const int maxit = o.fixed_iters > 0 ? o.fixed_iters : o.maxit;
+  const int check = o.fixed_iters > 0 ? 0 : 1;
+  // level-0 product of the V-cycle: the one the iteration uses
+  auto prod0 = [&](const double* in, double* out) -> int {
+    if (mf) return matfree_product(c, o.matfree, in, out, false, nullptr);
+    if (sell) return pyn_sell_spmv(c, A, in, out, false, nullptr);
+    return pyn_spmv_raw(c, A, in, out);
+  };
+
+  PYN_HIP(hipEventRecord(c->ev0, s));
+  mg_cg_init_kernel<<<g, 256, 0, s>>>(b, x, r, n);
+  PYN_TRY(pyn_mg_vcycle(c, A, r, z, prod0));
+  mg_cg_dots_kernel<<<g, 256, 0, s>>>(r, z, p, n, o.norm_type, c->d_part);
+  sum_partials_kernel<<<1, 256, 0, s>>>(c->d_part, 2, g, c->d_scal + S_TMP0, nullptr);
+  cg_scalar_init_kernel<<<1, 1, 0, s>>>(c->d_scal, c->d_flag, check ? o.rtol : 0.0, check ? o.atol : 0.0, o.dtol, o.norm_type, nullptr);
+  PYN_HIP(hipMemcpyAsync(c->h_flag, c->d_flag, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipStreamSynchronize(s));
+  int done = check ? c->h_flag[F_DONE] : 0;
+  if (!check) PYN_HIP(hipMemsetAsync(c->d_flag, 0, sizeof(int), s));   // fixed-iteration mode ignores "already converged"
+  int issued = 0;
+  while (!done && issued < maxit) {
+    int gsp = gs;
+    if (mf)
+      PYN_TRY(matfree_product(c, o.matfree, p, Ap, true, &gsp));
+    else if (sell)
+      PYN_TRY(pyn_sell_spmv(c, A, p, Ap, true, &gsp));
+    else
+      spmv_kernel<32, true><<<gs, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, p, Ap, n, A.br, A.bc, c->d_flag, c->d_part);
+    sum_partials_kernel<<<1, 256, 0, s>>>(c->d_part, 1, gsp, c->d_scal + S_TMP0, c->d_flag);
+    cg_scalar_alpha_kernel<<<1, 1, 0, s>>>(c->d_scal, c->d_flag);
+    mg_cg_update_kernel<<<g, 256, 0, s>>>(c->d_scal, c->d_flag, p, Ap, x, r, n);
+    PYN_TRY(pyn_mg_vcycle(c, A, r, z, prod0));
+    mg_cg_dots_kernel<<<g, 256, 0, s>>>(r, z, nullptr, n, o.norm_type, c->d_part);
+    sum_partials_kernel<<<1, 256, 0, s>>>(c->d_part, 2, g, c->d_scal + S_TMP0, c->d_flag);
+    cg_scalar_beta_kernel<<<1, 1, 0, s>>>(c->d_scal, c->d_flag, o.norm_type, maxit, check, nullptr, 0);
+    mg_cg_p_kernel<<<g, 256, 0, s>>>(c->d_scal, c->d_flag, z, p, n);
+    ++issued;
+    // a V-cycle is hundreds of launches: the flag is read after every iteration, no cycle runs past convergence
+    PYN_HIP(hipMemcpyAsync(c->h_flag, c->d_flag, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+    PYN_HIP(hipStreamSynchronize(s));
+    done = c->h_flag[F_DONE];
+  }
+  PYN_HIP(hipEventRecord(c->ev1, s));
+  PYN_HIP(hipMemcpyAsync(c->h_flag, c->d_flag, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipMemcpyAsync(c->h_scal, c->d_scal, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipStreamSynchronize(s));
+  PYN_HIP(hipGetLastError());
+  float ms = 0;
+  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  info->solve_ms = ms;
+  info->iters = c->h_flag[F_ITERS];
+  info->reason = c->h_flag[F_REASON] ? c->h_flag[F_REASON] : PYN_DIVERGED_ITS;
+  info->rnorm = c->h_scal[S_RNORM];
+  info->rnorm0 = c->h_scal[S_RNORM0];
+  return PYN_OK;
+}
+
 static int solve_cg_sr(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_solve_opts& o, pyn_solve_info* info) {
   const bool mf = o.matfree != PYN_MATFREE_OFF;
   const bool sell = !mf && pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL");
@@ -1370,7 +1487,8 @@ extern "C" int pyn_solve(pyn_ctx* c, int mat_id, int bv, int xv, const pyn_solve
   PYN_CHECK(!A.rhs_compact, "a compact imposed-column matrix (pyn_mat_create_rhs) is a right-hand-side operator, not a system matrix");
   PYN_CHECK(c->vecs[bv].bs == A.br && c->vecs[xv].bs == A.br, "vector block size mismatch");
   PYN_CHECK(opts->method == PYN_KSP_CG || opts->method == PYN_KSP_GMRES, "unknown method %d", opts->method);
-  PYN_CHECK(opts->pc == PYN_PC_NONE || opts->pc == PYN_PC_JACOBI, "unknown preconditioner %d", opts->pc);
+  PYN_CHECK(opts->pc == PYN_PC_NONE || opts->pc == PYN_PC_JACOBI || opts->pc == PYN_PC_MG, "unknown preconditioner %d", opts->pc);
+  PYN_CHECK(opts->pc != PYN_PC_MG || opts->method == PYN_KSP_CG, "the multigrid preconditioner (PYN_PC_MG) runs with CG only, not GMRES");
   PYN_CHECK(opts->maxit > 0 || opts->fixed_iters > 0, "maxit must be positive");
   PYN_CHECK(!(c->nranks > 1 && c->detached), "detached communicator: the Krylov solve needs collectives");
   PYN_CHECK(opts->matfree >= PYN_MATFREE_OFF && opts->matfree <= PYN_MATFREE_KLE, "unknown matrix-free operator %d", opts->matfree);
@@ -1395,7 +1513,9 @@ extern "C" int pyn_solve(pyn_ctx* c, int mat_id, int bv, int xv, const pyn_solve
     PYN_CHECK(dd <= 1e-20 * aa, "matrix-free operator differs from the assembled matrix (relative %.3e): was the matrix "
                                 "assembled as this operator with the current Dirichlet mask?", sqrt(dd / (aa > 0 ? aa : 1.0)));
   }
-  if (opts->method == PYN_KSP_CG) {
+  if (opts->method == PYN_KSP_CG && opts->pc == PYN_PC_MG) {
+    PYN_TRY(solve_cg_mg(c, A, b, x, *opts, info));
+  } else if (opts->method == PYN_KSP_CG) {
     // cg_variant: 0 auto (standard on one GPU, single-reduction across ranks), 1 standard, 2 single-reduction
     const int v = opts->cg_variant ? opts->cg_variant : (pyn_has_comm(c) ? 2 : 1);
     PYN_CHECK(v == 1 || v == 2, "cg_variant must be 0, 1 or 2");

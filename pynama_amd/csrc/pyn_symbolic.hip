@@ -40,6 +40,7 @@ static int pyn_symbolic_reset_dependents(pyn_ctx* c) {
     (void)hipFree(m.sell_val);
     (void)hipFree(m.dinv);
     m.release_lu();
+    m.release_mg();
     pyn_rhs_release(m);
   }
   c->mats.clear();

@@ -37,6 +37,13 @@ matrix version) -- a real direct solve for structured meshes, whose band grows w
 it: the factors replace the shell) and while the factors fit ``-pynama_direct_band_max_gb`` (default 16 GB).  When the band does not
 fit (the cap, the free device memory: e.g. imported meshes, whose numbering is not banded) the reason is logged and the Krylov
 substitute above runs; a zero pivot raises.
+
+``-ksp_type cg -pc_type mg`` (PETSc's PCMG): CG preconditioned by one geometric multigrid V-cycle per iteration
+(``pyn_mg_setup`` / ``PYN_PC_MG``: Galerkin coarse operators on the structured lattice, Chebyshev-Jacobi smoothing, dense LU on the
+coarsest level; one rank, lattice meshes).  Options: ``-pc_mg_levels`` (most levels, the matrix included), ``-mg_levels_ksp_max_it``
+(Chebyshev degree, default 2), ``-pynama_mg_coarse_max_rows`` (coarsening stops at this many rows, default 4096).  The hierarchy is
+cached in the matrix until its values change.  ``gmres`` or ``preonly`` with ``mg`` is refused in ``setUp``.  With a matrix-free tag
+CG multiplies with the shell at level 0 as with Jacobi.
 """
 import logging
 
@@ -62,6 +69,9 @@ class KspSolver(object):
         self.direct_max_rows = 8192      # preonly/lu: dense LU up to this many rows (the library's limit), the Krylov substitute above
         self.direct_band = False         # -pynama_direct_band: preonly/lu above that limit as a banded LU (one rank)
         self.direct_band_max_gb = 16.0   # -pynama_direct_band_max_gb: cap on the band factors' storage (1e9 bytes)
+        self.mg_levels = 0               # -pc_mg_levels (0: the library's default)
+        self.mg_degree = 0               # -mg_levels_ksp_max_it: Chebyshev degree (0: default 2)
+        self.mg_coarse_max_rows = 0      # -pynama_mg_coarse_max_rows (0: default 4096)
         self.info = None
         self._symmetric = None
 
@@ -98,6 +108,9 @@ class KspSolver(object):
         if o.hasName('pynama_direct_band'):
             self.direct_band = str(o.getString('pynama_direct_band', '1')).lower() not in ('0', 'false', 'no')
         self.direct_band_max_gb = o.getReal('pynama_direct_band_max_gb', self.direct_band_max_gb)
+        self.mg_levels = o.getInt('pc_mg_levels', self.mg_levels)
+        self.mg_degree = o.getInt('mg_levels_ksp_max_it', self.mg_degree)
+        self.mg_coarse_max_rows = o.getInt('pynama_mg_coarse_max_rows', self.mg_coarse_max_rows)
         if o.hasName('ksp_gmres_modifiedgramschmidt'):
             self.gmres_orthog = 2
         else:
@@ -126,12 +139,14 @@ class KspSolver(object):
         return abs(a - b) <= 1e-10 * (abs(a) + abs(b) + 1e-300)
 
     def setUp(self):
+        if self.pc_type == 'mg' and self.ksp_type != 'cg':
+            raise ValueError(f"-pc_type mg runs with -ksp_type cg only, not {self.ksp_type}")
         if self.ksp_type == 'preonly' and self.pc_type not in ('lu', 'cholesky'):
             raise ValueError("-ksp_type preonly needs a direct -pc_type")
         if self.ksp_type not in ('cg', 'gmres', 'preonly'):
             raise ValueError(f"unsupported -ksp_type {self.ksp_type}")
-        if self.ksp_type != 'preonly' and self.pc_type not in ('jacobi', 'none'):
-            raise ValueError(f"unsupported -pc_type {self.pc_type} (jacobi | none)")
+        if self.ksp_type != 'preonly' and self.pc_type not in ('jacobi', 'none', 'mg'):
+            raise ValueError(f"unsupported -pc_type {self.pc_type} (jacobi | none | mg)")
 
     def createSolver(self, mat, comm):
         self.logger = logging.getLogger("KSP Solver")
@@ -191,9 +206,12 @@ class KspSolver(object):
                                    f"{info.true_resid:.3e} after {info.iters} iterations (a direct solver would have solved "
                                    "this system or raised)")
         else:
+            if self.pc_type == 'mg':        # no-op unless the options or the values changed since the last build
+                ctx.mg_setup(A.id, max_levels=self.mg_levels, smooth_degree=self.mg_degree,
+                             coarse_max_rows=self.mg_coarse_max_rows)
             info = ctx.solve(A.id, b.id, x.id,
                              method=_lib.KSP_CG if self.ksp_type == 'cg' else _lib.KSP_GMRES,
-                             pc=_lib.PC_JACOBI if self.pc_type == 'jacobi' else _lib.PC_NONE,
+                             pc={'jacobi': _lib.PC_JACOBI, 'mg': _lib.PC_MG}.get(self.pc_type, _lib.PC_NONE),
                              rtol=self.rtol, atol=self.atol, dtol=self.divtol, maxit=self.max_it,
                              restart=self.restart, norm_type=_NORMS[self.norm_type], gmres_orthog=self.gmres_orthog,
                              matfree=mf)
