@@ -214,6 +214,19 @@ int pyn_vec_vtensv(pyn_ctx* ctx, int v, int out);   /* v (x) v, BaseProblem.comp
 int pyn_vec_dot(pyn_ctx* ctx, int x, int y, double* out);
 int pyn_vec_norm(pyn_ctx* ctx, int x, int type /*1, 2, 3=inf (PETSc NormType)*/, double* out);
 
+/* ---- explicit Runge-Kutta (TsSolver, pynama_amd/solver/ts_solver.py; pyn_ts.hip) ------------
+ * Owned entries only (n_owned*bs; ghosts untouched), on the context stream.  ids[m] are vectors of x's block size,
+ * 0 <= m <= PYN_TS_MAX_STAGES. */
+#define PYN_TS_MAX_STAGES 8
+/* y = x + sum_j w[j] * V[ids[j]], one pass, fixed j order (PETSc VecMAXPY after VecCopy: the stage vector of TSStep_RK, and
+ * the roll-back of a rejected step with w = -h b, TSRollBack_RK).  y may be x. */
+int pyn_vec_maxpy(pyn_ctx* ctx, int y, int x, int m, const int* ids, const double* w);
+/* x += sum_j hb[j] * K[ids[j]] in place (TSEvaluateStep_RK).  wnorm != NULL: also the weighted RMS norm of the embedded error
+ * d = sum_j hd[j] * K[ids[j]], sqrt( sum_i (|d_i| / (atol + rtol max(|x_i|, |x_i + d_i|)))^2 / N ) over the UPDATED x and all
+ * ranks' entries N (TSErrorWeightedNorm2 with scalar tolerances); hd may be NULL when wnorm is.  No id may be x. */
+int pyn_ts_step_finish(pyn_ctx* ctx, int x, int m, const int* ids, const double* hb, const double* hd, double atol, double rtol,
+                       double* wnorm);
+
 /* ---- numeric phase (HOT LOOP 1) -----------------------------------------------------------
  * One device pass over all local elements: quadrature (spectral.py:89-157) + scatter-add with
  * Dirichlet elimination (base_problem.py:499-552) + unit diagonal on imposed DOFs

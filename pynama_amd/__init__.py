@@ -18,7 +18,7 @@ _SUBPACKAGES = {
     "domain": ("dmplex", "gmsh"),
     "viewer": ("xml_generator", "paraviewer", "hdf5_writer"),
     "matrices": ("mat_generator", "mat_ns"),
-    "solver": ("ksp_solver",),
+    "solver": ("ksp_solver", "ts_solver"),
     "common": ("timer", "nswalls", "options", "comm"),
     "cases": ("base_problem", "uniform", "custom_func", "cavity"),
 }

@@ -23,6 +23,7 @@ KSP_CG, KSP_GMRES = 0, 1
 MATFREE_OFF, MATFREE_LAPLACE, MATFREE_KLE = 0, 1, 2
 PC_NONE, PC_JACOBI, PC_MG = 0, 1, 2
 MG_MAX_LEVELS = 16
+TS_MAX_STAGES = 8
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
 T_SYMBOLIC, T_ASSEMBLE, T_SPMV, T_SOLVE = 0, 1, 2, 3
 
@@ -105,6 +106,8 @@ SIGNATURES = {
     "pyn_vec_vtensv": [_P, _I, _I],
     "pyn_vec_dot": [_P, _I, _I, C.POINTER(_D)],
     "pyn_vec_norm": [_P, _I, _I, C.POINTER(_D)],
+    "pyn_vec_maxpy": [_P, _I, _I, _I, _pi32, _pf64],
+    "pyn_ts_step_finish": [_P, _I, _I, _pi32, _pf64, _P, _D, _D, C.POINTER(_D)],
     "pyn_assemble_kle": [_P, _D, _D, _I, _I, _I, _I, _I],
     "pyn_assemble_kle_noslip": [_P, _D, _D, C.POINTER(_I)],
     "pyn_assemble_scalar": [_P, _I, _I, _I, _I],
@@ -478,6 +481,24 @@ class Context:
         d = _D(0)
         _check(self.lib.pyn_vec_dot(self.h, x, y, C.byref(d)))
         return d.value
+
+    def vec_maxpy(self, y, x, ids, w):
+        """y = x + sum_j w[j] * vec ids[j] (at most TS_MAX_STAGES terms; y may be x)"""
+        ids, w = _i32(ids), _f64(w)
+        assert ids.size == w.size
+        _check(self.lib.pyn_vec_maxpy(self.h, y, x, ids.size, ids, w))
+
+    def ts_step_finish(self, x, ids, hb, hd=None, atol=0.0, rtol=0.0):
+        """x += sum_j hb[j] * vec ids[j]; with hd, the weighted RMS norm of sum_j hd[j] * vec ids[j] (else None)"""
+        ids, hb = _i32(ids), _f64(hb)
+        assert ids.size == hb.size
+        if hd is None:
+            _check(self.lib.pyn_ts_step_finish(self.h, x, ids.size, ids, hb, None, float(atol), float(rtol), None))
+            return None
+        hd, out = _f64(hd), _D(0.0)
+        assert hd.size == ids.size
+        _check(self.lib.pyn_ts_step_finish(self.h, x, ids.size, ids, hb, hd.ctypes.data, float(atol), float(rtol), C.byref(out)))
+        return out.value
 
     def vec_norm(self, x, norm_type=2) -> float:
         d = _D(0)

@@ -7,7 +7,8 @@ Mirrors ``src/cases/base_problem.py``: ``BaseProblem`` (config parsing :18-44,97
 
 Also here, from SURVEY.md section 8(f): the operator chain of ``evalRHS`` (f1: ``buildOperators`` / ``computeVtensV``,
 :132-140, 212-252) and ``NoSlipFreeSlip`` (f2, :315-454); ``saveStep`` writes the HDF5 / XDMF pair of f4.
-Not built (out of scope): the PETSc TS time integrator that would call ``evalRHS``.
+Time integration: ``setUpTimeSolver`` / ``startSolver`` / ``convergedStepFunction`` drive
+``solver.ts_solver.TsSolver`` -- explicit RK (``5bs`` adaptive, ``MATCHSTEP``), one ``evalRHS`` per stage, on device vectors.
 """
 import logging
 
@@ -169,6 +170,39 @@ class BaseProblem(object):
         self.operator.DivSrT.mult(stress, self._divStress)
         self._divStress.scale(1.0 / self.rho)
         self.operator.Curl.mult(self._divStress, f)
+
+    def setUpTimeSolver(self):
+        """TsSolver with evalRHS and convergedStepFunction.  start-time / end-time / max-steps come from the optional
+        `time-solver` block of the yaml, then from the constructor kwargs startTime / endTime / maxSteps; options given on
+        the command line (-ts_max_time, -ts_max_steps, ...) override both."""
+        from pynama_amd.solver.ts_solver import TsSolver
+        self.ts = TsSolver(self.comm)
+        block = self.config.get("time-solver") or {}
+        for key, kw, setter in (("start-time", "startTime", self.ts.setTime), ("end-time", "endTime", self.ts.setMaxTime),
+                                ("max-steps", "maxSteps", self.ts.setMaxSteps)):
+            value = self.opts.get(kw, block.get(key))
+            if value is not None:
+                setter(value)
+        self.ts.setFromOptions()
+        self.ts.setRHSFunction(self.evalRHS)
+        self.ts.setPostStep(self.convergedStepFunction)
+        self._saveEvery = int(self.config.get("save-n-steps", block.get("save-n-steps", 1)))
+
+    def startSolver(self):
+        """initial condition at the start time, then the time integration of self.vort in place"""
+        if getattr(self, "ts", None) is None:
+            self.setUpTimeSolver()
+        self.computeInitialCondition(startTime=self.ts.getTime())
+        self.ts.solve(self.vort)
+
+    def convergedStepFunction(self, ts):
+        """post-step callback: logs step, time and the next increment; saves the fields every `save-n-steps` steps when output
+        is enabled (`save-output: true` in the yaml); writes nothing otherwise"""
+        step, time = ts.getStepNumber(), ts.getTime()
+        if not self.comm.rank:
+            self.logger.info(f"Converged: Step {step:4} | Time {time:.4e} | Increment Time: {ts.getTimeStep():.2e}")
+        if self.config.get("save-output", False) and step % max(1, getattr(self, "_saveEvery", 1)) == 0:
+            self.saveStep(step, time)
 
     def solveKLE(self, time, vort):
         pass

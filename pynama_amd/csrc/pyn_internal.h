@@ -207,6 +207,21 @@ struct DVec {
 constexpr int64_t PYN_RHS_UNKNOWN = -2, PYN_RHS_ANY = -1;   // DMat::rhs_clean
 constexpr int PYN_MAX_PARTIALS = 2048;  // grid cap of every reducing kernel
 
+// deterministic two-stage sums (pyn_krylov.hip, pyn_ts.hip): 64-lane wave sum, then block-level sum of `acc` -> part[blockIdx.x]
+// (blocks of 256 threads; a second call in the same kernel needs a __syncthreads() before it)
+__device__ inline double wsum(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ inline void block_partial(double acc, double* __restrict__ part) {
+  __shared__ double sm_[4];
+  acc = wsum(acc);
+  if ((threadIdx.x & 63) == 0) sm_[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = sm_[0] + sm_[1] + sm_[2] + sm_[3];
+}
+
 struct pyn_ctx {
   int device = 0;
   hipStream_t stream = nullptr;

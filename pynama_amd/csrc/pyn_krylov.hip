@@ -20,20 +20,6 @@ enum { S_RZ = 0, S_PAP = 1, S_RZNEW = 2, S_ALPHA = 3, S_BETA = 4, S_RNORM = 5, S
        S_TMP0 = 16, S_TMP1 = 17 };
 enum { F_DONE = 0, F_ITERS = 1, F_REASON = 2 };
 
-__device__ inline double wsum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// block-level sum of `acc` -> part[blockIdx.x]
-__device__ inline void block_partial(double acc, double* __restrict__ part) {
-  __shared__ double sm_[4];
-  acc = wsum(acc);
-  if ((threadIdx.x & 63) == 0) sm_[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = sm_[0] + sm_[1] + sm_[2] + sm_[3];
-}
-
 // ---- SpMV: LPR lanes per scalar row, rows of one node are contiguous in `val` -----------------
 // y[(i,p)] = sum_k sum_q val[(rowptr[i]*br + p*len + k)*bc + q] * x[colidx[rowptr[i]+k]*bc + q]
 template <int LPR, bool DOT>
