@@ -137,6 +137,19 @@ int pyn_mesh_get(pyn_ctx* ctx, int32_t* conn, double* xyz);
  * kind 3 = structured mesh of Q1 quadrilaterals; for both nx, ny, nz count the NODES per x-line, x-lines per
  * plane and planes (2-D: nz = 1) and the atomics-free row-run kernels assemble them (pyn_assemble_ho3.hip). */
 int pyn_mesh_topology(pyn_ctx* ctx, int* kind, int* nx, int* ny, int* nz);
+/* Box meshes of order ngl >= 4 (the reference's box mesh, (ngl-1) nelem + 1 nodes per axis numbered lexicographically, or a rank's
+ * slab of one) stay kind 0 above: the assemblies, the direct solves and multigrid treat them as general meshes.  They are recognised
+ * all the same (every entry of the connectivity is checked) for the matrix-free KLE operator; this query reports it: *ngl = the order
+ * (0: not such a lattice, or an order above pyn_ho_matfree_max_ngl(dim)), nx, ny, nz as for kind 2. */
+int pyn_mesh_ho_lattice(pyn_ctx* ctx, int* ngl, int* nx, int* ny, int* nz);
+/* Host-side pieces of that operator (no device needed).  pyn_ho_matfree_max_ngl: the largest order with a kernel (2-D: 12, 3-D: 8).
+ * pyn_ho_tables_1d: the 1-D tables of order ngl, recomputed by the library (any pointer may be NULL): xl, wl [ngl] Lobatto nodes and
+ * weights; Dl [ngl][ngl], Dl[i][a] = h_a'(xl_i); xr, wr [ngl-1] Gauss points and weights; Br, Gr [ngl-1][ngl] values and derivatives
+ * of the ngl Lagrange functions at the Gauss points.  pyn_ho_local_lattice: loc [ngl^dim][dim], the lattice offset of every local
+ * node of a box-mesh cell in the reference's vertex / edge / face / interior order (2-D: with the x ~ -r, y ~ -s flip). */
+int pyn_ho_matfree_max_ngl(int dim);
+int pyn_ho_tables_1d(int ngl, double* xl, double* wl, double* Dl, double* xr, double* wr, double* Br, double* Gr);
+int pyn_ho_local_lattice(int ngl, int dim, int32_t* loc);
 /* One quadrature's tables -- Spectral.computeMats2D/3D output (spectral.py:220-344):
  * w[ngp], H[ngp*nn], Hrs[ngp*dim*nn], HrsCoo[ngp*dim*2^dim] (geometry basis, spectral.py:54-61). */
 int pyn_elem_tables_set(pyn_ctx* ctx, int which, int ngp, const double* w, const double* H,
@@ -275,8 +288,13 @@ int pyn_spmv(pyn_ctx* ctx, int mat_id, int x_vec, int y_vec);
  *   Q1 hexahedra (pyn_mesh_topology == lattice)            both operators
  *   second-order lattices (lattice-ngl3), 2-D and 3-D      PYN_MATFREE_KLE only, and only when every cell is affine
  *                                                          (parallelograms / parallelepipeds; sum-factorised, pyn_matfree_ho3.hip)
+ *   box lattices of order ngl >= 4 (pyn_mesh_ho_lattice)   PYN_MATFREE_KLE only, affine cells only, ngl <= 12 in 2-D and <= 8 in 3-D
+ *                                                          (lane per node, two passes, pyn_matfree_ho.hip).  Refused with a message:
+ *                                                          a cell that is not affine, PYN_MATFREE_LAPLACE, an order above the limit,
+ *                                                          a connectivity that is not the lexicographic box lattice (imported /
+ *                                                          renumbered meshes), tables that are not the Lobatto(ngl) / Gauss(ngl-1) rules
  *   PYN_MATFREE_LAPLACE  the scalar Laplacian pyn_assemble_scalar(PYN_FORM_LAPLACE) builds (1 DOF per node)
- *   PYN_MATFREE_KLE      the K of pyn_assemble_kle (dim DOFs per node: 3 on Q1 hexahedra, 2 / 3 on second-order meshes);
+ *   PYN_MATFREE_KLE      the K of pyn_assemble_kle (dim DOFs per node: 3 on Q1 hexahedra, 2 / 3 on second- and higher-order meshes);
  *                        alpha_d / alpha_w are that call's penalty weights (1e3 / 1e2 in the reference, spectral.py:152-153)
  * pyn_matfree_set defines the operator from the mesh, the element tables and a SNAPSHOT of the current Dirichlet mask
  * (imposed rows identity, imposed columns eliminated, base_problem.py:531-549): call it next to the assembly it mirrors;

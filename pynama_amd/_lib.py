@@ -73,6 +73,10 @@ SIGNATURES = {
     "pyn_halo_set": [_P, _L, _L, _I, _pi32, _pi64, _pi32, _pi64],
     "pyn_mesh_set": [_P, _I, _I, _L, _L, _pi32, _pf64],
     "pyn_mesh_topology": [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)],
+    "pyn_mesh_ho_lattice": [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)],
+    "pyn_ho_matfree_max_ngl": [_I],
+    "pyn_ho_tables_1d": [_I, _pf64, _pf64, _pf64, _pf64, _pf64, _pf64, _pf64],
+    "pyn_ho_local_lattice": [_I, _I, _pi32],
     "pyn_elem_tables_set": [_P, _I, _I, _pf64, _pf64, _pf64, _pf64],
     "pyn_bc_set": [_P, _I, _P],
     "pyn_csr_symbolic": [_P],
@@ -176,6 +180,31 @@ def device_count() -> int:
     n = _I(0)
     _check(lib.pyn_device_count(C.byref(n)))
     return n.value
+
+
+def ho_matfree_max_ngl(dim) -> int:
+    """largest order (ngl) the matrix-free KLE operator of high-order box lattices has a kernel for"""
+    return load_library().pyn_ho_matfree_max_ngl(int(dim))
+
+
+def ho_tables_1d(ngl):
+    """The 1-D tables the matrix-free KLE operator of order ngl >= 4 recomputes on the host (no device needed): dict with xl, wl
+    (Lobatto nodes / weights), Dl [ngl, ngl] (Dl[i, a] = h_a'(xl_i)), xr, wr (Gauss(ngl-1)), Br, Gr [ngl-1, ngl] (values and
+    derivatives of the Lagrange functions at the Gauss points)."""
+    n = int(ngl)
+    if n < 2:
+        raise PynamaHipError(f"ho_tables_1d: ngl {n} out of range")
+    t = dict(xl=np.zeros(n), wl=np.zeros(n), Dl=np.zeros((n, n)), xr=np.zeros(n - 1), wr=np.zeros(n - 1),
+             Br=np.zeros((n - 1, n)), Gr=np.zeros((n - 1, n)))
+    _check(load_library().pyn_ho_tables_1d(n, *(t[k] for k in ("xl", "wl", "Dl", "xr", "wr", "Br", "Gr"))))
+    return t
+
+
+def ho_local_lattice(ngl, dim):
+    """[ngl^dim, dim] lattice offset of every local node of a box-mesh cell as the library's lattice check assumes it"""
+    loc = np.zeros((int(ngl) ** int(dim), int(dim)), np.int32)
+    _check(load_library().pyn_ho_local_lattice(int(ngl), int(dim), loc))
+    return loc
 
 
 class _stdout_to_stderr:
@@ -545,9 +574,17 @@ class Context:
     def spmv(self, mid, x, y):
         _check(self.lib.pyn_spmv(self.h, mid, x, y))
 
+    def mesh_ho_lattice(self):
+        """(ngl, nx, ny, nz) when the mesh is a box lattice of order ngl >= 4 that the matrix-free KLE operator accepts
+        (mesh_topology() says 'general' for these), (0, 0, 0, 0) otherwise"""
+        g, a, b, c = _I(0), _I(0), _I(0), _I(0)
+        _check(self.lib.pyn_mesh_ho_lattice(self.h, C.byref(g), C.byref(a), C.byref(b), C.byref(c)))
+        return g.value, a.value, b.value, c.value
+
     def matfree_apply(self, x, y, op=1):
-        """y = A x without an assembled matrix (op: MATFREE_LAPLACE scalar / MATFREE_KLE 3 DOFs per node; structured Q1
-        hex meshes)"""
+        """y = A x without an assembled matrix (op: MATFREE_LAPLACE scalar, structured Q1 hex meshes; MATFREE_KLE dim DOFs per
+        node: structured Q1 hex meshes, second-order lattices of affine cells, box lattices of affine cells of order ngl 4..12
+        in 2-D / 4..8 in 3-D)"""
         _check(self.lib.pyn_matfree_apply(self.h, op, x, y))
 
     def matfree_set(self, op=1, alpha_d=0.0, alpha_w=0.0):

@@ -159,6 +159,7 @@ extern "C" int pyn_ctx_destroy(pyn_ctx* c) {
   (void)hipFree(c->lat.d_P);
   (void)hipFree(c->lat.d_zord);
   pyn_ho3_release(c);
+  pyn_ho_release(c);
   (void)hipFree(c->d_ho3_tabs);
   (void)hipFree(c->d_ho3_t1d);
   (void)hipFree(c->d_bcmask);
@@ -610,6 +611,7 @@ static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
   }
   PYN_TRY(pyn_lattice_detect(c, at));
   PYN_TRY(pyn_ho3_detect(c, at));
+  PYN_TRY(pyn_ho_detect(c, at));
   // graph + matrices depend on the mesh
   (void)hipFree(c->d_rowptr);
   (void)hipFree(c->d_colidx);

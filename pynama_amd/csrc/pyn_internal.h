@@ -189,6 +189,19 @@ struct Ho3MfBasis {
   int diag = 0;                // every cell's J^-1 is diagonal (axis-aligned boxes)
 };
 
+// Structured box lattice of order ngl >= 4 (pyn_matfree_ho.hip): (ngl - 1) E + 1 nodes per axis numbered lexicographically, the slowest
+// axis cut into planes (x-lines in 2-D) as in Ho3Lattice: id = P[c_slow] + c_y NX + c_x.  Only the matrix-free KLE operator uses it;
+// pyn_mesh_topology reports kind 0 for these meshes.
+struct HoLattice {
+  bool valid = false;
+  int dim = 0, ngl = 0;
+  int EX = 0, EY = 0, EL = 0;   // local cells along x, y (3-D), the slow axis
+  int NX = 0, NY = 0;           // nodes per x-line; x-lines per plane (3-D)
+  int npl = 0, p_own0 = 0, n_own = 0;
+  int32_t* d_P = nullptr;       // [npl]
+};
+constexpr int PYN_HO_MAX_NGL_2D = 12, PYN_HO_MAX_NGL_3D = 8;   // orders the matrix-free kernels are instantiated for
+
 struct SellShape {
   int br = 0, bc = 0, maxw = 0;
   int64_t ns = 0, total = 0;
@@ -280,6 +293,9 @@ struct pyn_ctx {
   bool plan_unfit[2] = {false, false};  // the automatic plan did not fit this graph (reset by pyn_csr_symbolic)
   Lattice lat;  // structured topology, if the mesh has one (plan-free assembly kernel)
   Ho3Lattice ho3;   // ... of a second-order (ngl = 3) mesh (pyn_assemble_ho3.hip)
+  HoLattice ho;     // ... of a box mesh of order ngl >= 4 (pyn_matfree_ho.hip)
+  double* d_ho_tab = nullptr;   // its matrix-free KLE operator: the 1-D tables of the order (set by pyn_matfree_set) ...
+  double* d_ho_ye = nullptr;    // ... and the per-cell results between the two passes [n_elem][dim][nn]
   // reference matrices of the ngl = 3 element in tensor (lattice) order, from the uploaded tables (pyn_elem_tables_set):
   // Tf / Tr[r][s][a][b] = sum_g w Hrs_r[a] Hrs_s[b] (full / reduced rule), Uf / Ur[r][a][b] = sum_g w H[a] Hrs_r[b]
   double* d_ho3_tabs = nullptr;
@@ -384,6 +400,12 @@ int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]);  
 inline bool pyn_ho3_matfree_mesh(const pyn_ctx* c) { return c->ho3.valid && c->ho3.ngl == 3; }
 int pyn_ho3_matfree_set(pyn_ctx* c, int op);   // checks the mesh and tables, fills c->mf_ho3
 int pyn_ho3_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);
+// matrix-free KLE operator on box lattices of order ngl >= 4 (pyn_matfree_ho.hip)
+int pyn_ho_detect(pyn_ctx* c, const ConnAt& at);
+void pyn_ho_release(pyn_ctx* c);
+inline bool pyn_ho_matfree_mesh(const pyn_ctx* c) { return c->ngl >= 4; }   // pyn_matfree_set answers for these meshes (accepts or refuses)
+int pyn_ho_matfree_set(pyn_ctx* c, int op);   // the refusals, the 1-D tables, the scratch
+int pyn_ho_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);
 int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
 // dense LU shared by the direct solve and the coarsest multigrid level (pyn_direct.hip): piv holds 2 n + 1 ints
 int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n);

@@ -682,12 +682,14 @@ extern "C" int pyn_spmv(pyn_ctx* c, int mat_id, int xv, int yv) {
 // -----------------------------------------------------------------------------------------------
 static int matfree_product(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
   if (op == PYN_MATFREE_KLE && pyn_ho3_matfree_mesh(c)) return pyn_ho3_matfree_spmv(c, x, y, dot, grid_out);
+  if (op == PYN_MATFREE_KLE && pyn_ho_matfree_mesh(c)) return pyn_ho_matfree_spmv(c, x, y, dot, grid_out);
   return op == PYN_MATFREE_KLE ? pyn_lattice_matfree_kle_spmv(c, x, y, dot, grid_out) : pyn_lattice_matfree_spmv(c, x, y, dot, grid_out);
 }
 
 // DOFs per node of a matrix-free operator: the KLE operator has dim of them (3 on Q1 hexahedra, 2 or 3 on second-order lattices)
 static int matfree_bs(const pyn_ctx* c, int op) {
   if (op != PYN_MATFREE_KLE) return 1;
+  if (pyn_ho_matfree_mesh(c)) return c->dim;
   return pyn_ho3_matfree_mesh(c) ? c->ho3.dim : 3;
 }
 
@@ -696,6 +698,8 @@ extern "C" int pyn_matfree_set(pyn_ctx* c, int op, double alpha_d, double alpha_
   PYN_CHECK(op == PYN_MATFREE_LAPLACE || op == PYN_MATFREE_KLE, "unknown matrix-free operator %d", op);
   if (pyn_ho3_matfree_mesh(c))   // second-order lattice: the KLE operator on affine cells (pyn_matfree_ho3.hip)
     PYN_TRY(pyn_ho3_matfree_set(c, op));
+  else if (pyn_ho_matfree_mesh(c))   // box lattice of order ngl >= 4: the KLE operator on affine cells (pyn_matfree_ho.hip)
+    PYN_TRY(pyn_ho_matfree_set(c, op));
   else
     PYN_CHECK(pyn_lattice_matfree_supported(c), "matrix-free operator: needs a Q1 hexahedral mesh with structured topology and the "
                                                  "full-rule tables");
@@ -993,8 +997,8 @@ static int solve_cg_sr(pyn_ctx* c, DMat& A, const double* b, double* x, const py
   const int check = o.fixed_iters > 0 ? 0 : 1;
   const bool multi = pyn_has_comm(c);
   const SellShape* S = sell ? pyn_sell_shape(c, A) : nullptr;
-  // (the second-order matrix-free operator has no interior / boundary split: it takes the blocking exchange)
-  const bool overlap = multi && !c->neigh.empty() && !c->detached && (mf ? !pyn_ho3_matfree_mesh(c) : (S && S->int_begin >= 0)) &&
+  // (the second- and higher-order matrix-free operators have no interior / boundary split: they take the blocking exchange)
+  const bool overlap = multi && !c->neigh.empty() && !c->detached && (mf ? !(pyn_ho3_matfree_mesh(c) || pyn_ho_matfree_mesh(c)) : (S && S->int_begin >= 0)) &&
                        !getenv("PYNAMA_NO_OVERLAP");
   if (getenv("PYNAMA_OVERLAP_REQUIRE")) PYN_CHECK(overlap, "halo/SpMV overlap not engaged (tests)");
   const bool no_fuse = getenv("PYNAMA_NO_SCALAR_FUSE") != nullptr;   // diagnostics: scalar step in its own launch
