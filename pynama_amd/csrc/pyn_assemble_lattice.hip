@@ -1848,14 +1848,14 @@ static int launch_matfree_march(pyn_ctx* c, LatArgs& T, const double* x, double*
   return PYN_OK;
 }
 
-bool pyn_lattice_matfree_supported(const pyn_ctx* c) {
+static bool q1_matfree_supported(const pyn_ctx* c) {
   return c->lat.valid && c->dim == 3 && c->nn == 8 && c->quad[0].ngp == 8;
 }
 
 // y = A x with A = the scalar Laplacian under the mask snapshot of pyn_matfree_set; x carries the ghost tail.
 // zsel / part_off / max_grid / st: see MfLaunch (whole product on the context stream by default).
 static int matfree_laplace_launch(pyn_ctx* c, const double* x, double* y, bool dot, const MfLaunch& L, int* grid_out) {
-  PYN_CHECK(pyn_lattice_matfree_supported(c), "matrix-free operator: needs a Q1 hexahedral mesh with structured topology and the "
+  PYN_CHECK(q1_matfree_supported(c), "matrix-free operator: needs a Q1 hexahedral mesh with structured topology and the "
                                                "full-rule tables");
   PYN_CHECK(c->mf_set[PYN_MATFREE_LAPLACE], "matrix-free Laplacian: pyn_matfree_set first");
   LatArgs T;
@@ -1915,7 +1915,7 @@ static int launch_matfree_kle(pyn_ctx* c, KleLatArgs& K, bool affine, const doub
 
 // y = K x with K = the KLE stiffness under the per-DOF mask snapshot (pyn_matfree_set supplied alpha_d, alpha_w and took the mask)
 static int matfree_kle_launch(pyn_ctx* c, const double* x, double* y, bool dot, const MfLaunch& L, int* grid_out) {
-  PYN_CHECK(pyn_lattice_matfree_supported(c) && c->quad[1].ngp == 1,
+  PYN_CHECK(q1_matfree_supported(c) && c->quad[1].ngp == 1,
             "matrix-free operator: needs a Q1 hexahedral mesh with structured topology and the full- and reduced-rule tables");
   PYN_CHECK(c->mf_set[PYN_MATFREE_KLE], "matrix-free KLE operator: pyn_matfree_set first");
   KleLatArgs K;
@@ -1939,27 +1939,33 @@ static int matfree_kle_launch(pyn_ctx* c, const double* x, double* y, bool dot, 
   return PYN_OK;
 }
 
-int pyn_lattice_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out) {
-  MfLaunch L;
-  L.st = c->stream;
-  return matfree_laplace_launch(c, x, y, dot, L, grid_out);
-}
-
-int pyn_lattice_matfree_kle_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out) {
-  MfLaunch L;
-  L.st = c->stream;
-  return matfree_kle_launch(c, x, y, dot, L, grid_out);
-}
-
 // part of a product (op = PYN_MATFREE_*): zsel 1 = the tiles that read no ghost plane, 2 = the others (see mf_select_layers)
-int pyn_lattice_matfree_part(pyn_ctx* c, int op, const double* x, double* y, bool dot, int zsel, int part_off, int max_grid, hipStream_t st,
-                             int* grid_out) {
+static int q1_matfree_part(pyn_ctx* c, int op, const double* x, double* y, bool dot, int zsel, int part_off, int max_grid, hipStream_t st,
+                           int* grid_out) {
   MfLaunch L;
   L.zsel = zsel;
   L.part_off = part_off;
   L.max_grid = max_grid;
   L.st = st;
   return op == PYN_MATFREE_KLE ? matfree_kle_launch(c, x, y, dot, L, grid_out) : matfree_laplace_launch(c, x, y, dot, L, grid_out);
+}
+
+static int q1_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
+  return q1_matfree_part(c, op, x, y, dot, 0, 0, PYN_MAX_PARTIALS, c->stream, grid_out);   // every tile, on the context stream
+}
+
+static int q1_matfree_set(pyn_ctx* c, int) {
+  PYN_CHECK(q1_matfree_supported(c), "matrix-free operator: needs a Q1 hexahedral mesh with structured topology and the "
+                                      "full-rule tables");
+  return PYN_OK;
+}
+
+// the KLE operator has 3 DOFs per node on Q1 hexahedra
+static int q1_matfree_bs(const pyn_ctx*, int op) { return op == PYN_MATFREE_KLE ? 3 : 1; }
+
+const MfBackend* pyn_mf_q1() {
+  static const MfBackend b = {q1_matfree_supported, q1_matfree_set, q1_matfree_bs, q1_matfree_spmv, q1_matfree_part};
+  return &b;
 }
 
 // Node graph of a lattice whose numbering has the arithmetic shape (one rank, or a rank's z-slab): built directly,

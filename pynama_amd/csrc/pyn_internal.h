@@ -381,11 +381,6 @@ inline bool pyn_has_comm(const pyn_ctx* c) { return c->comm != nullptr || c->shm
 int pyn_allreduce_dev(pyn_ctx* c, double* dbuf, int n, int op, hipStream_t st);   // op 0 sum, 1 max; in place, device buffer
 int pyn_lattice_symbolic(pyn_ctx* c, bool* done);
 int pyn_assemble_lattice(pyn_ctx* c, double* A, double* Arhs, bool* handled);   // pyn_assemble_lattice.hip
-bool pyn_lattice_matfree_supported(const pyn_ctx* c);
-int pyn_lattice_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);  // matrix-free Laplacian
-int pyn_lattice_matfree_kle_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);  // matrix-free KLE stiffness
-int pyn_lattice_matfree_part(pyn_ctx* c, int op, const double* x, double* y, bool dot, int zsel, int part_off, int max_grid, hipStream_t st,
-                             int* grid_out);   // tiles without (zsel 1) / with (zsel 2) ghost planes: halo overlap
 int pyn_assemble_kle_lattice(pyn_ctx* c, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
 bool pyn_q1_mixed_tables_standard(const double* w, const double* H, const double* Hrs);
 bool pyn_q1_gauss_tables_standard(const double* w, const double* H, const double* Hrs, const double* HrsCoo);   // pyn_assemble_march.hip
@@ -396,22 +391,49 @@ void pyn_ho3_release(pyn_ctx* c);
 int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double* H, const double* Hrs);
 int pyn_ho3_symbolic(pyn_ctx* c, bool* done);
 int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]);   // every cell affine / axis-aligned; corner derivatives
-// matrix-free KLE operator on second-order lattices (pyn_matfree_ho3.hip)
-inline bool pyn_ho3_matfree_mesh(const pyn_ctx* c) { return c->ho3.valid && c->ho3.ngl == 3; }
-int pyn_ho3_matfree_set(pyn_ctx* c, int op);   // checks the mesh and tables, fills c->mf_ho3
-int pyn_ho3_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);
-// matrix-free KLE operator on box lattices of order ngl >= 4 (pyn_matfree_ho.hip)
+// box lattices of order ngl >= 4 (pyn_matfree_ho.hip)
 int pyn_ho_detect(pyn_ctx* c, const ConnAt& at);
 void pyn_ho_release(pyn_ctx* c);
-inline bool pyn_ho_matfree_mesh(const pyn_ctx* c) { return c->ngl >= 4; }   // pyn_matfree_set answers for these meshes (accepts or refuses)
-int pyn_ho_matfree_set(pyn_ctx* c, int op);   // the refusals, the 1-D tables, the scratch
-int pyn_ho_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);
 int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
 // dense LU shared by the direct solve and the coarsest multigrid level (pyn_direct.hip): piv holds 2 n + 1 ints
 int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n);
 int pyn_dense_lu_solve(pyn_ctx* c, const double* D, const int* piv, int64_t n, const double* b, double* x, double* z);
+// A matrix-free backend: the mesh family whose kernels apply the shell operators (PYN_MATFREE_*).  One static record per family, next
+// to its kernels: second-order lattices (pyn_matfree_ho3.hip), box lattices of order ngl >= 4 (pyn_matfree_ho.hip), Q1 lattices
+// (pyn_assemble_lattice.hip).
+struct MfBackend {
+  bool (*owns)(const pyn_ctx* c);
+  int (*set)(pyn_ctx* c, int op);        // the checks and tables of pyn_matfree_set
+  int (*bs)(const pyn_ctx* c, int op);   // DOFs per node of the operator
+  int (*spmv)(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out);   // dot: fused x.y partials into c->d_part
+  // tiles without (zsel 1) / with (zsel 2) ghost planes, for the halo overlap; null: the backend has no interior / boundary split
+  int (*part)(pyn_ctx* c, int op, const double* x, double* y, bool dot, int zsel, int part_off, int max_grid, hipStream_t st, int* grid_out);
+};
+const MfBackend* pyn_mf_ho3();
+const MfBackend* pyn_mf_ho();
+const MfBackend* pyn_mf_q1();
+inline const MfBackend* pyn_matfree_backend(const pyn_ctx* c) { return pyn_mf_ho3()->owns(c) ? pyn_mf_ho3() : pyn_mf_ho()->owns(c) ? pyn_mf_ho() : pyn_mf_q1(); }
+
+// "apply A" of one solve (pyn_krylov.hip): the matrix-free shell, the product chosen by pyn_sell_ensure, or 32-lane block CSR -- resolved
+// once by init, which is also the only reader of PYNAMA_NO_SELL.  No halo exchange; products run on c->stream.
+struct LinOp {
+  enum Ensure { SOLVER, ONCE, IF_READY };   // pyn_sell_ensure for a repeated product / for a one-off pyn_spmv / not at all: A.prod_ready decides
+  pyn_ctx* c = nullptr;
+  DMat* A = nullptr;
+  const MfBackend* mf = nullptr;   // the shell's backend (matfree != PYN_MATFREE_OFF)
+  int op = PYN_MATFREE_OFF;
+  bool ensured = false;            // multiply through pyn_sell_spmv
+  const SellShape* S = nullptr;
+  int init(pyn_ctx* c, DMat& A, int matfree, Ensure e = SOLVER);
+  int apply(const double* x, double* y) const;
+  int apply_dot(const double* x, double* y, int* grid) const;   // + the x.y partials in c->d_part[0 .. *grid), skipped once F_DONE is up
+  bool can_split() const { return mf ? mf->part != nullptr : (S && S->int_begin >= 0); }
+  // apply_dot in two parts: the rows that read no ghost, then -- after c->ev_halo -- the others (partials [0, *grid) all the same)
+  int apply_split(const double* x, double* y, int* grid) const;
+};
+
 // geometric multigrid (pyn_mg.hip): the hierarchy for the current values (built with the last options, or the defaults), and one
 // V-cycle z = M^-1 r whose level-0 products are prod0 (the assembled product or the matrix-free shell)
 int pyn_mg_ensure(pyn_ctx* c, DMat& A);
-int pyn_mg_vcycle(pyn_ctx* c, DMat& A, const double* r, double* z, const std::function<int(const double*, double*)>& prod0);
+int pyn_mg_vcycle(pyn_ctx* c, DMat& A, const double* r, double* z, const LinOp& prod0);
 int pyn_assemble_ho3_operator(pyn_ctx* c, int rule, int br, int bc, int nterms, const int32_t* terms, const double* coef, double* M, bool* handled);

@@ -559,6 +559,7 @@ __global__ void wmul_kernel(double* __restrict__ w, const double* __restrict__ d
 }
 
 inline int vgrid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 511) / 512, PYN_MAX_PARTIALS)); }
+inline int sgrid(int64_t rows) { return (int)std::max<int64_t>(1, std::min<int64_t>((rows * 32 + 255) / 256, PYN_MAX_PARTIALS)); }   // spmv_kernel<32>
 
 int dev_dot(pyn_ctx* c, const double* x, const double* y, int64_t n, double* out) {
   int g = vgrid(n);
@@ -570,9 +571,53 @@ int dev_dot(pyn_ctx* c, const double* x, const double* y, int64_t n, double* out
 
 int pyn_spmv_raw(pyn_ctx* c, const DMat& A, const double* x, double* y) {
   int64_t rows = c->n_owned * A.br;
-  int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows * 32 + 255) / 256, PYN_MAX_PARTIALS));
-  spmv_kernel<32, false><<<grid, 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, A.val, x, y, rows, A.br, A.bc, nullptr, nullptr);
+  spmv_kernel<32, false><<<sgrid(rows), 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, A.val, x, y, rows, A.br, A.bc, nullptr, nullptr);
   PYN_HIP(hipGetLastError());
+  return PYN_OK;
+}
+
+// ---- LinOp: how A is applied, decided once -------------------------------------------------------------------------
+int LinOp::init(pyn_ctx* ctx, DMat& M, int matfree, Ensure e) {
+  c = ctx;
+  A = &M;
+  op = matfree;
+  mf = matfree != PYN_MATFREE_OFF ? pyn_matfree_backend(ctx) : nullptr;
+  // a compact imposed-column matrix has no other product than the one pyn_sell_ensure sets up (its stored rows, block CSR)
+  ensured = !mf && (e != IF_READY || M.prod_ready) && (M.rhs_compact || (pyn_sell_supported(M) && !getenv("PYNAMA_NO_SELL")));
+  if (ensured && e != IF_READY) PYN_TRY(pyn_sell_ensure(ctx, M, e == SOLVER));
+  S = ensured ? pyn_sell_shape(ctx, M) : nullptr;
+  return PYN_OK;
+}
+
+int LinOp::apply(const double* x, double* y) const {
+  if (mf) return mf->spmv(c, op, x, y, false, nullptr);
+  return ensured ? pyn_sell_spmv(c, *A, x, y, false, nullptr) : pyn_spmv_raw(c, *A, x, y);
+}
+
+int LinOp::apply_dot(const double* x, double* y, int* grid) const {
+  const int64_t rows = c->n_owned * A->br;
+  *grid = sgrid(rows);
+  if (mf) return mf->spmv(c, op, x, y, true, grid);
+  if (ensured) return pyn_sell_spmv(c, *A, x, y, true, grid);
+  spmv_kernel<32, true><<<*grid, 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, A->val, x, y, rows, A->br, A->bc, c->d_flag, c->d_part);
+  return PYN_OK;
+}
+
+// the part that reads no ghost leaves its partials in [0, g0), at most PYN_MAX_PARTIALS - 512 of them; the rest (matrix-free: the bottom
+// and top layers of tiles; assembled: the bottom and top boundary slices in one launch) follows in [g0, g0 + g1), g1 <= 512
+int LinOp::apply_split(const double* x, double* y, int* grid) const {
+  hipStream_t s = c->stream;
+  int g0 = 0, g1 = 0;
+  if (mf) {
+    PYN_TRY(mf->part(c, op, x, y, true, 1, 0, PYN_MAX_PARTIALS - 512, s, &g0));
+    PYN_HIP(hipStreamWaitEvent(s, c->ev_halo, 0));
+    PYN_TRY(mf->part(c, op, x, y, true, 2, g0, 512, s, &g1));
+  } else {
+    PYN_TRY(pyn_sell_spmv_range(c, *A, x, y, true, S->int_begin, S->int_end, 0, PYN_MAX_PARTIALS - 512, s, &g0));
+    PYN_HIP(hipStreamWaitEvent(s, c->ev_halo, 0));
+    PYN_TRY(pyn_sell_spmv_range2(c, *A, x, y, true, 0, S->int_begin, S->int_end, S->ns, g0, 512, s, &g1));
+  }
+  *grid = g0 + g1;
   return PYN_OK;
 }
 
@@ -661,16 +706,11 @@ extern "C" int pyn_spmv(pyn_ctx* c, int mat_id, int xv, int yv) {
   if (A.rhs_compact) {   // rows that are not stored are zero rows: y = 0, then the stored rows from their block-CSR values
     PYN_TRY(pyn_rhs_ensure(c, A));
     PYN_HIP(hipMemsetAsync(c->vecs[yv].d, 0, (size_t)c->n_owned * A.br * sizeof(double), c->stream));
-    PYN_TRY(pyn_sell_ensure(c, A, false));
-    PYN_HIP(hipEventRecord(c->ev0, c->stream));
-    PYN_TRY(pyn_sell_spmv(c, A, c->vecs[xv].d, c->vecs[yv].d, false, nullptr));
-  } else if (pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL")) {  // multiply through the SELL-64 image
-    PYN_TRY(pyn_sell_ensure(c, A, false));
-    PYN_HIP(hipEventRecord(c->ev0, c->stream));  // time the product, not the (one-off) conversion
-    PYN_TRY(pyn_sell_spmv(c, A, c->vecs[xv].d, c->vecs[yv].d, false, nullptr));
-  } else {
-    PYN_TRY(pyn_spmv_raw(c, A, c->vecs[xv].d, c->vecs[yv].d));
   }
+  LinOp Aop;
+  PYN_TRY(Aop.init(c, A, PYN_MATFREE_OFF, LinOp::ONCE));
+  if (Aop.ensured) PYN_HIP(hipEventRecord(c->ev0, c->stream));  // time the product, not the (one-off) conversion
+  PYN_TRY(Aop.apply(c->vecs[xv].d, c->vecs[yv].d));
   PYN_HIP(hipEventRecord(c->ev1, c->stream));
   PYN_HIP(hipStreamSynchronize(c->stream));
   float ms = 0;
@@ -680,30 +720,12 @@ extern "C" int pyn_spmv(pyn_ctx* c, int mat_id, int xv, int yv) {
 }
 
 // -----------------------------------------------------------------------------------------------
-static int matfree_product(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
-  if (op == PYN_MATFREE_KLE && pyn_ho3_matfree_mesh(c)) return pyn_ho3_matfree_spmv(c, x, y, dot, grid_out);
-  if (op == PYN_MATFREE_KLE && pyn_ho_matfree_mesh(c)) return pyn_ho_matfree_spmv(c, x, y, dot, grid_out);
-  return op == PYN_MATFREE_KLE ? pyn_lattice_matfree_kle_spmv(c, x, y, dot, grid_out) : pyn_lattice_matfree_spmv(c, x, y, dot, grid_out);
-}
-
-// DOFs per node of a matrix-free operator: the KLE operator has dim of them (3 on Q1 hexahedra, 2 or 3 on second-order lattices)
-static int matfree_bs(const pyn_ctx* c, int op) {
-  if (op != PYN_MATFREE_KLE) return 1;
-  if (pyn_ho_matfree_mesh(c)) return c->dim;
-  return pyn_ho3_matfree_mesh(c) ? c->ho3.dim : 3;
-}
-
 extern "C" int pyn_matfree_set(pyn_ctx* c, int op, double alpha_d, double alpha_w) {
   PYN_CHECK(c, "NULL context");
   PYN_CHECK(op == PYN_MATFREE_LAPLACE || op == PYN_MATFREE_KLE, "unknown matrix-free operator %d", op);
-  if (pyn_ho3_matfree_mesh(c))   // second-order lattice: the KLE operator on affine cells (pyn_matfree_ho3.hip)
-    PYN_TRY(pyn_ho3_matfree_set(c, op));
-  else if (pyn_ho_matfree_mesh(c))   // box lattice of order ngl >= 4: the KLE operator on affine cells (pyn_matfree_ho.hip)
-    PYN_TRY(pyn_ho_matfree_set(c, op));
-  else
-    PYN_CHECK(pyn_lattice_matfree_supported(c), "matrix-free operator: needs a Q1 hexahedral mesh with structured topology and the "
-                                                 "full-rule tables");
-  const int bs = matfree_bs(c, op);
+  const MfBackend* mf = pyn_matfree_backend(c);
+  PYN_TRY(mf->set(c, op));
+  const int bs = mf->bs(c, op);
   PYN_CHECK(!c->d_bcmask || c->bc_ndof == bs, "matrix-free operator %d: the current Dirichlet mask must have %d DOF(s) per node", op, bs);
   PYN_HIP(hipSetDevice(c->device));
   (void)hipFree(c->mf_mask[op]);
@@ -729,12 +751,13 @@ extern "C" int pyn_matfree_apply(pyn_ctx* c, int op, int xv, int yv) {
   PYN_TRY(pyn_check_vec(c, xv, "pyn_matfree_apply x"));
   PYN_TRY(pyn_check_vec(c, yv, "pyn_matfree_apply y"));
   PYN_CHECK(xv != yv, "x and y must differ");
-  const int bs = matfree_bs(c, op);
+  const MfBackend* mf = pyn_matfree_backend(c);
+  const int bs = mf->bs(c, op);
   PYN_CHECK(c->vecs[xv].bs == bs && c->vecs[yv].bs == bs, "this matrix-free operator acts on vectors of block size %d", bs);
   PYN_HIP(hipSetDevice(c->device));
   PYN_TRY(pyn_halo_exchange(c, c->vecs[xv].d, bs));
   PYN_HIP(hipEventRecord(c->ev0, c->stream));
-  PYN_TRY(matfree_product(c, op, c->vecs[xv].d, c->vecs[yv].d, false, nullptr));
+  PYN_TRY(mf->spmv(c, op, c->vecs[xv].d, c->vecs[yv].d, false, nullptr));
   PYN_HIP(hipEventRecord(c->ev1, c->stream));
   PYN_HIP(hipStreamSynchronize(c->stream));
   float ms = 0;
@@ -747,28 +770,69 @@ static int allreduce_tmp(pyn_ctx* c, int n) {
   return pyn_allreduce_dev(c, c->d_scal + S_TMP0, n, 0, c->stream);
 }
 
+// ---- what the drivers share at their ends ---------------------------------------------------------------------------------
+static int prof_pool(pyn_ctx* c, int count) {   // at least `count` events for the per-launch timing
+  while ((int)c->prof_ev.size() < count) {
+    hipEvent_t e;
+    PYN_HIP(hipEventCreate(&e));
+    c->prof_ev.push_back(e);
+  }
+  return PYN_OK;
+}
+
+// mean device time between the event pairs (a0 + k sa, b0 + k sb), k < count
+static int prof_mean(pyn_ctx* c, int a0, int sa, int b0, int sb, int count, double* out) {
+  double acc = 0;
+  for (int k = 0; k < count; ++k) {
+    float t = 0;
+    PYN_HIP(hipEventElapsedTime(&t, c->prof_ev[a0 + k * sa], c->prof_ev[b0 + k * sb]));
+    acc += t;
+  }
+  *out = acc / count;
+  return PYN_OK;
+}
+
+static int fill_info(pyn_ctx* c, pyn_solve_info* info, int iters, int reason, double rnorm, double rnorm0) {   // ev0 .. ev1 have passed
+  float ms = 0;
+  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  info->solve_ms = ms;
+  info->iters = iters;
+  info->reason = reason;
+  info->rnorm = rnorm;
+  info->rnorm0 = rnorm0;
+  return PYN_OK;
+}
+
+// end of a CG loop: flags and scalars come back with ONE synchronisation; prof_n products were bracketed by the events (2 k, 2 k + 1)
+static int cg_finish(pyn_ctx* c, pyn_solve_info* info, int prof_n) {
+  hipStream_t s = c->stream;
+  PYN_HIP(hipEventRecord(c->ev1, s));
+  PYN_HIP(hipMemcpyAsync(c->h_flag, c->d_flag, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipMemcpyAsync(c->h_scal, c->d_scal, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipStreamSynchronize(s));
+  if (prof_n) {
+    PYN_TRY(prof_mean(c, 0, 2, 1, 2, prof_n, &info->spmv_ms));
+    info->spmv_launches = prof_n;
+  }
+  return fill_info(c, info, c->h_flag[F_ITERS], c->h_flag[F_REASON] ? c->h_flag[F_REASON] : PYN_DIVERGED_ITS, c->h_scal[S_RNORM], c->h_scal[S_RNORM0]);
+}
+
 static int solve_cg(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_solve_opts& o, pyn_solve_info* info) {
-  const bool mf = o.matfree != PYN_MATFREE_OFF;
-  const bool sell = !mf && pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL");
-  if (sell) PYN_TRY(pyn_sell_ensure(c, A));
+  LinOp Aop;
+  PYN_TRY(Aop.init(c, A, o.matfree));
   const int64_t n = c->n_owned * A.br;
   const int64_t nl = n_local(c) * A.br;
-  // work: r[n] p[nl] Ap[n] dinv[n] hist
+  // work: r[n] p[nl] Ap[n] hist
   const int hist_cap = 4096;
-  size_t need = (size_t)(3 * n + nl + hist_cap) * sizeof(double);
-  PYN_TRY(pyn_ensure_work(c, need));
+  PYN_TRY(pyn_ensure_work(c, (size_t)(2 * n + nl + hist_cap) * sizeof(double)));
   double* r = c->d_work;
   double* p = r + n;
   double* Ap = p + nl;
-  double* dinv = Ap + n;
-  double* hist = dinv + n;
+  double* hist = Ap + n;
   const bool jac = o.pc == PYN_PC_JACOBI;
   if (jac) PYN_TRY(pyn_dinv_ensure(c, A));   // cached per matrix version (written by the lattice assemblies themselves)
   const double* dv = jac ? A.dinv : nullptr;
-  (void)dinv;
   const int g = vgrid(n);
-  const int64_t rows = n;
-  const int gs = (int)std::max<int64_t>(1, std::min<int64_t>((rows * 32 + 255) / 256, PYN_MAX_PARTIALS));
   hipStream_t s = c->stream;
   const int maxit = o.fixed_iters > 0 ? o.fixed_iters : o.maxit;
   const int check = o.fixed_iters > 0 ? 0 : 1;
@@ -788,11 +852,7 @@ static int solve_cg(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_s
   const int chunk = 32;
   const bool selfred = !pyn_has_comm(c) && !getenv("PYNAMA_NO_CG_FUSE");
   const int prof_max = o.profile ? 256 : 0;
-  while ((int)c->prof_ev.size() < 2 * prof_max) {
-    hipEvent_t e;
-    PYN_HIP(hipEventCreate(&e));
-    c->prof_ev.push_back(e);
-  }
+  PYN_TRY(prof_pool(c, 2 * prof_max));
   int prof_n = 0;
   while (!done && issued < maxit) {
     int todo = std::min(chunk, maxit - issued);
@@ -800,13 +860,8 @@ static int solve_cg(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_s
       PYN_TRY(pyn_halo_exchange(c, p, A.bc));
       const bool prof = prof_n < prof_max;
       if (prof) PYN_HIP(hipEventRecord(c->prof_ev[2 * prof_n], s));
-      int gsp = gs;
-      if (mf)
-        PYN_TRY(matfree_product(c, o.matfree, p, Ap, true, &gsp));
-      else if (sell)
-        PYN_TRY(pyn_sell_spmv(c, A, p, Ap, true, &gsp));
-      else
-        spmv_kernel<32, true><<<gs, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, p, Ap, rows, A.br, A.bc, c->d_flag, c->d_part);
+      int gsp = 0;
+      PYN_TRY(Aop.apply_dot(p, Ap, &gsp));
       if (prof) PYN_HIP(hipEventRecord(c->prof_ev[2 * prof_n++ + 1], s));
       if (selfred) {   // one rank: the consumers sum the partials and step the scalars themselves
         const int it = issued + k + 1;
@@ -828,28 +883,7 @@ static int solve_cg(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_s
     PYN_HIP(hipStreamSynchronize(s));
     done = c->h_flag[F_DONE];
   }
-  PYN_HIP(hipEventRecord(c->ev1, s));
-  PYN_HIP(hipMemcpyAsync(c->h_flag, c->d_flag, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
-  PYN_HIP(hipMemcpyAsync(c->h_scal, c->d_scal, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
-  PYN_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  info->solve_ms = ms;
-  if (prof_n) {
-    double acc = 0;
-    for (int k = 0; k < prof_n; ++k) {
-      float t = 0;
-      PYN_HIP(hipEventElapsedTime(&t, c->prof_ev[2 * k], c->prof_ev[2 * k + 1]));
-      acc += t;
-    }
-    info->spmv_ms = acc / prof_n;
-    info->spmv_launches = prof_n;
-  }
-  info->iters = c->h_flag[F_ITERS];
-  info->reason = c->h_flag[F_REASON] ? c->h_flag[F_REASON] : PYN_DIVERGED_ITS;
-  info->rnorm = c->h_scal[S_RNORM];
-  info->rnorm0 = c->h_scal[S_RNORM0];
-  return PYN_OK;
+  return cg_finish(c, info, prof_n);
 }
 
 // ---- PCG with the geometric multigrid preconditioner (pyn_mg.hip): unfused, z = Vcycle(r) between the update and the dots --------
@@ -897,11 +931,10 @@ __global__ void __launch_bounds__(256) mg_cg_p_kernel(const double* __restrict__
 }
 
 static int solve_cg_mg(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_solve_opts& o, pyn_solve_info* info) {
-  const bool mf = o.matfree != PYN_MATFREE_OFF;
-  const bool sell = !mf && pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL");
   PYN_TRY(pyn_mg_ensure(c, A));
   PYN_TRY(pyn_dinv_ensure(c, A));
-  if (sell) PYN_TRY(pyn_sell_ensure(c, A));
+  LinOp Aop;   // the iteration's product is also the level-0 product of the V-cycle
+  PYN_TRY(Aop.init(c, A, o.matfree));
   const int64_t n = c->n_owned * A.br;
   // work: r[n] p[n] Ap[n] z[n]
   PYN_TRY(pyn_ensure_work(c, (size_t)4 * n * sizeof(double)));
@@ -910,20 +943,13 @@ static int solve_cg_mg(pyn_ctx* c, DMat& A, const double* b, double* x, const py
   double* Ap = p + n;
   double* z = Ap + n;
   const int g = vgrid(n);
-  const int gs = (int)std::max<int64_t>(1, std::min<int64_t>((n * 32 + 255) / 256, PYN_MAX_PARTIALS));
   hipStream_t s = c->stream;
   const int maxit = o.fixed_iters > 0 ? o.fixed_iters : o.maxit;
   const int check = o.fixed_iters > 0 ? 0 : 1;
-  // level-0 product of the V-cycle: the one the iteration uses
-  auto prod0 = [&](const double* in, double* out) -> int {
-    if (mf) return matfree_product(c, o.matfree, in, out, false, nullptr);
-    if (sell) return pyn_sell_spmv(c, A, in, out, false, nullptr);
-    return pyn_spmv_raw(c, A, in, out);
-  };
 
   PYN_HIP(hipEventRecord(c->ev0, s));
   mg_cg_init_kernel<<<g, 256, 0, s>>>(b, x, r, n);
-  PYN_TRY(pyn_mg_vcycle(c, A, r, z, prod0));
+  PYN_TRY(pyn_mg_vcycle(c, A, r, z, Aop));
   mg_cg_dots_kernel<<<g, 256, 0, s>>>(r, z, p, n, o.norm_type, c->d_part);
   sum_partials_kernel<<<1, 256, 0, s>>>(c->d_part, 2, g, c->d_scal + S_TMP0, nullptr);
   cg_scalar_init_kernel<<<1, 1, 0, s>>>(c->d_scal, c->d_flag, check ? o.rtol : 0.0, check ? o.atol : 0.0, o.dtol, o.norm_type, nullptr);
@@ -933,17 +959,12 @@ static int solve_cg_mg(pyn_ctx* c, DMat& A, const double* b, double* x, const py
   if (!check) PYN_HIP(hipMemsetAsync(c->d_flag, 0, sizeof(int), s));   // fixed-iteration mode ignores "already converged"
   int issued = 0;
   while (!done && issued < maxit) {
-    int gsp = gs;
-    if (mf)
-      PYN_TRY(matfree_product(c, o.matfree, p, Ap, true, &gsp));
-    else if (sell)
-      PYN_TRY(pyn_sell_spmv(c, A, p, Ap, true, &gsp));
-    else
-      spmv_kernel<32, true><<<gs, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, p, Ap, n, A.br, A.bc, c->d_flag, c->d_part);
+    int gsp = 0;
+    PYN_TRY(Aop.apply_dot(p, Ap, &gsp));
     sum_partials_kernel<<<1, 256, 0, s>>>(c->d_part, 1, gsp, c->d_scal + S_TMP0, c->d_flag);
     cg_scalar_alpha_kernel<<<1, 1, 0, s>>>(c->d_scal, c->d_flag);
     mg_cg_update_kernel<<<g, 256, 0, s>>>(c->d_scal, c->d_flag, p, Ap, x, r, n);
-    PYN_TRY(pyn_mg_vcycle(c, A, r, z, prod0));
+    PYN_TRY(pyn_mg_vcycle(c, A, r, z, Aop));
     mg_cg_dots_kernel<<<g, 256, 0, s>>>(r, z, nullptr, n, o.norm_type, c->d_part);
     sum_partials_kernel<<<1, 256, 0, s>>>(c->d_part, 2, g, c->d_scal + S_TMP0, c->d_flag);
     cg_scalar_beta_kernel<<<1, 1, 0, s>>>(c->d_scal, c->d_flag, o.norm_type, maxit, check, nullptr, 0);
@@ -954,52 +975,34 @@ static int solve_cg_mg(pyn_ctx* c, DMat& A, const double* b, double* x, const py
     PYN_HIP(hipStreamSynchronize(s));
     done = c->h_flag[F_DONE];
   }
-  PYN_HIP(hipEventRecord(c->ev1, s));
-  PYN_HIP(hipMemcpyAsync(c->h_flag, c->d_flag, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
-  PYN_HIP(hipMemcpyAsync(c->h_scal, c->d_scal, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
-  PYN_HIP(hipStreamSynchronize(s));
   PYN_HIP(hipGetLastError());
-  float ms = 0;
-  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  info->solve_ms = ms;
-  info->iters = c->h_flag[F_ITERS];
-  info->reason = c->h_flag[F_REASON] ? c->h_flag[F_REASON] : PYN_DIVERGED_ITS;
-  info->rnorm = c->h_scal[S_RNORM];
-  info->rnorm0 = c->h_scal[S_RNORM0];
-  return PYN_OK;
+  return cg_finish(c, info, 0);
 }
 
 static int solve_cg_sr(pyn_ctx* c, DMat& A, const double* b, double* x, const pyn_solve_opts& o, pyn_solve_info* info) {
-  const bool mf = o.matfree != PYN_MATFREE_OFF;
-  const bool sell = !mf && pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL");
-  if (sell) PYN_TRY(pyn_sell_ensure(c, A));
+  LinOp Aop;
+  PYN_TRY(Aop.init(c, A, o.matfree));
   const int64_t n = c->n_owned * A.br;
   const int64_t nl = n_local(c) * A.br;
   const int hist_cap = 4096;
-  // work: r[n] u[nl] w[n] p[n] s[n] dinv[n] hist
-  PYN_TRY(pyn_ensure_work(c, (size_t)(5 * n + nl + hist_cap) * sizeof(double)));
+  // work: r[n] u[nl] w[n] p[n] s[n] hist
+  PYN_TRY(pyn_ensure_work(c, (size_t)(4 * n + nl + hist_cap) * sizeof(double)));
   double* r = c->d_work;
   double* u = r + n;
   double* w = u + nl;
   double* p = w + n;
   double* sv = p + n;
-  double* dinv = sv + n;
-  double* hist = dinv + n;
+  double* hist = sv + n;
   const bool jac = o.pc == PYN_PC_JACOBI;
   if (jac) PYN_TRY(pyn_dinv_ensure(c, A));   // cached per matrix version (written by the lattice assemblies themselves)
   const double* dv = jac ? A.dinv : nullptr;
-  (void)dinv;
   const int g = vgrid(n);
-  const int64_t rows = n;
-  const int gs = (int)std::max<int64_t>(1, std::min<int64_t>((rows * 32 + 255) / 256, PYN_MAX_PARTIALS));
   hipStream_t s = c->stream;
   const int maxit = o.fixed_iters > 0 ? o.fixed_iters : o.maxit;
   const int check = o.fixed_iters > 0 ? 0 : 1;
   const bool multi = pyn_has_comm(c);
-  const SellShape* S = sell ? pyn_sell_shape(c, A) : nullptr;
-  // (the second- and higher-order matrix-free operators have no interior / boundary split: they take the blocking exchange)
-  const bool overlap = multi && !c->neigh.empty() && !c->detached && (mf ? !(pyn_ho3_matfree_mesh(c) || pyn_ho_matfree_mesh(c)) : (S && S->int_begin >= 0)) &&
-                       !getenv("PYNAMA_NO_OVERLAP");
+  // (a product without an interior / boundary split takes the blocking exchange)
+  const bool overlap = multi && !c->neigh.empty() && !c->detached && Aop.can_split() && !getenv("PYNAMA_NO_OVERLAP");
   if (getenv("PYNAMA_OVERLAP_REQUIRE")) PYN_CHECK(overlap, "halo/SpMV overlap not engaged (tests)");
   const bool no_fuse = getenv("PYNAMA_NO_SCALAR_FUSE") != nullptr;   // diagnostics: scalar step in its own launch
 
@@ -1007,11 +1010,7 @@ static int solve_cg_sr(pyn_ctx* c, DMat& A, const double* b, double* x, const py
   cgsr_init_kernel<<<g, 256, 0, s>>>(b, dv, x, r, u, p, sv, n, o.norm_type, c->d_part);
   PYN_HIP(hipEventRecord(c->ev0, s));
   const int prof_max = o.profile ? 256 : 0;
-  while ((int)c->prof_ev.size() < 6 * prof_max) {   // [0, 2 P): product brackets, [2 P, 3 P): reduction end, [4 P, 6 P): halo brackets
-    hipEvent_t e;
-    PYN_HIP(hipEventCreate(&e));
-    c->prof_ev.push_back(e);
-  }
+  PYN_TRY(prof_pool(c, 6 * prof_max));   // [0, 2 P): product brackets, [2 P, 3 P): reduction end, [4 P, 6 P): halo brackets
   int prof_n = 0, issued = 0, done = 0;
   const int chunk = 32;
   // iteration k: w = A u_k ; scalars (tests ||r_k||, alpha_k, beta_k) ; update -> r_{k+1}, u_{k+1}
@@ -1019,7 +1018,7 @@ static int solve_cg_sr(pyn_ctx* c, DMat& A, const double* b, double* x, const py
     const int todo = std::min(chunk, maxit + 1 - issued);
     for (int k = 0; k < todo; ++k) {
       const bool prof = prof_n < prof_max;
-      int gsp = gs;
+      int gsp = 0;
       if (overlap) {
         // halo exchange of u on the communication stream while the rows without ghost columns are multiplied;
         // the boundary rows follow once the ghosts have arrived.  u (owned part) is final here: record, let the
@@ -1031,27 +1030,11 @@ static int solve_cg_sr(pyn_ctx* c, DMat& A, const double* b, double* x, const py
         if (prof) PYN_HIP(hipEventRecord(c->prof_ev[4 * prof_max + 2 * prof_n + 1], c->comm_stream));
         PYN_HIP(hipEventRecord(c->ev_halo, c->comm_stream));
         if (prof) PYN_HIP(hipEventRecord(c->prof_ev[2 * prof_n], s));
-        int g0 = 0, g1 = 0, g2 = 0;
-        if (mf) {   // tiles that read no ghost plane, then (ghosts arrived) the bottom / top layers of tiles
-          PYN_TRY(pyn_lattice_matfree_part(c, o.matfree, u, w, true, 1, 0, PYN_MAX_PARTIALS - 512, s, &g0));
-          PYN_HIP(hipStreamWaitEvent(s, c->ev_halo, 0));
-          PYN_TRY(pyn_lattice_matfree_part(c, o.matfree, u, w, true, 2, g0, 512, s, &g1));
-        } else {
-          PYN_TRY(pyn_sell_spmv_range(c, A, u, w, true, S->int_begin, S->int_end, 0, PYN_MAX_PARTIALS - 512, s, &g0));
-          PYN_HIP(hipStreamWaitEvent(s, c->ev_halo, 0));
-          // bottom and top boundary slices in one launch
-          PYN_TRY(pyn_sell_spmv_range2(c, A, u, w, true, 0, S->int_begin, S->int_end, S->ns, g0, 512, s, &g1));
-        }
-        gsp = g0 + g1 + g2;
+        PYN_TRY(Aop.apply_split(u, w, &gsp));
       } else {
         PYN_TRY(pyn_halo_exchange(c, u, A.bc));
         if (prof) PYN_HIP(hipEventRecord(c->prof_ev[2 * prof_n], s));
-        if (mf)
-          PYN_TRY(matfree_product(c, o.matfree, u, w, true, &gsp));
-        else if (sell)
-          PYN_TRY(pyn_sell_spmv(c, A, u, w, true, &gsp));
-        else
-          spmv_kernel<32, true><<<gs, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, u, w, rows, A.br, A.bc, c->d_flag, c->d_part);
+        PYN_TRY(Aop.apply_dot(u, w, &gsp));
       }
       if (prof) PYN_HIP(hipEventRecord(c->prof_ev[2 * prof_n + 1], s));
       const int first = (issued + k) == 0;
@@ -1079,46 +1062,13 @@ static int solve_cg_sr(pyn_ctx* c, DMat& A, const double* b, double* x, const py
     PYN_HIP(hipStreamSynchronize(s));
     done = c->h_flag[F_DONE];
   }
-  PYN_HIP(hipEventRecord(c->ev1, s));
-  PYN_HIP(hipMemcpyAsync(c->h_flag, c->d_flag, 8 * sizeof(int), hipMemcpyDeviceToHost, s));
-  PYN_HIP(hipMemcpyAsync(c->h_scal, c->d_scal, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
-  PYN_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  info->solve_ms = ms;
+  PYN_TRY(cg_finish(c, info, prof_n));
   if (prof_n) {
-    double acc = 0;
-    for (int k = 0; k < prof_n; ++k) {
-      float t = 0;
-      PYN_HIP(hipEventElapsedTime(&t, c->prof_ev[2 * k], c->prof_ev[2 * k + 1]));
-      acc += t;
-    }
-    info->spmv_ms = acc / prof_n;
-    info->spmv_launches = prof_n;
-    acc = 0;
-    for (int k = 0; k < prof_n; ++k) {
-      float t = 0;
-      PYN_HIP(hipEventElapsedTime(&t, c->prof_ev[2 * k + 1], c->prof_ev[2 * prof_max + k]));
-      acc += t;
-    }
-    info->reduce_ms = acc / prof_n;
-    if (overlap) {
-      acc = 0;
-      for (int k = 0; k < prof_n; ++k) {
-        float t = 0;
-        PYN_HIP(hipEventElapsedTime(&t, c->prof_ev[4 * prof_max + 2 * k], c->prof_ev[4 * prof_max + 2 * k + 1]));
-        acc += t;
-      }
-      info->halo_ms = acc / prof_n;
-    }
+    PYN_TRY(prof_mean(c, 1, 2, 2 * prof_max, 1, prof_n, &info->reduce_ms));
+    if (overlap) PYN_TRY(prof_mean(c, 4 * prof_max, 2, 4 * prof_max + 1, 2, prof_n, &info->halo_ms));
   }
-  info->iters = c->h_flag[F_ITERS];
-  info->reason = c->h_flag[F_REASON] ? c->h_flag[F_REASON] : PYN_DIVERGED_ITS;
-  info->rnorm = c->h_scal[S_RNORM];
-  info->rnorm0 = c->h_scal[S_RNORM0];
   return PYN_OK;
 }
-
 
 // ---- fused classical Gram-Schmidt for GMRES: all k+1 projections in ONE pass over the basis -----------------
 // h[j] = V_j . w for j < k1 (partials per block, chunks of 8 vectors so the accumulators stay in registers)
@@ -1299,13 +1249,12 @@ static int solve_gmres(pyn_ctx* c, DMat& A, const double* b, double* x, const py
   const int64_t nl = n_local(c) * A.br;
   const int m = std::max(1, o.restart);
   const int mh = m + 2;                                  // h1[m+1], then (offset mh) h2[m+1], then (2 mh) the norm
-  size_t need = (size_t)((int64_t)(m + 1) * nl + 2 * nl + n + (int64_t)(m + 1) * MD_GRID + 3 * mh + (int64_t)(m + 1) * m + 3 * m + 1) * sizeof(double);
+  size_t need = (size_t)((int64_t)(m + 1) * nl + 2 * nl + (int64_t)(m + 1) * MD_GRID + 3 * mh + (int64_t)(m + 1) * m + 3 * m + 1) * sizeof(double);
   PYN_TRY(pyn_ensure_work(c, need));
   double* V = c->d_work;            // (m+1) x nl
   double* w = V + (int64_t)(m + 1) * nl;  // nl (needs ghost space as SpMV input? no: output) -> n used
   double* t = w + nl;               // nl  (SpMV input with ghosts)
-  double* dinv = t + nl;
-  double* mpart = dinv + n;         // (m+1) x MD_GRID partial sums of the fused projections
+  double* mpart = t + nl;           // (m+1) x MD_GRID partial sums of the fused projections
   double* dh = mpart + (int64_t)(m + 1) * MD_GRID;       // device copy of the projection coefficients
   double* Hd = dh + 3 * mh;                              // (m+1) x m Hessenberg matrix after the rotations, then cs, sn, g
   double* csd = Hd + (int64_t)(m + 1) * m;
@@ -1313,21 +1262,14 @@ static int solve_gmres(pyn_ctx* c, DMat& A, const double* b, double* x, const py
   double* ggd = snd + m;
   const bool mgs = o.gmres_orthog == 2 || getenv("PYNAMA_GMRES_MGS") != nullptr;
   const int npass = o.gmres_orthog == 1 ? 1 : 2;
-  // the product: matrix-free operator, the SELL-64 image, or block CSR
-  const bool sell = !o.matfree && pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL");
-  if (sell) PYN_TRY(pyn_sell_ensure(c, A));
-  auto product = [&](const double* xin, double* yout) -> int {
-    if (o.matfree) return matfree_product(c, o.matfree, xin, yout, false, nullptr);
-    if (sell) return pyn_sell_spmv(c, A, xin, yout, false, nullptr);
-    return pyn_spmv_raw(c, A, xin, yout);
-  };
+  LinOp Aop;
+  PYN_TRY(Aop.init(c, A, o.matfree));
   const int mdg = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, MD_GRID));
   // grid of the update that also leaves the |vn|^2 partials: they may spill over all rows of mpart (consumed by then)
   const int gn = (int)std::min<int64_t>(vgrid(n), (int64_t)(m + 1) * MD_GRID);
   const bool jac = o.pc == PYN_PC_JACOBI;
   if (jac) PYN_TRY(pyn_dinv_ensure(c, A));   // cached per matrix version (written by the lattice assemblies themselves)
   const double* dv = jac ? A.dinv : nullptr;
-  (void)dinv;
   hipStream_t s = c->stream;
   const int g = vgrid(n);
   PYN_HIP(hipMemsetAsync(x, 0, n * sizeof(double), s));
@@ -1347,7 +1289,7 @@ static int solve_gmres(pyn_ctx* c, DMat& A, const double* b, double* x, const py
     // r = dinv (b - A x)
     PYN_HIP(hipMemcpyAsync(t, x, n * sizeof(double), hipMemcpyDeviceToDevice, s));
     PYN_TRY(pyn_halo_exchange(c, t, A.bc));
-    PYN_TRY(product(t, w));
+    PYN_TRY(Aop.apply(t, w));
     waxpby_kernel<<<g, 256, 0, s>>>(w, 1.0, b, -1.0, w, n);
     double uu = 0;
     if (unpre) PYN_TRY(dev_dot(c, w, w, n, &uu));
@@ -1379,7 +1321,7 @@ static int solve_gmres(pyn_ctx* c, DMat& A, const double* b, double* x, const py
         double* vk = V + (int64_t)k * nl;
         double* vn = V + (int64_t)(k + 1) * nl;
         PYN_TRY(pyn_halo_exchange(c, vk, A.bc));
-        PYN_TRY(product(vk, w));
+        PYN_TRY(Aop.apply(vk, w));
         const int k1 = k + 1;
         for (int pass = 0; pass < npass; ++pass) {      // projection + update (, then once more: refinement)
           // pass 0 also forms vn = dinv .* w; the last pass also leaves the partial sums of |vn|^2 in mpart[0][..]
@@ -1415,7 +1357,7 @@ static int solve_gmres(pyn_ctx* c, DMat& A, const double* b, double* x, const py
       double* vk = V + (int64_t)k * nl;
       double* vn = V + (int64_t)(k + 1) * nl;
       PYN_TRY(pyn_halo_exchange(c, vk, A.bc));
-      PYN_TRY(product(vk, w));
+      PYN_TRY(Aop.apply(vk, w));
       double hh = 0;
       wmul_kernel<<<g, 256, 0, s>>>(vn, dv, w, n);
       for (int j = 0; j <= k; ++j) {
@@ -1456,14 +1398,7 @@ static int solve_gmres(pyn_ctx* c, DMat& A, const double* b, double* x, const py
   }
   PYN_HIP(hipEventRecord(c->ev1, s));
   PYN_HIP(hipStreamSynchronize(s));
-  float ms = 0;
-  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  info->solve_ms = ms;
-  info->iters = its;
-  info->reason = reason;
-  info->rnorm = rn;
-  info->rnorm0 = rnorm0;
-  return PYN_OK;
+  return fill_info(c, info, its, reason, rn, rnorm0);
 }
 
 extern "C" int pyn_solve(pyn_ctx* c, int mat_id, int bv, int xv, const pyn_solve_opts* opts, pyn_solve_info* info) {
@@ -1489,13 +1424,15 @@ extern "C" int pyn_solve(pyn_ctx* c, int mat_id, int bv, int xv, const pyn_solve
   if (opts->matfree) {
     // the shell operator must BE the assembled matrix (which keeps supplying the Jacobi diagonal and the exit check):
     // compare both products on b before iterating
-    PYN_CHECK(A.br == matfree_bs(c, opts->matfree), "matrix-free operator: block size of the matrix does not match");
+    LinOp shell;
+    PYN_TRY(shell.init(c, A, opts->matfree));
+    PYN_CHECK(A.br == shell.mf->bs(c, opts->matfree), "matrix-free operator: block size of the matrix does not match");
     const int64_t n1 = c->n_owned * A.br;
     PYN_TRY(pyn_ensure_work(c, (size_t)2 * n1 * sizeof(double)));
     double *w0 = c->d_work, *w1 = c->d_work + n1;
     PYN_TRY(pyn_halo_exchange(c, b, A.bc));
     PYN_TRY(pyn_spmv_raw(c, A, b, w0));
-    PYN_TRY(matfree_product(c, opts->matfree, b, w1, false, nullptr));
+    PYN_TRY(shell.apply(b, w1));
     waxpby_kernel<<<vgrid(n1), 256, 0, c->stream>>>(w1, 1.0, w0, -1.0, w1, n1);
     double dd = 0, aa = 0;
     PYN_TRY(dev_dot(c, w1, w1, n1, &dd));
@@ -1528,10 +1465,9 @@ extern "C" int pyn_solve(pyn_ctx* c, int mat_id, int bv, int xv, const pyn_solve
   PYN_TRY(pyn_ensure_work(c, (size_t)n * sizeof(double)));
   double* w = c->d_work;
   PYN_TRY(pyn_halo_exchange(c, x, A.bc));
-  if (A.prod_ready && pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL"))
-    PYN_TRY(pyn_sell_spmv(c, A, x, w, false, nullptr));   // the image the iteration just used (2.6x the CSR product)
-  else
-    PYN_TRY(pyn_spmv_raw(c, A, x, w));
+  LinOp Aop;   // the product the iteration just used, if it used one (2.6x the CSR product)
+  PYN_TRY(Aop.init(c, A, PYN_MATFREE_OFF, LinOp::IF_READY));
+  PYN_TRY(Aop.apply(x, w));
   waxpby_kernel<<<vgrid(n), 256, 0, c->stream>>>(w, 1.0, b, -1.0, w, n);
   double rr = 0, bb = 0;
   PYN_TRY(dev_dot(c, w, w, n, &rr));

@@ -11,7 +11,7 @@
 // space and both rules are symmetric under a flip of a reference axis, so the lattice orientation gives the reference's operator
 // (2-D meshes carry the x ~ -r, y ~ -s flip of SURVEY.md A.2).  The 1-D tables (Lobatto nodes / weights, the derivative matrix at
 // the nodes, values and derivatives at the Gauss(ngl - 1) points) are recomputed on the host for the mesh's order
-// (pyn_ho_tables_1d) and checked against the uploaded tensor tables in pyn_ho_matfree_set.
+// (pyn_ho_tables_1d) and checked against the uploaded tensor tables in ho_matfree_set.
 //
 // Mapping: one lane per node of a cell (2-D and low 3-D orders: several cells per workgroup), x_e and the tables in LDS, every
 // contraction along one axis with a barrier between the axes.  Two passes:
@@ -857,7 +857,7 @@ int pyn_ho_detect(pyn_ctx* c, const ConnAt& at) {
 
 // pyn_matfree_set on a mesh of order ngl >= 4: the refusals, the 1-D tables of the order (checked against the uploaded reduced-rule
 // tables), the per-cell scratch
-int pyn_ho_matfree_set(pyn_ctx* c, int op) {
+static int ho_matfree_set(pyn_ctx* c, int op) {
   const int dim = c->dim, ngl = c->ngl, lim = pyn_ho_matfree_max_ngl(dim);
   PYN_CHECK(ngl >= 4, "matrix-free operator: not a mesh of order ngl >= 4");
   PYN_CHECK(op == PYN_MATFREE_KLE, "matrix-free operator %d: meshes of order ngl >= 4 have the matrix-free KLE operator only "
@@ -923,9 +923,9 @@ int pyn_ho_matfree_set(pyn_ctx* c, int op) {
 
 // y = K x under the mask snapshot of pyn_matfree_set; x carries the ghost tail.  dot: fused p.Ap partials into c->d_part (one per
 // workgroup of the gather pass, *grid_out of them).
-int pyn_ho_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out) {
+static int ho_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
   PYN_CHECK(c->ho.valid, "matrix-free operator: not a structured mesh of order ngl >= 4");
-  PYN_CHECK(c->mf_set[PYN_MATFREE_KLE] && c->d_ho_tab && c->d_ho_ye, "matrix-free KLE operator: pyn_matfree_set first");
+  PYN_CHECK(op == PYN_MATFREE_KLE && c->mf_set[PYN_MATFREE_KLE] && c->d_ho_tab && c->d_ho_ye, "matrix-free KLE operator: pyn_matfree_set first");
   const HoLattice& L = c->ho;
   const HoMfArgs A = ho_args(c);
   const int* flag = dot ? c->d_flag : nullptr;
@@ -946,4 +946,13 @@ int pyn_ho_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* g
   }
   PYN_HIP(hipGetLastError());
   return PYN_OK;
+}
+
+// every mesh of order ngl >= 4 is answered here: ho_matfree_set accepts it or says why not
+static bool ho_matfree_mesh(const pyn_ctx* c) { return c->ngl >= 4; }
+static int ho_matfree_bs(const pyn_ctx* c, int op) { return op == PYN_MATFREE_KLE ? c->dim : 1; }
+
+const MfBackend* pyn_mf_ho() {
+  static const MfBackend b = {ho_matfree_mesh, ho_matfree_set, ho_matfree_bs, ho_matfree_spmv, nullptr};
+  return &b;
 }

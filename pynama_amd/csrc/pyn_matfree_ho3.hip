@@ -8,7 +8,7 @@
 //                               D = grad u (physical), W = alpha_d tr(D) I + alpha_w (D - D^T), test side sum_dp Dv[d][p] W[d][p]
 // On an affine cell J^-1 is constant, so both are sum factorisations with 1-D point bases: the 1-D factors of pyn_ho3_tables
 // (M = sum w h h, D = sum w h' h, S = sum w h' h' per rule) are split on the host as M = B^T B, D = G^T B, S = G^T G with
-// B, G [points][3 nodes] (pyn_ho3_matfree_set; the square roots of the weights sit in B and G).  Any such split gives the same
+// B, G [points][3 nodes] (ho3_matfree_set; the square roots of the weights sit in B and G).  Any such split gives the same
 // operator because the point-wise map is the same at every point of an affine cell.  A cell's product runs one z-point slice at
 // a time (3-D): 3x3 / 2x3 contractions along one axis at a time, never a dense 27 x 27 block.
 //
@@ -516,8 +516,10 @@ bool split_rule(const double* M, const double* D, const double* S, double (&B)[N
 
 // pyn_matfree_set(PYN_MATFREE_KLE) on a second-order lattice: every cell affine, tables that are tensor products of one full (Gauss 3)
 // and one reduced (Gauss 2) rule; fills c->mf_ho3
-int pyn_ho3_matfree_set(pyn_ctx* c, int op) {
-  PYN_CHECK(pyn_ho3_matfree_mesh(c), "matrix-free operator: not a second-order structured mesh");
+static bool ho3_matfree_mesh(const pyn_ctx* c) { return c->ho3.valid && c->ho3.ngl == 3; }
+
+static int ho3_matfree_set(pyn_ctx* c, int op) {
+  PYN_CHECK(ho3_matfree_mesh(c), "matrix-free operator: not a second-order structured mesh");
   PYN_CHECK(op == PYN_MATFREE_KLE, "matrix-free operator %d: second-order (ngl 3) meshes have the matrix-free KLE operator only "
                                    "(PYN_MATFREE_KLE)", op);
   PYN_CHECK(c->ho3_tabs_nn == c->nn && c->ho3_tabs_ok[0] && c->ho3_tabs_ok[1] && c->ho3_tens_ok && c->quad[0].ngp > 0,
@@ -546,9 +548,9 @@ int pyn_ho3_matfree_set(pyn_ctx* c, int op) {
 
 // y = K x, K = the KLE stiffness of pyn_assemble_kle on a second-order lattice under the mask snapshot of pyn_matfree_set; x carries
 // the ghost tail.  dot: fused p.Ap partials into c->d_part (one per workgroup, *grid_out of them).
-int pyn_ho3_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out) {
-  PYN_CHECK(pyn_ho3_matfree_mesh(c), "matrix-free operator: not a second-order structured mesh");
-  PYN_CHECK(c->mf_set[PYN_MATFREE_KLE], "matrix-free KLE operator: pyn_matfree_set first");
+static int ho3_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
+  PYN_CHECK(ho3_matfree_mesh(c), "matrix-free operator: not a second-order structured mesh");
+  PYN_CHECK(op == PYN_MATFREE_KLE && c->mf_set[PYN_MATFREE_KLE], "matrix-free KLE operator: pyn_matfree_set first");
   const Ho3Lattice& L = c->ho3;
   Ho3MfArgs A;
   A.xyz = c->d_xyz;
@@ -573,4 +575,12 @@ int pyn_ho3_matfree_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* 
   }
   if (dg) return dot ? launch_ho3_matfree_dim<2, true, true>(c, A, x, y, grid_out) : launch_ho3_matfree_dim<2, true, false>(c, A, x, y, grid_out);
   return dot ? launch_ho3_matfree_dim<2, false, true>(c, A, x, y, grid_out) : launch_ho3_matfree_dim<2, false, false>(c, A, x, y, grid_out);
+}
+
+// 2 or 3 DOFs per node
+static int ho3_matfree_bs(const pyn_ctx* c, int op) { return op == PYN_MATFREE_KLE ? c->ho3.dim : 1; }
+
+const MfBackend* pyn_mf_ho3() {
+  static const MfBackend b = {ho3_matfree_mesh, ho3_matfree_set, ho3_matfree_bs, ho3_matfree_spmv, nullptr};
+  return &b;
 }

@@ -551,11 +551,9 @@ static Grid grid_of(const MgHier& H, int l) {
 
 // the level-0 product of the set-up: the assembled matrix, through the image the CG loop uses
 static int mg_assembled_product(pyn_ctx* c, DMat& A, const double* x, double* y) {
-  if (pyn_sell_supported(A) && !getenv("PYNAMA_NO_SELL")) {
-    PYN_TRY(pyn_sell_ensure(c, A));
-    return pyn_sell_spmv(c, A, x, y, false, nullptr);
-  }
-  return pyn_spmv_raw(c, A, x, y);
+  LinOp op;
+  PYN_TRY(op.init(c, A, PYN_MATFREE_OFF));
+  return op.apply(x, y);
 }
 
 static int mg_dot(pyn_ctx* c, const double* x, const double* y, int64_t n, double* out) {
@@ -816,7 +814,7 @@ static int vcycle_level(pyn_ctx* c, MgHier& H, int l, double** out) {
   return PYN_OK;
 }
 
-int pyn_mg_vcycle(pyn_ctx* c, DMat& A, const double* r, double* z, const std::function<int(const double*, double*)>& prod0) {
+int pyn_mg_vcycle(pyn_ctx* c, DMat& A, const double* r, double* z, const LinOp& prod0) {
   MgHier& H = *A.mg;
   MgLevel& L = H.L[0];
   hipStream_t s = c->stream;
@@ -827,19 +825,19 @@ int pyn_mg_vcycle(pyn_ctx* c, DMat& A, const double* r, double* z, const std::fu
   double rho = 0, c1 = 0, c2 = 0;
   for (int j = 0; j < k; ++j) {   // pre-smoothing from zero
     cheb_coef(H, L.lam, j, &rho, &c1, &c2);
-    if (j > 0) PYN_TRY(prod0(z, Az));
+    if (j > 0) PYN_TRY(prod0.apply(z, Az));
     mg_cheb0_kernel<<<gv, 256, 0, s>>>(r, j > 0 ? Az : nullptr, z, L.d, A.dinv, L.dec, L.diag, c1, c2, n);
   }
   const Grid g = grid_of(H, 0), gc = grid_of(H, 1);
   MgLevel& C = H.L[1];
-  PYN_TRY(prod0(z, Az));
+  PYN_TRY(prod0.apply(z, Az));
   PYN_MG_DISPATCH(b, dim, (mg_restrict_kernel<B_, D_><<<grid_for(C.nn), 256, 0, s>>>(g, gc, nullptr, r, nullptr, Az, L.dec, C.dec, C.b)));
   double* ec = nullptr;
   PYN_TRY(vcycle_level(c, H, 1, &ec));
   PYN_MG_DISPATCH(b, dim, (mg_prolong_kernel<B_, D_><<<grid_for(L.nn), 256, 0, s>>>(g, gc, ec, L.dec, C.dec, z)));
   for (int j = 0; j < k; ++j) {   // post-smoothing
     cheb_coef(H, L.lam, j, &rho, &c1, &c2);
-    PYN_TRY(prod0(z, Az));
+    PYN_TRY(prod0.apply(z, Az));
     // the first post step starts a new polynomial: d = D^-1 t / theta (c1 = 0), z += d
     mg_cheb0_kernel<<<gv, 256, 0, s>>>(r, Az, z, L.d, A.dinv, L.dec, L.diag, j == 0 ? 0.0 : c1, c2, n);
   }
@@ -883,7 +881,9 @@ extern "C" int pyn_mg_apply(pyn_ctx* c, int mat_id, int rv, int zv) {
   PYN_HIP(hipSetDevice(c->device));
   PYN_TRY(pyn_mg_ensure(c, A));
   PYN_TRY(pyn_dinv_ensure(c, A));
-  PYN_TRY(pyn_mg_vcycle(c, A, c->vecs[rv].d, c->vecs[zv].d, [&](const double* x, double* y) { return mg_assembled_product(c, A, x, y); }));
+  LinOp op;
+  PYN_TRY(op.init(c, A, PYN_MATFREE_OFF));
+  PYN_TRY(pyn_mg_vcycle(c, A, c->vecs[rv].d, c->vecs[zv].d, op));
   PYN_HIP(hipStreamSynchronize(c->stream));
   PYN_HIP(hipGetLastError());
   return PYN_OK;
