@@ -385,6 +385,34 @@ int pyn_mg_apply(pyn_ctx* ctx, int mat_id, int r_vec, int z_vec);
  * k = sum_a (o_a + 1) 3^a for the node offset o in {-1, 0, 1}^dim (x first) */
 int pyn_mg_level_get(pyn_ctx* ctx, int mat_id, int level, double* out);
 
+/* ---- immersed boundary (pyn_ibm.hip) ---------------------------------------------------------
+ * One set of Lagrangian markers per context, on a UNIFORM node lattice (structured box mesh of ngl 2 or 3, pyn_mesh_topology kind
+ * 1, 2 or 3; nodes lower + i h, x fastest).  With W_kj = prod_d phi((x_jd - X_kd) / h_d): interpolation (H u)_k = sum_j W_kj u_j,
+ * spreading (S q)_j = sum_k W_kj c_k q_k with c_k = dl_k / prod_d h_d, and A = H S (n x n, the same for every component).
+ * Velocity vectors have block size dim; marker arrays on the host are [marker][component].  Every sum has a fixed order (no
+ * atomics): repeated calls give identical bits.  Every entry but pyn_ibm_set is PYN_EINVAL before a successful pyn_ibm_set. */
+/* Uploads the markers and builds, for this position, the stencils, the node-major spreading lists, A and its dense LU factors --
+ * ImmersedBoundaryStatic.buildIBMMatrix (src/cases/immersed_boundary.py) with the marker loops of src/domain/immersed_body.py.
+ * kernel 0: Peskin's 4-point delta (the reference's fourGrid), 1: Roma's 3-point delta (threeGrid).  X[n*dim], dl[n] (arc-length /
+ * area element), lower[dim], h[dim].  Refused with a message, before any kernel touches the markers: more than one rank or ghost
+ * nodes; a mesh of kind 0; nodes that are not lower + i h to 1e-12 of the box extent (checked on the device); a stencil line outside
+ * 1 .. n_d - 2 on any axis (imposed boundary nodes are never altered); n = 0 or n > pyn_direct_max_rows(); non-finite X or dl.
+ * A refused call leaves no marker set. */
+int pyn_ibm_set(pyn_ctx* ctx, int kernel, int dim, int64_t n, const double* X, const double* dl, const double* lower, const double* h);
+/* out[n*dim] = H u -- the interpolation loop of computeVelocityCorrection */
+int pyn_ibm_interp(pyn_ctx* ctx, int u_vec, double* out);
+/* u += S q, q[n*dim] -- the spreading loop of computeVelocityCorrection */
+int pyn_ibm_spread(pyn_ctx* ctx, const double* q, int u_vec);
+/* The whole of computeVelocityCorrection in one call: r = ub - H u stays on the device, A q = r per component with the cached
+ * factors, u += S q; q_out[n*dim] is the only device -> host copy.  Afterwards H u = ub. */
+int pyn_ibm_correct(pyn_ctx* ctx, int u_vec, const double* ub, double* q_out);
+/* A[n*n] row-major (the reference's H S product, for condition numbers and tests) */
+int pyn_ibm_matrix_get(pyn_ctx* ctx, double* A);
+/* info[4]: markers, stencil width per axis (4 or 3), affected lattice nodes, pyn_ibm_set builds since the set was created */
+int pyn_ibm_info(pyn_ctx* ctx, int64_t* info);
+/* drops the marker set (pyn_mesh_set / pyn_mesh_box and pyn_ctx_destroy do the same) */
+int pyn_ibm_clear(pyn_ctx* ctx);
+
 /* ---- timers -------------------------------------------------------------------------------
  * Device time (HIP events on the context stream) of the last call of each phase, in ms.
  * Replaces the tic/toc log of src/run_case.py:156-162. */

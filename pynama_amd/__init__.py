@@ -15,12 +15,12 @@ __version__ = "0.1.0"
 
 _SUBPACKAGES = {
     "elements": ("element", "utilities", "spectral", "simplex"),
-    "domain": ("dmplex", "gmsh"),
+    "domain": ("dmplex", "gmsh", "immersed_body"),
     "viewer": ("xml_generator", "paraviewer", "hdf5_writer"),
     "matrices": ("mat_generator", "mat_ns"),
     "solver": ("ksp_solver", "ts_solver"),
     "common": ("timer", "nswalls", "options", "comm"),
-    "cases": ("base_problem", "uniform", "custom_func", "cavity"),
+    "cases": ("base_problem", "uniform", "custom_func", "cavity", "immersed_boundary"),
 }
 
 

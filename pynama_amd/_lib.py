@@ -130,6 +130,13 @@ SIGNATURES = {
     "pyn_mg_info": [_P, _I, C.POINTER(_I), _pi64, _pf64, C.POINTER(_D), C.POINTER(_I)],
     "pyn_mg_apply": [_P, _I, _I, _I],
     "pyn_mg_level_get": [_P, _I, _I, _pf64],
+    "pyn_ibm_set": [_P, _I, _I, _L, _pf64, _pf64, _pf64, _pf64],
+    "pyn_ibm_interp": [_P, _I, _pf64],
+    "pyn_ibm_spread": [_P, _pf64, _I],
+    "pyn_ibm_correct": [_P, _I, _pf64, _pf64],
+    "pyn_ibm_matrix_get": [_P, _pf64],
+    "pyn_ibm_info": [_P, _pi64],
+    "pyn_ibm_clear": [_P],
     "pyn_timers_get": [_P, _pf64, _I],
 }
 
@@ -648,6 +655,64 @@ class Context:
         out = np.empty(rows * 3 ** self.dim * b)
         _check(self.lib.pyn_mg_level_get(self.h, mid, level, out))
         return out.reshape(rows // b, 3 ** self.dim, b, b)
+
+    # -- immersed boundary
+    def ibm_set(self, kernel, X, dl, lower, h):
+        """marker set X [n, dim] with weights dl [n] on the uniform node lattice lower + i h: stencils, node-major spreading lists,
+        A = H S and its LU factors for this position (kernel 0: 4-point delta, 1: 3-point)"""
+        X = _f64(X)
+        dim = self.dim
+        if X.ndim == 1:
+            X = X.reshape(-1, dim) if dim else X.reshape(0, 1)
+        dl, lower, h = _f64(dl).ravel(), _f64(lower).ravel(), _f64(h).ravel()
+        n = X.shape[0]
+        if dl.size != n or lower.size != dim or h.size != dim or (n and X.shape[1] != dim):
+            raise PynamaHipError(f"ibm_set: X {X.shape}, dl {dl.shape}, lower {lower.shape}, h {h.shape} do not fit {n} markers in {dim}-D")
+        pad = np.zeros(1)
+        _check(self.lib.pyn_ibm_set(self.h, int(kernel), dim, n, X if n else pad, dl if n else pad, lower, h))
+
+    def _ibm_count(self):
+        return int(self.ibm_info()["markers"])
+
+    def ibm_interp(self, u):
+        """H u at the markers, [n, dim]"""
+        out = np.empty((self._ibm_count(), self.dim))
+        _check(self.lib.pyn_ibm_interp(self.h, u, out))
+        return out
+
+    def ibm_spread(self, q, u):
+        """u += S q, q [n, dim]"""
+        q = _f64(q)
+        n = self._ibm_count()
+        if q.size != n * self.dim:
+            raise PynamaHipError(f"ibm_spread: q has {q.size} entries, the marker set needs {n} x {self.dim}")
+        _check(self.lib.pyn_ibm_spread(self.h, q, u))
+
+    def ibm_correct(self, u, ub):
+        """solve A q = ub - H u per component and u += S q on the device; returns q [n, dim]"""
+        ub = _f64(ub)
+        n = self._ibm_count()
+        if ub.size != n * self.dim:
+            raise PynamaHipError(f"ibm_correct: ub has {ub.size} entries, the marker set needs {n} x {self.dim}")
+        q = np.empty((n, self.dim))
+        _check(self.lib.pyn_ibm_correct(self.h, u, ub, q))
+        return q
+
+    def ibm_matrix(self):
+        """A = H S, [n, n]"""
+        n = self._ibm_count()
+        A = np.empty((n, n))
+        _check(self.lib.pyn_ibm_matrix_get(self.h, A))
+        return A
+
+    def ibm_info(self):
+        """{'markers', 'width' (stencil lines per axis), 'affected_nodes', 'builds'}"""
+        info = np.zeros(4, np.int64)
+        _check(self.lib.pyn_ibm_info(self.h, info))
+        return {"markers": int(info[0]), "width": int(info[1]), "affected_nodes": int(info[2]), "builds": int(info[3])}
+
+    def ibm_clear(self):
+        _check(self.lib.pyn_ibm_clear(self.h))
 
     def timers(self):
         t = np.zeros(8)

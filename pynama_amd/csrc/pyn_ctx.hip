@@ -160,6 +160,7 @@ extern "C" int pyn_ctx_destroy(pyn_ctx* c) {
   (void)hipFree(c->lat.d_zord);
   pyn_ho3_release(c);
   pyn_ho_release(c);
+  pyn_ibm_release(c);
   (void)hipFree(c->d_ho3_tabs);
   (void)hipFree(c->d_ho3_t1d);
   (void)hipFree(c->d_bcmask);
@@ -609,6 +610,7 @@ static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
     c->mf_mask[k] = nullptr;
     c->mf_set[k] = false;
   }
+  pyn_ibm_release(c);             // ... and so does the immersed-boundary marker set
   PYN_TRY(pyn_lattice_detect(c, at));
   PYN_TRY(pyn_ho3_detect(c, at));
   PYN_TRY(pyn_ho_detect(c, at));

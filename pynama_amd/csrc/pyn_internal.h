@@ -342,6 +342,7 @@ struct pyn_ctx {
   // element-local scratch for pyn_elem_local
   double* d_eloc = nullptr;
   size_t eloc_bytes = 0;
+  struct IbmState* ibm = nullptr;   // immersed-boundary marker set (pyn_ibm.hip): stencils, node-major spreading lists, A = H S and its LU
 };
 
 inline int64_t n_local(const pyn_ctx* c) { return c->n_owned + c->n_ghost; }
@@ -395,7 +396,8 @@ int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]);  
 int pyn_ho_detect(pyn_ctx* c, const ConnAt& at);
 void pyn_ho_release(pyn_ctx* c);
 int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
-// dense LU shared by the direct solve and the coarsest multigrid level (pyn_direct.hip): piv holds 2 n + 1 ints
+void pyn_ibm_release(pyn_ctx* c);   // pyn_ibm.hip: the marker set belongs to the mesh
+// dense LU shared by the direct solve, the coarsest multigrid level and the immersed-boundary force solve (pyn_direct.hip): piv holds 2 n + 1 ints
 int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n);
 int pyn_dense_lu_solve(pyn_ctx* c, const double* D, const int* piv, int64_t n, const double* b, double* x, double* z);
 // A matrix-free backend: the mesh family whose kernels apply the shell operators (PYN_MATFREE_*).  One static record per family, next

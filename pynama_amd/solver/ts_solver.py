@@ -19,7 +19,9 @@ same step was rejected as well; ``e = 0`` gives the factor 10, a NaN or Inf norm
 rejection rolls ``X`` back (``X -= sum_j h b_j K_j``, the same maxpy with negated weights) and retries; more than
 ``max_reject`` rejections of one step end the solve with reason -2 (``TS_DIVERGED_STEP_REJECTED``).  ``MATCHSTEP`` shortens
 the step that would pass ``max_time`` and lands on it exactly.  Reasons: 1 ``TS_CONVERGED_TIME``, 2 ``TS_CONVERGED_ITS``.
-The post-step callback runs once per accepted step.
+The post-step callback runs once per accepted step.  A callback that changes the state (the immersed-boundary correction does) calls
+``restartStep()`` -- the role of PETSc's ``TSRestartStep`` -- and the next step evaluates stage 0 at the changed state instead of
+taking the FSAL stage of the step before; ``getPrevTime()`` is the time before the last accepted step.
 
 Options (PETSc names): ``-ts_type rk`` (any other type raises), ``-ts_rk_type 5bs|3bs|4``, ``-ts_dt``, ``-ts_max_time``,
 ``-ts_max_steps``, ``-ts_adapt_type basic|none`` (default ``basic`` for a tableau with an embedded pair; ``4`` has none and always
@@ -149,6 +151,8 @@ class TsSolver(object):
         self.steps, self.rejects, self.rhs_evals, self.reason = 0, 0, 0, 0
         self._rhs, self._post = None, None
         self._stages = None
+        self._restart = False                   # restartStep() since the last stage 0
+        self.t_prev = self.t
         self.setType("rk")
         self.setRKType("5bs")
         self.setExactFinalTime(self.ExactFinalTime.MATCHSTEP)
@@ -245,6 +249,14 @@ class TsSolver(object):
 
     time = property(getTime, setTime)
 
+    def getPrevTime(self):
+        """time before the last accepted step (TSGetPrevTime): getTime() - getPrevTime() is the step a post-step callback just saw"""
+        return self.t_prev
+
+    def restartStep(self):
+        """the state was changed from outside (TSRestartStep): the next step evaluates stage 0 again, no FSAL stage is reused"""
+        self._restart = True
+
     def getTimeStep(self):
         return self.dt
 
@@ -302,6 +314,8 @@ class TsSolver(object):
             if self.t >= self.max_time:
                 self.reason = self.ConvergedReason.CONVERGED_TIME
                 break
+            if self._restart:
+                have_k0, self._restart = False, False
             rejected = 0
             while True:
                 hh, last = h, False
@@ -335,6 +349,7 @@ class TsSolver(object):
                     self.dt = h
                     self.logger.warning(f"step {self.steps} at t = {self.t:.6e}: {rejected} rejections, giving up (reason -2)")
                     return
+            self.t_prev = self.t
             self.t = self.max_time if last else self.t + hh
             self.steps += 1
             h = h_next
