@@ -35,25 +35,19 @@
 
 namespace {
 
-// lattice offset (x, y[, z]) in {0, 1, 2} of local node a: the reference's vertex / edge / face / interior order
-// (spectral.py:346-431, fixture tests/golden/g2_tables.npz `order_*`); 2-D carries the x ~ -r, y ~ -s flip of SURVEY.md A.2
-constexpr int LOC2[9][2] = {{0, 0}, {2, 0}, {2, 2}, {0, 2}, {1, 0}, {2, 1}, {1, 2}, {0, 1}, {1, 1}};
-// first-order cells: the corners in DMPlex closure order (src/tests/test_domain.py:26-30, 94-104)
-constexpr int LOQ2[4][2] = {{0, 0}, {1, 0}, {1, 1}, {0, 1}};
-constexpr int LOQ3[8][3] = {{0, 0, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}, {0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}};
-constexpr int LOC3[27][3] = {{0, 0, 0}, {0, 2, 0}, {2, 2, 0}, {2, 0, 0}, {0, 0, 2}, {2, 0, 2}, {2, 2, 2}, {0, 2, 2}, {0, 1, 0},
-                             {1, 2, 0}, {2, 1, 0}, {1, 0, 0}, {1, 0, 2}, {2, 1, 2}, {1, 2, 2}, {0, 1, 2}, {2, 0, 1}, {0, 0, 1},
-                             {0, 2, 1}, {2, 2, 1}, {1, 1, 0}, {1, 1, 2}, {1, 0, 1}, {1, 2, 1}, {2, 1, 1}, {0, 1, 1}, {1, 1, 1}};
-
-inline int loc_of(int dim, int ngl, int a, int d) {
-  if (ngl == 2) return dim == 2 ? LOQ2[a][d] : LOQ3[a][d];
-  return dim == 2 ? LOC2[a][d] : LOC3[a][d];
-}
-inline int tens_of(int dim, int ngl, int a) {
-  int t = 0;
-  for (int d = dim - 1; d >= 0; --d) t = t * ngl + loc_of(dim, ngl, a, d);
-  return t;
-}
+// lattice offset (x, y[, z]) of every local node of an ngl 2 / 3 cell, [a * dim + d], and its tensor position x + ngl (y + ngl z): the
+// reference's vertex / edge / face / interior order with the 2-D flip (mesh_local_lattice; tests/test_ho_matfree_host.py)
+struct LocalOrder {
+  int dim, ngl;
+  std::vector<int> loc;
+  LocalOrder(int dim_, int ngl_) : dim(dim_), ngl(ngl_) { mesh_local_lattice(ngl, dim, loc); }
+  int loc_of(int a, int d) const { return loc[a * dim + d]; }
+  int tens_of(int a) const {
+    int t = 0;
+    for (int d = dim - 1; d >= 0; --d) t = t * ngl + loc_of(a, d);
+    return t;
+  }
+};
 
 enum { M_K = 0, M_RW = 1, M_LAP = 2, M_OP = 3 };
 constexpr int MAX_TERMS = 32;
@@ -106,26 +100,10 @@ __device__ __forceinline__ int x_prefix(int x, int NX) {
 // exact k / n for 0 <= k < 2048, n in {2, 3, 4, 5, 6, 9, 15, 25}
 __device__ __forceinline__ int small_div(int k, int n) { return (k * (65536 / n + 1)) >> 16; }
 
-// corner cn of an element (first 2^dim local nodes) as lattice bits x | y << 1 | z << 2 -- LOC2 / LOC3 halved, spelled out for device code
+// corner cn of an element (first 2^dim local nodes) as lattice bits x | y << 1 | z << 2, spelled out for device code (checked against
+// the local node order by pyn_ho3_view)
 constexpr int CB2[4] = {0, 1, 3, 2};
 constexpr int CB3[8] = {0, 2, 3, 1, 4, 5, 7, 6};
-constexpr bool corner_bits_match() {
-  for (int cn = 0; cn < 4; ++cn)
-    if (CB2[cn] != ((LOC2[cn][0] >> 1) | ((LOC2[cn][1] >> 1) << 1))) return false;
-  for (int cn = 0; cn < 8; ++cn)
-    if (CB3[cn] != ((LOC3[cn][0] >> 1) | ((LOC3[cn][1] >> 1) << 1) | ((LOC3[cn][2] >> 1) << 2))) return false;
-  return true;
-}
-static_assert(corner_bits_match(), "corner tables out of step with the local node order");
-constexpr bool q1_corners_match() {
-  for (int cn = 0; cn < 4; ++cn)
-    if (CB2[cn] != (LOQ2[cn][0] | (LOQ2[cn][1] << 1))) return false;
-  for (int cn = 0; cn < 8; ++cn)
-    if (CB3[cn] != (LOQ3[cn][0] | (LOQ3[cn][1] << 1) | (LOQ3[cn][2] << 2))) return false;
-  return true;
-}
-static_assert(q1_corners_match(), "first-order corner table out of step");
-
 template <int DIM>
 __global__ void __launch_bounds__(256) ho3_geom_kernel(const int32_t* __restrict__ conn, const double* __restrict__ xyz, int64_t n_elem, int NN,
                                                        const double* __restrict__ hcoo, double* __restrict__ geom, int* __restrict__ not_affine) {
@@ -996,12 +974,13 @@ __global__ void ho3_columns_kernel(Ho3Args T, int dim, int ngl, int64_t n_rows, 
 }
 
 void fill_lattice_args(const pyn_ctx* c, Ho3Args& T) {
-  const Ho3Lattice& L = c->ho3;
+  const BoxLattice& L = c->box;
+  const bool d3 = L.dim == 3;
   T.EX = L.EX;
-  T.EY = L.EY;
-  T.EZ = L.EZ;
+  T.EY = d3 ? L.EY : L.EL;   // 2-D: the element rows are the layers, EZ and NY stay 0
+  T.EZ = d3 ? L.EL : 0;
   T.NX = L.NX;
-  T.NY = L.NY;
+  T.NY = d3 ? L.NY : 0;
   T.npl = L.npl;
   T.p_own0 = L.p_own0;
   T.n_own = L.n_own;
@@ -1009,7 +988,7 @@ void fill_lattice_args(const pyn_ctx* c, Ho3Args& T) {
   T.rowptr = c->d_rowptr;
   T.nbits = nullptr;
   T.runflag = nullptr;
-  T.geom = L.d_geom;
+  T.geom = c->ho3.d_geom;
   T.tabs = c->d_ho3_tabs;
   T.tabs1d = c->ho3_tens_ok ? c->d_ho3_t1d : nullptr;
   T.alpha_d = T.alpha_w = 0.0;
@@ -1021,16 +1000,8 @@ void fill_lattice_args(const pyn_ctx* c, Ho3Args& T) {
   T.so0 = 0;
   T.img_len = 0;
   T.step = L.ngl == 3 ? 2 : 1;
-  T.diag = L.diag == 1 && !getenv("PYNAMA_HO3_NO_DIAG");
-  {
-    const int64_t PS = L.dim == 3 ? (int64_t)L.NX * L.NY : L.NX;
-    bool std_p = !getenv("PYNAMA_HO3_NO_PSTD") && PS * L.npl < (int64_t)INT32_MAX;
-    for (int j = 0; j < L.npl && std_p; ++j) {
-      const int64_t want = (j < L.p_own0 ? L.n_own + j : (j >= L.p_own0 + L.n_own ? j : j - L.p_own0)) * PS;
-      std_p = L.P[j] == want;
-    }
-    T.pstd = std_p;
-  }
+  T.diag = c->ho3.diag == 1 && !getenv("PYNAMA_HO3_NO_DIAG");
+  T.pstd = !getenv("PYNAMA_HO3_NO_PSTD") && L.plane() * L.npl < (int64_t)INT32_MAX && L.slab_order();
   {
     const char* ab = getenv("PYNAMA_HO3_ABLATE");
     T.ablate = ab ? atoi(ab) : 0;
@@ -1043,7 +1014,8 @@ template <int DIM, int NGL, int MAT, int R, bool DG>
 int launch_ho3_g(pyn_ctx* c, Ho3Args T) {
   const int BR = MAT == M_OP ? T.obr : (MAT == M_LAP ? 1 : DIM);
   const int BC = MAT == M_OP ? T.obc : (MAT == M_K ? DIM : (MAT == M_RW ? (DIM == 3 ? 3 : 1) : 1));
-  Ho3Lattice& L = c->ho3;
+  const BoxLattice& L = c->box;
+  Ho3View& V = c->ho3;
   T.nruns = (L.NX + R - 1) / R;
   static bool attr_done = false;
   if (!attr_done) {
@@ -1053,14 +1025,14 @@ int launch_ho3_g(pyn_ctx* c, Ho3Args T) {
   }
   T.runflag = nullptr;
   if (T.nbits) {   // which runs see an imposed DOF: once per Dirichlet set and run length
-    if (L.runflag_stamp != c->bc_stamp || L.runflag_R != R) {
-      if (!L.d_runflag) PYN_HIP(hipMalloc((void**)&L.d_runflag, (size_t)c->n_owned + 8));
-      ho3_runflag_kernel<<<(int)((c->n_owned + 255) / 256), 256, 0, c->stream>>>(T, DIM, NGL - 1, R, c->n_owned, L.d_runflag);
+    if (V.runflag_stamp != c->bc_stamp || V.runflag_R != R) {
+      if (!V.d_runflag) PYN_HIP(hipMalloc((void**)&V.d_runflag, (size_t)c->n_owned + 8));
+      ho3_runflag_kernel<<<(int)((c->n_owned + 255) / 256), 256, 0, c->stream>>>(T, DIM, NGL - 1, R, c->n_owned, V.d_runflag);
       PYN_HIP(hipGetLastError());
-      L.runflag_stamp = c->bc_stamp;
-      L.runflag_R = R;
+      V.runflag_stamp = c->bc_stamp;
+      V.runflag_R = R;
     }
-    T.runflag = L.d_runflag;
+    T.runflag = V.d_runflag;
   }
   // ngl 3: one launch per class of x-lines (parity of y, z), its LDS sized for that class; ngl 2: every line is of one class
   const int ncls = NGL == 3 ? 2 : 1;
@@ -1121,7 +1093,7 @@ template <int DIM, int MAT>
 int launch_ho3_r(pyn_ctx* c, const Ho3Args& T) {
   const char* e = getenv("PYNAMA_HO3_RUN");
   const int r = e ? atoi(e) : 0;
-  if (c->ho3.ngl == 2) {
+  if (c->box.ngl == 2) {
     if (DIM == 3) return launch_ho3<3, 2, MAT, 8>(c, T);
     return launch_ho3<2, 2, MAT, 32>(c, T);
   }
@@ -1140,9 +1112,9 @@ int launch_ho3_r(pyn_ctx* c, const Ho3Args& T) {
 // geometry pre-pass (+ the once-per-mesh check that every cell is a parallelogram / parallelepiped); *ok = the closed forms apply
 int ho3_prepare(pyn_ctx* c, bool* ok) {
   *ok = false;
-  Ho3Lattice& L = c->ho3;
+  Ho3View& L = c->ho3;
   hipStream_t s = c->stream;
-  const int gs = L.dim == 3 ? 10 : 6;
+  const int gs = c->dim == 3 ? 10 : 6;
   if (!L.d_geom) PYN_HIP(hipMalloc((void**)&L.d_geom, (size_t)c->n_elem * gs * sizeof(double)));
   const int ge = (int)((c->n_elem + 255) / 256);
   DevTmp flag;
@@ -1153,7 +1125,7 @@ int ho3_prepare(pyn_ctx* c, bool* ok) {
     d_flag = flag.as<int>();
   }
   // J^-1, detJ of every element (part of the numeric phase: runs inside the timed region of every assembly)
-  if (L.dim == 3)
+  if (c->dim == 3)
     ho3_geom_kernel<3><<<ge, 256, 0, s>>>(c->d_conn, c->d_xyz, c->n_elem, c->nn, c->quad[0].HrsCoo, L.d_geom, d_flag);
   else
     ho3_geom_kernel<2><<<ge, 256, 0, s>>>(c->d_conn, c->d_xyz, c->n_elem, c->nn, c->quad[0].HrsCoo, L.d_geom, d_flag);
@@ -1175,13 +1147,13 @@ int ho3_prepare(pyn_ctx* c, bool* ok) {
 // derivative along reference axis r of the Q1 function of the corner at lattice offsets 2 * bit d (HrsCoo at the first full-rule point)
 int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]) {
   *affine = *diag = false;
-  const Ho3Lattice& L = c->ho3;
-  if (!L.valid || L.ngl != 3 || c->quad[0].ngp < 1 || !c->quad[0].HrsCoo) return PYN_OK;
+  const Ho3View& L = c->ho3;
+  if (!L.valid || c->box.ngl != 3 || c->quad[0].ngp < 1 || !c->quad[0].HrsCoo) return PYN_OK;
   bool ok = false;
   PYN_TRY(ho3_prepare(c, &ok));
   *affine = L.affine == 1;
   *diag = L.diag == 1;
-  const int dim = L.dim, nc = 1 << dim;
+  const int dim = c->dim, nc = 1 << dim;
   double h[3 * 8];
   PYN_HIP(hipMemcpy(h, c->quad[0].HrsCoo, (size_t)dim * nc * sizeof(double), hipMemcpyDeviceToHost));
   for (int r = 0; r < dim; ++r)
@@ -1190,127 +1162,26 @@ int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]) {
 }
 
 void pyn_ho3_release(pyn_ctx* c) {
-  Ho3Lattice& L = c->ho3;
-  (void)hipFree(L.d_P);
+  Ho3View& L = c->ho3;
   (void)hipFree(L.d_geom);
   (void)hipFree(L.d_nbits);
   (void)hipFree(L.d_runflag);
-  L = Ho3Lattice();
+  L = Ho3View();
 }
 
-// Is the connectivity that of a structured mesh of tensor-product cells of order 1 or 2 (ngl 2 / 3: the reference's box mesh,
-// src/domain/dmplex.py:8-21, 42-61, or a rank's slab of one)?  Host, once per pyn_mesh_set; every entry of `conn` is checked against
-// the closed form the kernels use.
-// every element of a structured block against its closed form (one thread per entry of the connectivity)
-struct LocTab {
-  signed char v[27][3];
-};
-__global__ void ho3_conn_verify_kernel(const int32_t* __restrict__ conn, const int32_t* __restrict__ P, LocTab loc, int dim, int nn, int m,
-                                       int64_t ne, int EX, int EY, int NX, int64_t per_layer, int* __restrict__ bad) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= ne * nn) return;
-  const int64_t e = t / nn;
-  const int a = (int)(t - e * nn);
-  const int ex = (int)(e % EX), ey = dim == 3 ? (int)((e / EX) % EY) : 0;
-  const int64_t el = e / per_layer;
-  int64_t id;
-  if (dim == 3)
-    id = (int64_t)P[m * el + loc.v[a][2]] + (int64_t)(m * ey + loc.v[a][1]) * NX + m * ex + loc.v[a][0];
-  else
-    id = (int64_t)P[m * el + loc.v[a][1]] + m * ex + loc.v[a][0];
-  if (conn[t] != id) atomicAdd(bad, 1);
-}
-
-// `at(i)`: entry i of the local connectivity as the host sees it; the shape guessed from O(element rows + layers) entries is checked
-// against all of c->d_conn on the device
-int pyn_ho3_detect(pyn_ctx* c, const ConnAt& at) {
+// The ngl 2 / 3 view of c->box: structured meshes of tensor-product cells of order 1 or 2, whose corners sit where the device code has
+// them spelled out (CB2 / CB3)
+void pyn_ho3_view(pyn_ctx* c) {
   pyn_ho3_release(c);
-  const int dim = c->dim, nn = c->nn;
-  const int ngl = (nn == 9 || nn == 27) ? 3 : 2;
-  if (!((dim == 2 && (nn == 9 || nn == 4)) || (dim == 3 && (nn == 27 || nn == 8))) || c->n_elem < 1 || getenv("PYNAMA_NO_HO3")) return PYN_OK;
-  const int m = ngl - 1;
-  int a_of[27];
-  for (int a = 0; a < nn; ++a) a_of[tens_of(dim, ngl, a)] = a;
-  const int a0 = a_of[0];
-  const int64_t ne = c->n_elem;
-  const int32_t c0 = at(a0);
-  int64_t EX = 1;
-  while (EX < ne && at(EX * nn + a0) == c0 + m * EX) ++EX;
-  if (ne % EX) return PYN_OK;
-  const int64_t NX = m * EX + 1;
-  int64_t EY, EZ = 0, NY = 0, PS, EL;   // EL: element layers along the slow axis
-  if (dim == 3) {
-    EY = 1;
-    while (EY * EX < ne && at(EY * EX * nn + a0) == c0 + m * EY * NX) ++EY;
-    if ((ne / EX) % EY) return PYN_OK;
-    EZ = ne / (EX * EY);
-    NY = m * EY + 1;
-    PS = NX * NY;
-    EL = EZ;
-  } else {
-    EY = ne / EX;
-    PS = NX;
-    EL = EY;
+  const BoxLattice& B = c->box;
+  if (!B.valid || B.ngl > 3 || B.plane() > INT32_MAX / 4 || B.n_own < 1 || getenv("PYNAMA_NO_HO3")) return;
+  const LocalOrder lo(B.dim, B.ngl);
+  for (int cn = 0; cn < (1 << B.dim); ++cn) {
+    int bits = 0;
+    for (int d = 0; d < B.dim; ++d) bits |= (lo.loc_of(cn, d) / (B.ngl - 1)) << d;
+    if (bits != (B.dim == 2 ? CB2[cn] : CB3[cn])) return;
   }
-  const int64_t npl = m * EL + 1;
-  if (PS * npl != c->n_node || PS > INT32_MAX / 4) return PYN_OK;
-  std::vector<int32_t> P((size_t)npl, -1);
-  const int64_t per_layer = ne / EL;
-  const int stride_s = dim == 3 ? ngl * ngl : ngl;     // tensor stride of the slow axis
-  for (int64_t l = 0; l < EL; ++l)
-    for (int j = 0; j < ngl; ++j) {
-      const int32_t base = at(l * per_layer * nn + a_of[j * stride_s]);
-      if (P[m * l + j] >= 0 && P[m * l + j] != base) return PYN_OK;
-      P[m * l + j] = base;
-    }
-  std::vector<int32_t> sorted(P);
-  std::sort(sorted.begin(), sorted.end());
-  for (int64_t j = 0; j < npl; ++j)
-    if (sorted[j] != j * PS) return PYN_OK;
-  if (c->n_owned % PS) return PYN_OK;
-  const int n_own = (int)(c->n_owned / PS);
-  int p0 = -1;
-  for (int64_t j = 0; j < npl; ++j)
-    if (P[j] == 0) p0 = (int)j;
-  if (p0 < 0 || p0 + n_own > npl || n_own < 1) return PYN_OK;
-  for (int j = 0; j < n_own; ++j)
-    if (P[p0 + j] != (int64_t)j * PS) return PYN_OK;
-  Ho3Lattice& L = c->ho3;
-  PYN_HIP(hipMalloc((void**)&L.d_P, npl * sizeof(int32_t)));
-  PYN_HIP(hipMemcpy(L.d_P, P.data(), npl * sizeof(int32_t), hipMemcpyHostToDevice));
-  {   // every element against the guessed shape
-    int* d_bad = nullptr;
-    int bad = 0;
-    PYN_HIP(hipMalloc((void**)&d_bad, sizeof(int)));
-    PYN_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
-    const unsigned grid = (unsigned)((ne * nn + 255) / 256);
-    LocTab lt;
-    for (int a = 0; a < nn; ++a)
-      for (int d = 0; d < dim; ++d) lt.v[a][d] = (signed char)loc_of(dim, ngl, a, d);
-    ho3_conn_verify_kernel<<<grid, 256, 0, c->stream>>>(c->d_conn, L.d_P, lt, dim, nn, m, ne, (int)EX, (int)EY, (int)NX, per_layer, d_bad);
-    PYN_HIP(hipGetLastError());
-    PYN_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    PYN_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_bad);
-    if (bad) {
-      (void)hipFree(L.d_P);
-      L.d_P = nullptr;
-      return PYN_OK;
-    }
-  }
-  L.P = P;
-  L.dim = dim;
-  L.ngl = ngl;
-  L.EX = (int)EX;
-  L.EY = (int)EY;
-  L.EZ = (int)EZ;
-  L.NX = (int)NX;
-  L.NY = (int)NY;
-  L.npl = (int)npl;
-  L.p_own0 = p0;
-  L.n_own = n_own;
-  L.valid = true;
-  return PYN_OK;
+  c->ho3.valid = true;
 }
 
 // Reference matrices of the element from one uploaded rule (pyn_elem_tables_set): the part of every node pair's record (TabRec) that
@@ -1333,9 +1204,10 @@ int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double
     c->ho3_tabs_nn = nn;
   }
   std::vector<double>& R = c->ho3_tabs_host;
+  const LocalOrder lo(dim, ngl);
   for (int a = 0; a < nn; ++a)
     for (int b = 0; b < nn; ++b) {
-      const int ta = tens_of(dim, ngl, a), tb = tens_of(dim, ngl, b);
+      const int ta = lo.tens_of(a), tb = lo.tens_of(b);
       double* rec = R.data() + (size_t)(ta * nn + tb) * ts;
       double* recT = R.data() + (size_t)(tb * nn + ta) * ts;      // Ur is read transposed
       for (int r = 0; r < dim; ++r) {
@@ -1369,7 +1241,7 @@ int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double
     for (int d = 1; d < dim; ++d) norm *= 2.0;
     for (int a = 0; a < nn; ++a)
       for (int b = 0; b < nn; ++b) {
-        const int i = loc_of(dim, ngl, a, 0), j = loc_of(dim, ngl, b, 0);
+        const int i = lo.loc_of(a, 0), j = lo.loc_of(b, 0);
         double mass = 0.0, u0 = 0.0, t00 = 0.0;
         for (int g = 0; g < ngp; ++g) {
           mass += w[g] * H[(size_t)g * nn + a] * H[(size_t)g * nn + b];
@@ -1430,8 +1302,8 @@ int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double
 
 int pyn_ho3_symbolic(pyn_ctx* c, bool* done) {
   *done = false;
-  const Ho3Lattice& L = c->ho3;
-  if (!L.valid || getenv("PYNAMA_NO_HO3_SYMBOLIC")) return PYN_OK;
+  const BoxLattice& L = c->box;
+  if (!c->ho3.valid || getenv("PYNAMA_NO_HO3_SYMBOLIC")) return PYN_OK;
   hipStream_t s = c->stream;
   Ho3Args T;
   fill_lattice_args(c, T);
@@ -1471,9 +1343,9 @@ int pyn_ho3_symbolic(pyn_ctx* c, bool* done) {
 // own, pyn_assemble_lattice.hip).  *handled stays false when the mesh or the tables do not fit (the caller falls back).
 int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled) {
   *handled = false;
-  Ho3Lattice& L = c->ho3;
+  Ho3View& L = c->ho3;
   if (!L.valid || c->ho3_tabs_nn != c->nn || !c->ho3_tabs_ok[0] || c->quad[0].ngp < 1) return PYN_OK;
-  if (L.ngl == 2 && L.dim == 3) return PYN_OK;
+  if (c->box.ngl == 2 && c->dim == 3) return PYN_OK;
   if (form == PYN_FORM_KLE && !c->ho3_tabs_ok[1]) return PYN_OK;
   if (form != PYN_FORM_KLE && form != PYN_FORM_LAPLACE) return PYN_OK;
   hipStream_t s = c->stream;
@@ -1498,7 +1370,7 @@ int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_
     T.Arhs = Krhs;
     T.rhs_clean = c->asm_rhs_clean ? 1 : 0;
     T.rcrow = c->asm_rcrow;
-    if (L.dim == 3)
+    if (c->dim == 3)
       PYN_TRY((launch_ho3_r<3, M_LAP>(c, T)));
     else
       PYN_TRY((launch_ho3_r<2, M_LAP>(c, T)));
@@ -1510,7 +1382,7 @@ int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_
     T.Arhs = Krhs;
     T.rhs_clean = c->asm_rhs_clean ? 1 : 0;
     T.rcrow = c->asm_rcrow;
-    if (L.dim == 3)
+    if (c->dim == 3)
       PYN_TRY((launch_ho3_r<3, M_K>(c, T)));
     else
       PYN_TRY((launch_ho3_r<2, M_K>(c, T)));
@@ -1520,7 +1392,7 @@ int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_
     T.Arhs = nullptr;
     T.rhs_clean = 0;
     T.rcrow = nullptr;
-    if (L.dim == 3)
+    if (c->dim == 3)
       PYN_TRY((launch_ho3_r<3, M_RW>(c, T)));
     else
       PYN_TRY((launch_ho3_r<2, M_RW>(c, T)));
@@ -1534,8 +1406,7 @@ int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_
 int pyn_assemble_ho3_operator(pyn_ctx* c, int rule, int br, int bc, int nterms, const int32_t* terms, const double* coef, double* M,
                               bool* handled) {
   *handled = false;
-  Ho3Lattice& L = c->ho3;
-  if (!L.valid || rule != PYN_Q_NODAL || c->ho3_tabs_nn != c->nn || !c->ho3_tabs_ok[2] || c->quad[0].ngp < 1 || nterms > MAX_TERMS ||
+  if (!c->ho3.valid || rule != PYN_Q_NODAL || c->ho3_tabs_nn != c->nn || !c->ho3_tabs_ok[2] || c->quad[0].ngp < 1 || nterms > MAX_TERMS ||
       getenv("PYNAMA_NO_HO3_OPERATOR"))
     return PYN_OK;
   bool ok = false;
@@ -1553,7 +1424,7 @@ int pyn_assemble_ho3_operator(pyn_ctx* c, int rule, int br, int bc, int nterms, 
     T.t_der[t] = terms[3 * t + 2];
     T.t_coef[t] = coef[t];
   }
-  if (L.dim == 3)
+  if (c->dim == 3)
     PYN_TRY((launch_ho3_r<3, M_OP>(c, T)));
   else
     PYN_TRY((launch_ho3_r<2, M_OP>(c, T)));

@@ -1482,64 +1482,16 @@ __global__ void lattice_symbolic_kernel(LatArgs T, int64_t n_rows, int32_t* __re
 
 }  // namespace
 
-// ---- structured topology: detection (host, once per pyn_mesh_set) and launch -------------------------
-// every element of a structured Q1 block against its closed form (one thread per element; `bad` counts the mismatches)
-__global__ void lattice_conn_verify_kernel(const int32_t* __restrict__ conn, const int32_t* __restrict__ P, int64_t ne, int ex, int ey, int nx,
-                                           int* __restrict__ bad) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= ne) return;
-  const int ix = (int)(e % ex), iy = (int)((e / ex) % ey);
-  const int64_t l = e / ((int64_t)ex * ey);
-  const int32_t lo = P[l] + iy * nx + ix, hi = P[l + 1] + iy * nx + ix;
-  const int4 q0 = *reinterpret_cast<const int4*>(conn + e * 8), q1 = *reinterpret_cast<const int4*>(conn + e * 8 + 4);
-  if (q0.x != lo || q0.y != lo + nx || q0.z != lo + nx + 1 || q0.w != lo + 1 || q1.x != hi || q1.y != hi + 1 || q1.z != hi + nx + 1 ||
-      q1.w != hi + nx)
-    atomicAdd(bad, 1);
-}
-
-// `at(i)`: entry i of the local connectivity (the uploaded host array, or the closed form of pyn_mesh_box); it is asked for O(layers +
-// element rows) entries -- the shape guessed from them is then checked against ALL of c->d_conn on the device
-int pyn_lattice_detect(pyn_ctx* c, const ConnAt& at) {
+// ---- structured topology: the view of 3-D first-order boxes (once per pyn_mesh_set) and launch -------------------------
+// c->box at dim 3, ngl 2 (the detector's plane limit is this view's), + the z-neighbour planes of every plane in id order (zord)
+int pyn_lattice_view(pyn_ctx* c) {
   Lattice& L = c->lat;
-  (void)hipFree(L.d_P);
   (void)hipFree(L.d_zord);
   L = Lattice();
-  if (c->dim != 3 || c->nn != 8 || c->n_elem < 1 || getenv("PYNAMA_NO_LATTICE")) return PYN_OK;
-  const int64_t ne = c->n_elem;
-  const int64_t nx = (int64_t)at(1) - at(0);
-  if (nx < 2 || at(3) != at(0) + 1) return PYN_OK;
-  const int64_t ex = nx - 1;
-  if (ne % ex) return PYN_OK;
-  // rows of elements per layer: the first element row that does not continue the bottom plane of layer 0
-  int64_t ey = 0;
-  const int32_t c0 = at(0);
-  for (int64_t j = 0; j * ex < ne; ++j) {
-    if (at(j * ex * 8) != c0 + j * nx) break;
-    ey = j + 1;
-  }
-  if (ey < 1 || (ne / ex) % ey) return PYN_OK;
-  const int64_t ny = ey + 1, ezl = ne / (ex * ey), npl = ezl + 1, nxny = nx * ny;
-  if (nxny * npl != c->n_node || nxny > INT32_MAX / 2) return PYN_OK;
-  std::vector<int32_t> P((size_t)npl);
-  for (int64_t l = 0; l < ezl; ++l) {
-    const int64_t e0 = l * ex * ey * 8;
-    P[l] = at(e0);
-    if (l + 1 == ezl) P[l + 1] = at(e0 + 4);
-    if (l > 0 && P[l] != at((l - 1) * ex * ey * 8 + 4)) return PYN_OK;
-  }
-  // planes are disjoint blocks of nx*ny ids; the owned ones are consecutive in z and carry ids 0..n_owned-1
-  std::vector<int32_t> sorted(P);
-  std::sort(sorted.begin(), sorted.end());
-  for (int64_t j = 0; j < npl; ++j)
-    if (sorted[j] != j * nxny) return PYN_OK;
-  if (c->n_owned % nxny) return PYN_OK;
-  const int n_own = (int)(c->n_owned / nxny);
-  int p0 = -1;
-  for (int64_t j = 0; j < npl; ++j)
-    if (P[j] == 0) p0 = (int)j;
-  if (p0 < 0 || p0 + n_own > npl) return PYN_OK;
-  for (int j = 0; j < n_own; ++j)
-    if (P[p0 + j] != (int64_t)j * nxny) return PYN_OK;
+  const BoxLattice& B = c->box;
+  if (!B.valid || B.dim != 3 || B.ngl != 2 || getenv("PYNAMA_NO_LATTICE")) return PYN_OK;
+  const std::vector<int32_t>& P = B.P;
+  const int64_t npl = B.npl;
   std::vector<int32_t> zord((size_t)npl);
   for (int64_t j = 0; j < npl; ++j) {
     int dz[3], n = 0;
@@ -1550,41 +1502,9 @@ int pyn_lattice_detect(pyn_ctx* c, const ConnAt& at) {
     for (int i = 0; i < n; ++i) code |= (dz[i] + 1) << (2 + 2 * i);
     zord[j] = code;
   }
-  PYN_HIP(hipMalloc((void**)&L.d_P, npl * sizeof(int32_t)));
   PYN_HIP(hipMalloc((void**)&L.d_zord, npl * sizeof(int32_t)));
-  PYN_HIP(hipMemcpy(L.d_P, P.data(), npl * sizeof(int32_t), hipMemcpyHostToDevice));
   PYN_HIP(hipMemcpy(L.d_zord, zord.data(), npl * sizeof(int32_t), hipMemcpyHostToDevice));
-  {   // every element against the guessed shape
-    int* d_bad = nullptr;
-    int bad = 0;
-    PYN_HIP(hipMalloc((void**)&d_bad, sizeof(int)));
-    PYN_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
-    lattice_conn_verify_kernel<<<(unsigned)((ne + 255) / 256), 256, 0, c->stream>>>(c->d_conn, L.d_P, ne, (int)ex, (int)ey, (int)nx, d_bad);
-    PYN_HIP(hipGetLastError());
-    PYN_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    PYN_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_bad);
-    if (bad) {
-      (void)hipFree(L.d_P);
-      (void)hipFree(L.d_zord);
-      L = Lattice();
-      return PYN_OK;
-    }
-  }
-  L.nx = (int)nx;
-  L.ny = (int)ny;
-  L.npl = (int)npl;
-  L.p_own0 = p0;
-  L.n_own = n_own;
-  // does the numbering have the arithmetic shape lat_plane / lat_zcode assume (one rank, or a rank's z-slab)?
-  L.std_shape = true;
-  for (int64_t j = 0; j < npl && L.std_shape; ++j) {
-    int64_t want;
-    if (j < p0) want = (n_own + j) * nxny;
-    else if (j >= p0 + n_own) want = (n_own + p0 + (j - p0 - n_own)) * nxny;
-    else want = (j - p0) * nxny;
-    L.std_shape = P[j] == want;
-  }
+  L.std_shape = B.slab_order();   // the arithmetic shape lat_plane / lat_zcode assume (one rank, or a rank's z-slab)
   L.valid = true;
   return PYN_OK;
 }
@@ -1615,16 +1535,17 @@ static int launch_lattice(pyn_ctx* c, LatArgs& T, bool affine) {
 // lattice descriptor -> kernel arguments (+ the one-off verification that index arithmetic may replace the loads)
 static int lat_fill_args(pyn_ctx* c, LatArgs& T, double* A, double* Arhs, int* mesh_aff) {
   Lattice& L = c->lat;
+  const BoxLattice& B = c->box;
   T.xyz = c->d_xyz;
   T.rowptr = c->d_rowptr;
   T.bcmask = c->d_bcmask;
-  T.P = L.d_P;
+  T.P = B.d_P;
   T.zord = L.d_zord;
-  T.nx = L.nx;
-  T.ny = L.ny;
-  T.npl = L.npl;
-  T.p_own0 = L.p_own0;
-  T.n_own = L.n_own;
+  T.nx = B.NX;
+  T.ny = B.NY;
+  T.npl = B.npl;
+  T.p_own0 = B.p_own0;
+  T.n_own = B.n_own;
   T.ntx = T.nty = 0;
   T.bz0 = 0;
   T.bzs = 1;
@@ -1972,16 +1893,16 @@ const MfBackend* pyn_mf_q1() {
 // without the sort of pyn_csr_symbolic.  *done = false when the mesh does not qualify.
 int pyn_lattice_symbolic(pyn_ctx* c, bool* done) {
   *done = false;
-  const Lattice& L = c->lat;
-  if (!L.valid || !L.std_shape || getenv("PYNAMA_NO_LATTICE_SYMBOLIC")) return PYN_OK;
+  const BoxLattice& L = c->box;
+  if (!c->lat.valid || !c->lat.std_shape || getenv("PYNAMA_NO_LATTICE_SYMBOLIC")) return PYN_OK;
   LatArgs T;
   T.xyz = c->d_xyz;
   T.rowptr = nullptr;
   T.bcmask = nullptr;
   T.P = L.d_P;
-  T.zord = L.d_zord;
-  T.nx = L.nx;
-  T.ny = L.ny;
+  T.zord = c->lat.d_zord;
+  T.nx = L.NX;
+  T.ny = L.NY;
   T.npl = L.npl;
   T.p_own0 = L.p_own0;
   T.n_own = L.n_own;
@@ -1991,7 +1912,7 @@ int pyn_lattice_symbolic(pyn_ctx* c, bool* done) {
   T.lean = 0;
   T.q = TileArgs();
   T.A = T.Arhs = nullptr;
-  const int64_t sx = 3 * (int64_t)L.nx - 2, sy = 3 * (int64_t)L.ny - 2;
+  const int64_t sx = 3 * (int64_t)L.NX - 2, sy = 3 * (int64_t)L.NY - 2;
   const int64_t nnz = (3 * (int64_t)L.n_own - (L.p_own0 == 0 ? 1 : 0) - (L.p_own0 + L.n_own == L.npl ? 1 : 0)) * sy * sx;
   PYN_CHECK(nnz > 0 && nnz < (int64_t)INT32_MAX, "pattern has %lld entries (int32 CSR limit)", (long long)nnz);
   (void)hipFree(c->d_rowptr);

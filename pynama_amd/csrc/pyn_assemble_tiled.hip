@@ -1279,16 +1279,16 @@ static int ensure_default_plan(pyn_ctx* c, int kind) {
   if (c->lat.valid) {
     // structured topology: node tiles (7x7x7 for the scalar kernel, 3x3x3 for the 3x3-block kernels)
     const int t = kind == 0 ? 7 : 3;
-    const Lattice& L = c->lat;
-    const int64_t nxny = (int64_t)L.nx * L.ny;
+    const BoxLattice& L = c->box;
+    const int64_t nxny = L.plane();
     int64_t pos = 0;
     ptr.push_back(0);
     for (int z0 = 0; z0 < L.n_own; z0 += t)
-      for (int y0 = 0; y0 < L.ny; y0 += t)
-        for (int x0 = 0; x0 < L.nx; x0 += t) {
+      for (int y0 = 0; y0 < L.NY; y0 += t)
+        for (int x0 = 0; x0 < L.NX; x0 += t) {
           for (int z = z0; z < std::min(z0 + t, L.n_own); ++z)
-            for (int y = y0; y < std::min(y0 + t, L.ny); ++y)
-              for (int x = x0; x < std::min(x0 + t, L.nx); ++x) rows[pos++] = (int32_t)(z * nxny + (int64_t)y * L.nx + x);
+            for (int y = y0; y < std::min(y0 + t, L.NY); ++y)
+              for (int x = x0; x < std::min(x0 + t, L.NX); ++x) rows[pos++] = (int32_t)(z * nxny + (int64_t)y * L.NX + x);
           ptr.push_back((int32_t)pos);
         }
   } else {

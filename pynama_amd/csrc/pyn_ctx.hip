@@ -156,8 +156,8 @@ extern "C" int pyn_ctx_destroy(pyn_ctx* c) {
   (void)hipFree(c->d_conn);
   (void)hipFree(c->d_xyz);
   (void)hipFree(c->d_aff);
-  (void)hipFree(c->lat.d_P);
   (void)hipFree(c->lat.d_zord);
+  pyn_box_release(c);
   pyn_ho3_release(c);
   pyn_ho_release(c);
   pyn_ibm_release(c);
@@ -611,9 +611,10 @@ static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
     c->mf_set[k] = false;
   }
   pyn_ibm_release(c);             // ... and so does the immersed-boundary marker set
-  PYN_TRY(pyn_lattice_detect(c, at));
-  PYN_TRY(pyn_ho3_detect(c, at));
-  PYN_TRY(pyn_ho_detect(c, at));
+  PYN_TRY(pyn_box_detect(c, at));   // structured topology: found once, admitted per kernel family
+  PYN_TRY(pyn_lattice_view(c));
+  pyn_ho3_view(c);
+  pyn_ho_view(c);
   // graph + matrices depend on the mesh
   (void)hipFree(c->d_rowptr);
   (void)hipFree(c->d_colidx);
@@ -753,18 +754,12 @@ extern "C" int pyn_mesh_get(pyn_ctx* c, int32_t* conn, double* xyz) {
 
 extern "C" int pyn_mesh_topology(pyn_ctx* c, int* kind, int* nx, int* ny, int* nz) {
   PYN_CHECK(c && c->n_elem > 0, "pyn_mesh_set first");
-  if (c->ho3.valid && (c->ho3.ngl == 3 || c->ho3.dim == 2)) {   // second-order lattice (kind 2) / first-order quadrilaterals (kind 3):
-                                                                // nodes per x-line, x-lines per plane, planes (2-D: ny = x-lines, nz = 1)
-    if (kind) *kind = c->ho3.ngl == 3 ? 2 : 3;
-    if (nx) *nx = c->ho3.NX;
-    if (ny) *ny = c->ho3.dim == 3 ? c->ho3.NY : c->ho3.npl;
-    if (nz) *nz = c->ho3.dim == 3 ? c->ho3.npl : 1;
-    return PYN_OK;
-  }
-  if (kind) *kind = c->lat.valid ? 1 : 0;
-  if (nx) *nx = c->lat.nx;
-  if (ny) *ny = c->lat.ny;
-  if (nz) *nz = c->lat.npl;
+  // nodes per x-line, x-lines per plane, planes (2-D: ny = x-lines, nz = 1)
+  const int k = pyn_lattice_kind(c);
+  if (kind) *kind = k;
+  if (nx) *nx = k ? c->box.NX : 0;
+  if (ny) *ny = k ? c->box.ny() : 0;
+  if (nz) *nz = k ? c->box.nz() : 0;
   return PYN_OK;
 }
 

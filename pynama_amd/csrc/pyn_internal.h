@@ -143,31 +143,44 @@ struct PatchPlan {
   int64_t npe = 0;
 };
 
-// Structured-topology descriptor of a Q1 hex mesh (detected in pyn_mesh_set, verified entry by entry):
-// nodes form nx*ny planes stacked in z; plane j (z order) starts at node id P[j]; element
-// e = ix + (nx-1)*(iy + (ny-1)*l) sits between planes l and l+1.  Owned rows = planes
-// [p_own0, p_own0 + n_own) (ids 0 .. n_owned-1); ghost planes of a rank's slab have ids >= n_owned.
+// The one structured-topology fact of the library: the connectivity is the reference's box mesh (src/domain/dmplex.py:8-21, 42-61) of
+// order ngl >= 2, or a rank's slab of one (pyn_box_detect, pyn_box_lattice.hip: guessed on the host, every entry verified on the device).
+// (ngl - 1) E + 1 nodes per axis numbered lexicographically; the slowest axis (y in 2-D, z in 3-D) is cut into "planes" (x-lines in
+// 2-D) of NX * NY ids whose first node ids are P[j]: id = P[c_slow] + c_y NX + c_x.  Owned rows = planes [p_own0, p_own0 + n_own)
+// (ids 0 .. n_owned-1); the ghost planes of a slab have ids >= n_owned.  Cell e = ex + EX (ey + EY el) sits between planes
+// (ngl - 1) el and (ngl - 1) (el + 1).  Three views admit a mesh to their kernels: Lattice, Ho3View, pyn_ctx::ho_valid.
+struct BoxLattice {
+  bool valid = false;
+  int dim = 0, ngl = 0;
+  int EX = 0, EY = 0, EL = 0;   // local cells along x, y (1 in 2-D), the slow axis
+  int NX = 0, NY = 0;           // nodes per x-line; x-lines per plane (1 in 2-D)
+  int npl = 0, p_own0 = 0, n_own = 0;
+  int32_t* d_P = nullptr;       // [npl]
+  std::vector<int32_t> P;
+  int64_t plane() const { return (int64_t)NX * NY; }
+  // nodes along y and z as pyn_mesh_topology reports them (2-D: the planes are the y axis, nz = 1)
+  int ny() const { return dim == 3 ? NY : npl; }
+  int nz() const { return dim == 3 ? npl : 1; }
+  bool slab_order() const {     // ids follow the slab numbering: owned planes, then the ghost planes below, then those above
+    bool ok = true;
+    for (int j = 0; j < npl && ok; ++j) ok = P[j] == (j < p_own0 ? n_own + j : (j >= p_own0 + n_own ? j : j - p_own0)) * plane();
+    return ok;
+  }
+  bool natural() const { return p_own0 == 0 && n_own == npl && slab_order(); }   // all planes owned: id = lexicographic lattice index
+};
+
+// View of 3-D first-order boxes (pyn_assemble_lattice.hip: Q1 hexahedron tiles, matrix-free Q1 products)
 struct Lattice {
   bool valid = false;
-  int nx = 0, ny = 0, npl = 0, p_own0 = 0, n_own = 0;
-  bool std_shape = false;      // all planes owned, in id order (single rank)
+  bool std_shape = false;      // ids follow the slab numbering: owned planes, ghost planes below, ghost planes above (one rank, or a rank's slab)
   int std_ok = -1;             // closed-form row offsets verified against the graph (-1: not checked yet)
-  int32_t* d_P = nullptr;      // [npl]
   int32_t* d_zord = nullptr;   // [npl]: count | (dz+1) codes of the z-neighbour planes sorted by node id
 };
 
-// Structured topology of a SECOND-ORDER mesh (ngl = 3: 9-node quadrilaterals / 27-node hexahedra in the reference's local order,
-// src/elements/spectral.py:346-431), the order all of the reference's cases run (src/cases/*.yaml: `ngl: 3`).  Nodes sit on the GLL
-// lattice of 2 E + 1 points per axis; the slowest axis (y in 2-D, z in 3-D) is cut into "planes" (x-lines in 2-D) whose first node
-// ids are P[j], so that a rank's slab with its ghost planes fits the same arithmetic: id = P[c_slow] + c_y NX + c_x (3-D).
-struct Ho3Lattice {
+// View of orders ngl 2 and 3 (pyn_assemble_ho3.hip: row-run assembly; ngl 3, the order all of the reference's cases run,
+// src/cases/*.yaml, also has the matrix-free KLE operator of pyn_matfree_ho3.hip) and what its kernels cache per mesh
+struct Ho3View {
   bool valid = false;
-  int dim = 0, ngl = 0;         // ngl 3 (second order) or 2 (first order: the row-run kernels serve 2-D Q1 cells and the operators there)
-  int EX = 0, EY = 0, EZ = 0;   // local elements per axis (2-D: EY = local element rows, EZ = 0)
-  int NX = 0, NY = 0;           // nodes per x-line; x-lines per plane (3-D)
-  int npl = 0, p_own0 = 0, n_own = 0;   // planes of the local mesh, owned ones = [p_own0, p_own0 + n_own) with ids 0 .. n_owned-1
-  int32_t* d_P = nullptr;       // [npl]
-  std::vector<int32_t> P;
   int affine = -1;              // every element a parallelogram / parallelepiped? (-1: not checked yet)
   int diag = 0;                 // ... and axis-aligned (J diagonal): set with `affine`
   double* d_geom = nullptr;     // [n_elem][6 | 10]: J^-1 (row = physical axis) and det J, rewritten by every assembly
@@ -189,17 +202,6 @@ struct Ho3MfBasis {
   int diag = 0;                // every cell's J^-1 is diagonal (axis-aligned boxes)
 };
 
-// Structured box lattice of order ngl >= 4 (pyn_matfree_ho.hip): (ngl - 1) E + 1 nodes per axis numbered lexicographically, the slowest
-// axis cut into planes (x-lines in 2-D) as in Ho3Lattice: id = P[c_slow] + c_y NX + c_x.  Only the matrix-free KLE operator uses it;
-// pyn_mesh_topology reports kind 0 for these meshes.
-struct HoLattice {
-  bool valid = false;
-  int dim = 0, ngl = 0;
-  int EX = 0, EY = 0, EL = 0;   // local cells along x, y (3-D), the slow axis
-  int NX = 0, NY = 0;           // nodes per x-line; x-lines per plane (3-D)
-  int npl = 0, p_own0 = 0, n_own = 0;
-  int32_t* d_P = nullptr;       // [npl]
-};
 constexpr int PYN_HO_MAX_NGL_2D = 12, PYN_HO_MAX_NGL_3D = 8;   // orders the matrix-free kernels are instantiated for
 
 struct SellShape {
@@ -291,9 +293,10 @@ struct pyn_ctx {
   // patch plans of the tiled assemblies (pyn_assemble_tiled.hip): [0] scalar forms, [1] KLE (3x3 blocks)
   PatchPlan plan[2];
   bool plan_unfit[2] = {false, false};  // the automatic plan did not fit this graph (reset by pyn_csr_symbolic)
-  Lattice lat;  // structured topology, if the mesh has one (plan-free assembly kernel)
-  Ho3Lattice ho3;   // ... of a second-order (ngl = 3) mesh (pyn_assemble_ho3.hip)
-  HoLattice ho;     // ... of a box mesh of order ngl >= 4 (pyn_matfree_ho.hip)
+  BoxLattice box;   // structured topology, if the mesh has one, and the views of it that the kernel families admit:
+  Lattice lat;      // 3-D first-order cells (pyn_assemble_lattice.hip)
+  Ho3View ho3;      // ngl 2 and 3 (pyn_assemble_ho3.hip)
+  bool ho_valid = false;        // 4 <= ngl <= pyn_ho_matfree_max_ngl(dim) (pyn_matfree_ho.hip); pyn_mesh_topology says kind 0 for these
   double* d_ho_tab = nullptr;   // its matrix-free KLE operator: the 1-D tables of the order (set by pyn_matfree_set) ...
   double* d_ho_ye = nullptr;    // ... and the per-cell results between the two passes [n_elem][dim][nn]
   // reference matrices of the ngl = 3 element in tensor (lattice) order, from the uploaded tables (pyn_elem_tables_set):
@@ -346,6 +349,12 @@ struct pyn_ctx {
 };
 
 inline int64_t n_local(const pyn_ctx* c) { return c->n_owned + c->n_ghost; }
+// kind of pyn_mesh_topology: 2 second-order lattice, 3 first-order quadrilaterals (both through the row-run view), 1 first-order
+// hexahedra, 0 no view that assembles (general connectivity, or order ngl >= 4)
+inline int pyn_lattice_kind(const pyn_ctx* c) {
+  if (c->ho3.valid && (c->box.ngl == 3 || c->box.dim == 2)) return c->box.ngl == 3 ? 2 : 3;
+  return c->lat.valid ? 1 : 0;
+}
 
 // ---- cross-TU helpers ---------------------------------------------------------------------
 int pyn_ensure_work(pyn_ctx* c, size_t bytes);
@@ -374,7 +383,13 @@ int pyn_bc_elements(pyn_ctx* c);                        // c->d_esel / n_esel fo
 int64_t pyn_mat_blocks(const pyn_ctx* c, const DMat& M);        // blocks stored by the matrix (graph entries, or the compact count)
 // entry i of the local connectivity as the host sees it: the array handed to pyn_mesh_set, or the closed form of pyn_mesh_box
 using ConnAt = std::function<int32_t(int64_t)>;
-int pyn_lattice_detect(pyn_ctx* c, const ConnAt& at);  // pyn_assemble_lattice.hip
+// pyn_box_lattice.hip: c->box from the connectivity; the local node offsets of the box mesh (reference position / flipped in 2-D)
+int pyn_box_detect(pyn_ctx* c, const ConnAt& at);
+void pyn_box_release(pyn_ctx* c);
+void ref_local_lattice(int n, int dim, std::vector<int>& out);
+void mesh_local_lattice(int ngl, int dim, std::vector<int>& loc);
+// the three views of c->box, each next to its kernels (once per pyn_mesh_set, after pyn_box_detect)
+int pyn_lattice_view(pyn_ctx* c);   // pyn_assemble_lattice.hip
 bool pyn_q1_affine_tables_standard(const double* aff);
 int pyn_mesh_all_affine(pyn_ctx* c, int* out);                        // pyn_assemble_tiled.hip
 // collectives behind one switch: RCCL (product) or the shared-memory test transport
@@ -387,13 +402,13 @@ bool pyn_q1_mixed_tables_standard(const double* w, const double* H, const double
 bool pyn_q1_gauss_tables_standard(const double* w, const double* H, const double* Hrs, const double* HrsCoo);   // pyn_assemble_march.hip
 int pyn_assemble_lattice_march(pyn_ctx* c, void* lat_args, int tile);   // general geometry, z-marching (pyn_assemble_march.hip)
 // second-order (ngl = 3) lattices (pyn_assemble_ho3.hip)
-int pyn_ho3_detect(pyn_ctx* c, const ConnAt& at);
+void pyn_ho3_view(pyn_ctx* c);
 void pyn_ho3_release(pyn_ctx* c);
 int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double* H, const double* Hrs);
 int pyn_ho3_symbolic(pyn_ctx* c, bool* done);
 int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]);   // every cell affine / axis-aligned; corner derivatives
 // box lattices of order ngl >= 4 (pyn_matfree_ho.hip)
-int pyn_ho_detect(pyn_ctx* c, const ConnAt& at);
+void pyn_ho_view(pyn_ctx* c);
 void pyn_ho_release(pyn_ctx* c);
 int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
 void pyn_ibm_release(pyn_ctx* c);   // pyn_ibm.hip: the marker set belongs to the mesh

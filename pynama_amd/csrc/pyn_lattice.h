@@ -54,7 +54,7 @@ struct LatTile {
 
 // First node id of z-plane j.  Arithmetic form (std_lat): the owned planes carry the ids 0 .. n_owned-1 in z
 // order, the ghost planes below them follow, then the ghost planes above (the numbering of a rank's z-slab; on one
-// rank simply j*nx*ny).  pyn_lattice_detect verified that the uploaded numbering has this shape.
+// rank simply j*nx*ny).  BoxLattice::slab_order checked that the uploaded numbering has this shape.
 template <bool STD = false>   // STD: the caller has checked T.std_lat (no index loads compiled in)
 __device__ __forceinline__ int lat_plane(const LatArgs& T, int j) {
   if (!STD && !T.std_lat) return T.P[j];

@@ -20,7 +20,7 @@
 // Every owned row is written once, no atomics, no zero fill, bit-identical from run to run.  Cost of the second pass: one write and
 // one read of (ngl / (ngl - 1))^dim vectors.
 // Dirichlet: a SNAPSHOT of the per-DOF mask taken by pyn_matfree_set.  Rank slabs: x carries the ghost tail; planes (3-D) / x-lines
-// (2-D) are numbered through HoLattice::P; every cell of the local mesh touches an owned plane, so all of them are computed.
+// (2-D) are numbered through BoxLattice::P; every cell of the local mesh touches an owned plane, so all of them are computed.
 #include <algorithm>
 #include <cmath>
 
@@ -133,83 +133,6 @@ struct HoTab1D {
     return t;
   }
 };
-
-// Reference position (i, j[, k]) of every local point of an n^dim tensor set in the reference's vertex / edge / face / interior order
-// (src/elements/spectral.py:220-271 in 2-D, :346-431 in 3-D)
-void ref_local_lattice(int n, int dim, std::vector<int>& out) {
-  out.clear();
-  auto push = [&](int i, int j, int k) {
-    out.push_back(i);
-    out.push_back(j);
-    if (dim == 3) out.push_back(k);
-  };
-  if (n == 1) {
-    push(0, 0, 0);
-    return;
-  }
-  const int m = n - 1;
-  if (dim == 2) {
-    const int v[4][2] = {{m, m}, {0, m}, {0, 0}, {m, 0}};
-    for (auto& p : v) push(p[0], p[1], 0);
-    for (int a = 0; a < 4; ++a) {
-      const int* p0 = v[a];
-      const int* p1 = v[(a + 1) % 4];
-      for (int s = 1; s < m; ++s) push(p0[0] + s * (p1[0] - p0[0]) / m, p0[1] + s * (p1[1] - p0[1]) / m, 0);
-    }
-    for (int i = 1; i < m; ++i)
-      for (int j = m - 1; j >= 1; --j) push(i, j, 0);
-    return;
-  }
-  const int v[8][3] = {{0, 0, 0}, {0, m, 0}, {m, m, 0}, {m, 0, 0}, {0, 0, m}, {m, 0, m}, {m, m, m}, {0, m, m}};
-  const int edges[12][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 0}, {4, 5}, {5, 6}, {6, 7}, {7, 4}, {3, 5}, {4, 0}, {1, 7}, {6, 2}};
-  for (auto& p : v) push(p[0], p[1], p[2]);
-  for (auto& e : edges) {
-    const int* p0 = v[e[0]];
-    const int* p1 = v[e[1]];
-    for (int s = 1; s < m; ++s)
-      push(p0[0] + s * (p1[0] - p0[0]) / m, p0[1] + s * (p1[1] - p0[1]) / m, p0[2] + s * (p1[2] - p0[2]) / m);
-  }
-  for (int j = m - 1; j >= 1; --j)
-    for (int i = 1; i < m; ++i) push(i, j, 0);   // face t = -1
-  for (int j = 1; j < m; ++j)
-    for (int i = m - 1; i >= 1; --i) push(i, j, m);   // face t = +1
-  for (int i = m - 1; i >= 1; --i)
-    for (int k = 1; k < m; ++k) push(i, 0, k);   // face s = -1
-  for (int i = 1; i < m; ++i)
-    for (int k = m - 1; k >= 1; --k) push(i, m, k);   // face s = +1
-  for (int k = m - 1; k >= 1; --k)
-    for (int j = m - 1; j >= 1; --j) push(m, j, k);   // face r = +1
-  for (int k = 1; k < m; ++k)
-    for (int j = 1; j < m; ++j) push(0, j, k);   // face r = -1
-  for (int k = m - 1; k >= 1; --k)
-    for (int j = m - 1; j >= 1; --j)
-      for (int i = 1; i < m; ++i) push(i, j, k);
-}
-
-// lattice offset of every local node of the box mesh: the reference position, flipped on both axes in 2-D (dmplex.py: x ~ -r, y ~ -s)
-void mesh_local_lattice(int ngl, int dim, std::vector<int>& loc) {
-  ref_local_lattice(ngl, dim, loc);
-  if (dim == 2)
-    for (int& v : loc) v = ngl - 1 - v;
-}
-
-// every entry of the connectivity against the closed form of the lattice (one thread per entry)
-__global__ void ho_conn_verify_kernel(const int32_t* __restrict__ conn, const int32_t* __restrict__ P, const int32_t* __restrict__ loc, int dim,
-                                      int nn, int m, int64_t ne, int EX, int EY, int NX, int64_t per_layer, int* __restrict__ bad) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= ne * nn) return;
-  const int64_t e = t / nn;
-  const int a = (int)(t - e * nn);
-  const int ex = (int)(e % EX), ey = dim == 3 ? (int)((e / EX) % EY) : 0;
-  const int64_t el = e / per_layer;
-  const int32_t* l = loc + a * dim;
-  int64_t id;
-  if (dim == 3)
-    id = (int64_t)P[m * el + l[2]] + (int64_t)(m * ey + l[1]) * NX + m * ex + l[0];
-  else
-    id = (int64_t)P[m * el + l[1]] + m * ex + l[0];
-  if (conn[t] != id) atomicAdd(bad, 1);
-}
 
 struct HoMfArgs {
   const double* xyz;
@@ -693,7 +616,7 @@ int launch_ho_cells_any(pyn_ctx* c, int dim, int ngl, const HoMfArgs& A, const d
 }
 
 HoMfArgs ho_args(const pyn_ctx* c) {
-  const HoLattice& L = c->ho;
+  const BoxLattice& L = c->box;
   HoMfArgs A;
   A.xyz = c->d_xyz;
   A.P = L.d_P;
@@ -701,12 +624,12 @@ HoMfArgs ho_args(const pyn_ctx* c) {
   A.tab = c->d_ho_tab;
   A.ye = c->d_ho_ye;
   A.NX = L.NX;
-  A.NY = L.dim == 3 ? L.NY : 1;
+  A.NY = L.NY;
   A.npl = L.npl;
   A.p_own0 = L.p_own0;
   A.n_own = L.n_own;
   A.EX = L.EX;
-  A.EY = L.dim == 3 ? L.EY : 1;
+  A.EY = L.EY;
   A.EL = L.EL;
   A.n_cells = (int)c->n_elem;
   A.alpha_d = c->mf_alpha_d;
@@ -744,115 +667,28 @@ extern "C" int pyn_ho_local_lattice(int ngl, int dim, int32_t* loc) {
 
 extern "C" int pyn_mesh_ho_lattice(pyn_ctx* c, int* ngl, int* nx, int* ny, int* nz) {
   PYN_CHECK(c && c->n_elem > 0, "pyn_mesh_set first");
-  const HoLattice& L = c->ho;
-  if (ngl) *ngl = L.valid ? L.ngl : 0;
-  if (nx) *nx = L.valid ? L.NX : 0;
-  if (ny) *ny = L.valid ? (L.dim == 3 ? L.NY : L.npl) : 0;
-  if (nz) *nz = L.valid ? (L.dim == 3 ? L.npl : 1) : 0;
+  const BoxLattice& L = c->box;
+  if (ngl) *ngl = c->ho_valid ? L.ngl : 0;
+  if (nx) *nx = c->ho_valid ? L.NX : 0;
+  if (ny) *ny = c->ho_valid ? L.ny() : 0;
+  if (nz) *nz = c->ho_valid ? L.nz() : 0;
   return PYN_OK;
 }
 
 void pyn_ho_release(pyn_ctx* c) {
-  (void)hipFree(c->ho.d_P);
   (void)hipFree(c->d_ho_tab);
   (void)hipFree(c->d_ho_ye);
   c->d_ho_tab = c->d_ho_ye = nullptr;
-  c->ho = HoLattice();
+  c->ho_valid = false;
 }
 
-// Is the connectivity that of the reference's box mesh at order ngl >= 4 (src/domain/dmplex.py:8-21, 42-61: (ngl - 1) nelem + 1 nodes
-// per axis, numbered lexicographically), or a rank's slab of one?  The shape guessed from O(element rows + layers) entries is checked
-// against all of c->d_conn on the device.  pyn_mesh_topology keeps reporting kind 0 for these meshes: only the matrix-free operator
-// uses the descriptor.
-int pyn_ho_detect(pyn_ctx* c, const ConnAt& at) {
+// The ngl >= 4 view of c->box: the orders the kernels are instantiated for.  pyn_mesh_topology keeps reporting kind 0 for these meshes:
+// only the matrix-free operator uses the view.
+void pyn_ho_view(pyn_ctx* c) {
   pyn_ho_release(c);
-  const int dim = c->dim, nn = c->nn, ngl = c->ngl;
-  if (ngl < 4 || ngl > pyn_ho_matfree_max_ngl(dim) || c->n_elem < 1 || c->n_elem >= INT32_MAX || getenv("PYNAMA_NO_HO_LATTICE")) return PYN_OK;
-  const int m = ngl - 1;
-  std::vector<int> loc;
-  mesh_local_lattice(ngl, dim, loc);
-  std::vector<int> a_of((size_t)nn, -1);   // local node at tensor position i + ngl (j + ngl k)
-  for (int a = 0; a < nn; ++a) {
-    int t = 0;
-    for (int d = dim - 1; d >= 0; --d) t = t * ngl + loc[a * dim + d];
-    a_of[t] = a;
-  }
-  const int a0 = a_of[0];
-  const int64_t ne = c->n_elem;
-  const int32_t c0 = at(a0);
-  int64_t EX = 1;
-  while (EX < ne && at(EX * nn + a0) == c0 + m * EX) ++EX;
-  if (ne % EX) return PYN_OK;
-  const int64_t NX = m * EX + 1;
-  int64_t EY = 1, NY = 1, PS, EL;
-  if (dim == 3) {
-    while (EY * EX < ne && at(EY * EX * nn + a0) == c0 + m * EY * NX) ++EY;
-    if ((ne / EX) % EY) return PYN_OK;
-    EL = ne / (EX * EY);
-    NY = m * EY + 1;
-    PS = NX * NY;
-  } else {
-    EL = ne / EX;
-    PS = NX;
-  }
-  const int64_t npl = m * EL + 1;
-  if (PS * npl != c->n_node || PS > INT32_MAX / 4) return PYN_OK;
-  std::vector<int32_t> P((size_t)npl, -1);
-  const int64_t per_layer = ne / EL;
-  const int stride_s = dim == 3 ? ngl * ngl : ngl;
-  for (int64_t l = 0; l < EL; ++l)
-    for (int j = 0; j < ngl; ++j) {
-      const int32_t base = at(l * per_layer * nn + a_of[j * stride_s]);
-      if (P[m * l + j] >= 0 && P[m * l + j] != base) return PYN_OK;
-      P[m * l + j] = base;
-    }
-  std::vector<int32_t> sorted(P);
-  std::sort(sorted.begin(), sorted.end());
-  for (int64_t j = 0; j < npl; ++j)
-    if (sorted[j] != j * PS) return PYN_OK;
-  if (c->n_owned % PS) return PYN_OK;
-  const int n_own = (int)(c->n_owned / PS);
-  int p0 = -1;
-  for (int64_t j = 0; j < npl; ++j)
-    if (P[j] == 0) p0 = (int)j;
-  if (p0 < 0 || p0 + n_own > npl || n_own < 1) return PYN_OK;
-  for (int j = 0; j < n_own; ++j)
-    if (P[p0 + j] != (int64_t)j * PS) return PYN_OK;
-  HoLattice& L = c->ho;
-  PYN_HIP(hipMalloc((void**)&L.d_P, npl * sizeof(int32_t)));
-  PYN_HIP(hipMemcpy(L.d_P, P.data(), npl * sizeof(int32_t), hipMemcpyHostToDevice));
-  {   // every element against the guessed shape
-    DevTmp d_bad, d_loc;
-    int bad = 0;
-    std::vector<int32_t> loc32(loc.begin(), loc.end());
-    PYN_HIP(d_bad.alloc(sizeof(int)));
-    PYN_HIP(d_loc.alloc(loc32.size() * sizeof(int32_t)));
-    PYN_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), c->stream));
-    PYN_HIP(hipMemcpyAsync(d_loc.p, loc32.data(), loc32.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    const unsigned grid = (unsigned)((ne * nn + 255) / 256);
-    ho_conn_verify_kernel<<<grid, 256, 0, c->stream>>>(c->d_conn, L.d_P, d_loc.as<int32_t>(), dim, nn, m, ne, (int)EX, (int)EY, (int)NX,
-                                                       per_layer, d_bad.as<int>());
-    PYN_HIP(hipGetLastError());
-    PYN_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    PYN_HIP(hipStreamSynchronize(c->stream));
-    if (bad) {
-      (void)hipFree(L.d_P);
-      L.d_P = nullptr;
-      return PYN_OK;
-    }
-  }
-  L.dim = dim;
-  L.ngl = ngl;
-  L.EX = (int)EX;
-  L.EY = (int)EY;
-  L.EL = (int)EL;
-  L.NX = (int)NX;
-  L.NY = (int)NY;
-  L.npl = (int)npl;
-  L.p_own0 = p0;
-  L.n_own = n_own;
-  L.valid = true;
-  return PYN_OK;
+  const BoxLattice& B = c->box;
+  c->ho_valid = B.valid && B.ngl >= 4 && B.ngl <= pyn_ho_matfree_max_ngl(B.dim) && B.plane() <= INT32_MAX / 4 && B.n_own >= 1 &&
+                c->n_elem < INT32_MAX && !getenv("PYNAMA_NO_HO_LATTICE");
 }
 
 // pyn_matfree_set on a mesh of order ngl >= 4: the refusals, the 1-D tables of the order (checked against the uploaded reduced-rule
@@ -864,8 +700,8 @@ static int ho_matfree_set(pyn_ctx* c, int op) {
                                    "(PYN_MATFREE_KLE)", op);
   PYN_CHECK(ngl <= lim, "matrix-free KLE operator: ngl %d is above the limit of %d-D meshes (ngl <= %d; 2-D: %d, 3-D: %d)", ngl, dim, lim,
             PYN_HO_MAX_NGL_2D, PYN_HO_MAX_NGL_3D);
-  PYN_CHECK(c->ho.valid, "matrix-free KLE operator (ngl %d): the connectivity is not that of a structured box lattice numbered "
-                         "lexicographically (imported / renumbered meshes have no matrix-free form)", ngl);
+  PYN_CHECK(c->ho_valid, "matrix-free KLE operator (ngl %d): the connectivity is not that of a structured box lattice numbered "
+                        "lexicographically (imported / renumbered meshes have no matrix-free form)", ngl);
   const int nn = c->nn, nq = ngl - 1;
   int npt = 1;
   for (int d = 0; d < dim; ++d) npt *= nq;
@@ -924,13 +760,13 @@ static int ho_matfree_set(pyn_ctx* c, int op) {
 // y = K x under the mask snapshot of pyn_matfree_set; x carries the ghost tail.  dot: fused p.Ap partials into c->d_part (one per
 // workgroup of the gather pass, *grid_out of them).
 static int ho_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
-  PYN_CHECK(c->ho.valid, "matrix-free operator: not a structured mesh of order ngl >= 4");
+  PYN_CHECK(c->ho_valid, "matrix-free operator: not a structured mesh of order ngl >= 4");
   PYN_CHECK(op == PYN_MATFREE_KLE && c->mf_set[PYN_MATFREE_KLE] && c->d_ho_tab && c->d_ho_ye, "matrix-free KLE operator: pyn_matfree_set first");
-  const HoLattice& L = c->ho;
+  const BoxLattice& L = c->box;
   const HoMfArgs A = ho_args(c);
   const int* flag = dot ? c->d_flag : nullptr;
   PYN_TRY(launch_ho_cells_any(c, L.dim, L.ngl, A, x, flag));
-  const int64_t rows = (int64_t)L.n_own * (L.dim == 3 ? (int64_t)L.NX * L.NY : L.NX);
+  const int64_t rows = L.n_own * L.plane();
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, PYN_MAX_PARTIALS));
   if (grid_out) *grid_out = grid;
   if (L.dim == 3) {

@@ -19,7 +19,7 @@
 // ((E+1)/E per axis with E = T/2 cells per tile).
 // Dirichlet: a SNAPSHOT of the per-DOF mask taken by pyn_matfree_set, read as "imposed columns eliminated, imposed rows identity" --
 // K after Mat.setIndices2One (src/matrices/mat_generator.py:113-118).
-// Rank slabs: x carries the ghost tail; planes (3-D) / x-lines (2-D) are numbered through Ho3Lattice::P as in the assembly.
+// Rank slabs: x carries the ghost tail; planes (3-D) / x-lines (2-D) are numbered through BoxLattice::P as in the assembly.
 #include <algorithm>
 #include <cmath>
 
@@ -409,7 +409,7 @@ __global__ void __launch_bounds__(256) ho3_matfree_kle_kernel(Ho3MfArgs A, const
 template <int DIM, int TX, int TY, int TZ, bool DG, bool DOT>
 int launch_ho3_matfree(pyn_ctx* c, Ho3MfArgs& A, const double* x, double* y, int* grid_out) {
   using MT = Ho3MfTile<DIM, TX, TY, TZ>;
-  const Ho3Lattice& L = c->ho3;
+  const BoxLattice& L = c->box;
   A.ntx = (L.NX + TX - 1) / TX;
   A.nty = DIM == 3 ? (L.NY + TY - 1) / TY : 1;
   A.zb = L.p_own0 & ~1;
@@ -516,7 +516,7 @@ bool split_rule(const double* M, const double* D, const double* S, double (&B)[N
 
 // pyn_matfree_set(PYN_MATFREE_KLE) on a second-order lattice: every cell affine, tables that are tensor products of one full (Gauss 3)
 // and one reduced (Gauss 2) rule; fills c->mf_ho3
-static bool ho3_matfree_mesh(const pyn_ctx* c) { return c->ho3.valid && c->ho3.ngl == 3; }
+static bool ho3_matfree_mesh(const pyn_ctx* c) { return c->ho3.valid && c->box.ngl == 3; }
 
 static int ho3_matfree_set(pyn_ctx* c, int op) {
   PYN_CHECK(ho3_matfree_mesh(c), "matrix-free operator: not a second-order structured mesh");
@@ -528,7 +528,7 @@ static int ho3_matfree_set(pyn_ctx* c, int op) {
   Ho3MfBasis b;
   double hc[3][8] = {};
   PYN_TRY(pyn_ho3_cell_facts(c, &affine, &diag, hc));
-  const int dim = c->ho3.dim;
+  const int dim = c->dim;
   for (int r = 0; r < 3; ++r)
     for (int d = 0; d < 3; ++d) {
       b.C[r][d] = 0.0;
@@ -551,18 +551,18 @@ static int ho3_matfree_set(pyn_ctx* c, int op) {
 static int ho3_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
   PYN_CHECK(ho3_matfree_mesh(c), "matrix-free operator: not a second-order structured mesh");
   PYN_CHECK(op == PYN_MATFREE_KLE && c->mf_set[PYN_MATFREE_KLE], "matrix-free KLE operator: pyn_matfree_set first");
-  const Ho3Lattice& L = c->ho3;
+  const BoxLattice& L = c->box;
   Ho3MfArgs A;
   A.xyz = c->d_xyz;
   A.P = L.d_P;
   A.mask = c->mf_mask[PYN_MATFREE_KLE];
   A.NX = L.NX;
-  A.NY = L.NY;
+  A.NY = L.dim == 3 ? L.NY : 0;
   A.npl = L.npl;
   A.p_own0 = L.p_own0;
   A.n_own = L.n_own;
   A.EX = L.EX;
-  A.EY = L.dim == 3 ? L.EY : 1;
+  A.EY = L.EY;
   A.EL = (L.npl - 1) / 2;
   A.ntx = A.nty = A.zb = 0;
   A.alpha_d = c->mf_alpha_d;
@@ -578,7 +578,7 @@ static int ho3_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool
 }
 
 // 2 or 3 DOFs per node
-static int ho3_matfree_bs(const pyn_ctx* c, int op) { return op == PYN_MATFREE_KLE ? c->ho3.dim : 1; }
+static int ho3_matfree_bs(const pyn_ctx* c, int op) { return op == PYN_MATFREE_KLE ? c->dim : 1; }
 
 const MfBackend* pyn_mf_ho3() {
   static const MfBackend b = {ho3_matfree_mesh, ho3_matfree_set, ho3_matfree_bs, ho3_matfree_spmv, nullptr};

@@ -621,29 +621,12 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
   PYN_CHECK(A.br >= 1 && A.br <= 3, "multigrid: block size %d (1, 2 or 3 DOFs per node)", A.br);
   PYN_CHECK(!A.rhs_compact, "multigrid: a compact imposed-column matrix (pyn_mat_create_rhs) is not a system matrix");
   // the node lattice of level 0 (pyn_mesh_topology's kinds 1, 2 and 3)
-  int dim = 0, nx = 0, ny = 0, nz = 1;
-  std::vector<int32_t> P;
-  if (c->ho3.valid && (c->ho3.ngl == 3 || c->ho3.dim == 2)) {
-    dim = c->ho3.dim;
-    nx = c->ho3.NX;
-    if (dim == 3) {
-      ny = c->ho3.NY;
-      nz = c->ho3.npl;
-    } else {
-      ny = c->ho3.npl;
-    }
-    P = c->ho3.P;
-  } else if (c->lat.valid) {
-    dim = 3;
-    nx = c->lat.nx;
-    ny = c->lat.ny;
-    nz = c->lat.npl;
-    P.resize(nz);
-    PYN_HIP(hipMemcpy(P.data(), c->lat.d_P, nz * sizeof(int32_t), hipMemcpyDeviceToHost));
-  }
+  const BoxLattice& B = c->box;
+  const int dim = pyn_lattice_kind(c) ? B.dim : 0, nx = B.NX, ny = B.ny(), nz = B.nz();
+  const std::vector<int32_t>& P = B.P;
   PYN_CHECK(dim > 0, "multigrid: needs a structured lattice mesh (pyn_mesh_topology kind 1, 2 or 3); this mesh has general connectivity (kind 0)");
-  const int planes = dim == 3 ? nz : ny;
-  const int64_t plane = dim == 3 ? (int64_t)nx * ny : nx;
+  const int planes = B.npl;
+  const int64_t plane = B.plane();
   PYN_CHECK((int64_t)planes * plane == c->n_owned && (int)P.size() == planes, "multigrid: the lattice (%d x %d x %d) does not cover the %lld owned nodes",
             nx, ny, nz, (long long)c->n_owned);
   std::vector<int32_t> invP(planes, -1);

@@ -725,25 +725,9 @@ __global__ void pat_verify_sample_kernel(const int32_t* __restrict__ rowptr, con
 static int lattice_pattern_dictionary(pyn_ctx* c, bool* done) {
   *done = false;
   if (getenv("PYNAMA_NO_LATTICE_PATTERNS")) return PYN_OK;
-  int ngl = 0, dim = 0, NX = 0, NY = 0, NZ = 1;
-  if (c->lat.valid && c->lat.std_shape && c->lat.p_own0 == 0 && c->lat.n_own == c->lat.npl && c->n_ghost == 0) {
-    ngl = 2;
-    dim = 3;
-    NX = c->lat.nx;
-    NY = c->lat.ny;
-    NZ = c->lat.npl;
-  } else if (c->ho3.valid && c->ho3.p_own0 == 0 && c->ho3.n_own == c->ho3.npl && c->n_ghost == 0 && !(c->ho3.ngl == 3 && c->ho3.dim == 3)) {
-    const Ho3Lattice& L = c->ho3;
-    for (int j = 0; j < L.npl; ++j)
-      if (L.P[j] != (int64_t)j * (L.dim == 3 ? L.NX * L.NY : L.NX)) return PYN_OK;
-    ngl = L.ngl;
-    dim = L.dim;
-    NX = L.NX;
-    NY = dim == 3 ? L.NY : L.npl;
-    NZ = dim == 3 ? L.npl : 1;
-  } else {
-    return PYN_OK;
-  }
+  const BoxLattice& B = c->box;
+  if (!(c->lat.valid || c->ho3.valid) || (B.ngl == 3 && B.dim == 3) || c->n_ghost != 0 || !B.natural()) return PYN_OK;
+  const int ngl = B.ngl, dim = B.dim, NX = B.NX, NY = B.ny(), NZ = B.nz();
   const int ncls = ngl == 2 ? 3 : 4;
   const int npat = dim == 3 ? ncls * ncls * ncls : ncls * ncls;
   // offsets of one axis per class
