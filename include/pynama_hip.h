@@ -225,6 +225,8 @@ int pyn_vec_pointwise_mult(pyn_ctx* ctx, int w, int x, int y);
 int pyn_vec_reciprocal(pyn_ctx* ctx, int x);
 int pyn_vec_vtensv(pyn_ctx* ctx, int v, int out);   /* v (x) v, BaseProblem.computeVtensV (base_problem.py:234-252) */
 int pyn_vec_dot(pyn_ctx* ctx, int x, int y, double* out);
+/* A NaN entry makes every norm of this rank NaN, type 3 included (its max keeps NaN, as PETSc's NORM_INFINITY does).  Across ranks
+ * the all-reduce's max decides what a NaN of ONE rank becomes: it may be dropped there. */
 int pyn_vec_norm(pyn_ctx* ctx, int x, int type /*1, 2, 3=inf (PETSc NormType)*/, double* out);
 
 /* ---- explicit Runge-Kutta (TsSolver, pynama_amd/solver/ts_solver.py; pyn_ts.hip) ------------
@@ -283,6 +285,18 @@ int pyn_elem_operator_local(pyn_ctx* ctx, int rule, int br, int bc, int nterms, 
  * y = A x with halo exchange of x over RCCL when nranks > 1 (PETSc MatMult,
  * base_problem.py:481 "Rw*vort + Krhs*vel"). */
 int pyn_spmv(pyn_ctx* ctx, int mat_id, int x_vec, int y_vec);
+/* Which product kernel the context launched last (pyn_spmv, the products inside pyn_solve, ...): a host-side record, for tests and
+ * diagnostics (no counterpart in the reference).  info[8]:
+ *   [0] family: 0 none yet, 1 32-lane block CSR (spmv_kernel), 2 sell_spmv (image, explicit columns), 3 sellp_spmv (image, column
+ *       dictionary), 4 sellb_spmv with explicit columns, 5 sellb_spmv with the dictionary, 6 csrl_spmv, 7 csrlb_spmv, 8 bcsr_spmv
+ *   [1] staging width W of families 6 and 7; lanes per node row G of family 8; block columns BC of families 4 and 5; else 0
+ *   [2] entries per lane and trip U of family 8, else 0
+ *   [3] 1 when the launch carried the fused dot x.Ax
+ *   [4] grid (workgroups)
+ *   [5] patterns of the column dictionary (0: none)
+ *   [6] longest scalar row of the matrix's block shape (0 for family 1)
+ *   [7] product launches of this context so far (a product split around a halo exchange counts 2) */
+int pyn_product_last(pyn_ctx* ctx, int64_t* info);
 /* Matrix-free operators: y = A x WITHOUT an assembled matrix (PETSc analogue: a MATSHELL).  Element matrices are recomputed
  * on the fly (Spectral.getElemKLEMatrices, spectral.py:120-153) and applied per element; needs a structured mesh, errors otherwise:
  *   Q1 hexahedra (pyn_mesh_topology == lattice)            both operators

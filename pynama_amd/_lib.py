@@ -119,6 +119,7 @@ SIGNATURES = {
     "pyn_assemble_operator": [_P, _I, _I, _pi32, _pf64, _I],
     "pyn_elem_operator_local": [_P, _I, _I, _I, _I, _pi32, _pf64, _pf64, _pf64],
     "pyn_spmv": [_P, _I, _I, _I],
+    "pyn_product_last": [_P, _pi64],
     "pyn_matfree_apply": [_P, _I, _I, _I],
     "pyn_matfree_set": [_P, _I, _D, _D],
     "pyn_solve": [_P, _I, _I, _I, C.POINTER(SolveOpts), C.POINTER(SolveInfo)],
@@ -580,6 +581,15 @@ class Context:
 
     def spmv(self, mid, x, y):
         _check(self.lib.pyn_spmv(self.h, mid, x, y))
+
+    def product_last(self):
+        """the most recent product launch of this context: {'family' (0 none, 1 raw, 2 sell, 3 sellp, 4 sellb explicit, 5 sellb
+        dictionary, 6 csrl, 7 csrlb, 8 bcsr), 'param' (W / lanes per node row / BC), 'unroll', 'dot', 'grid', 'npat', 'maxw',
+        'launches' (running count)}"""
+        info = np.zeros(8, np.int64)
+        _check(self.lib.pyn_product_last(self.h, info))
+        keys = ("family", "param", "unroll", "dot", "grid", "npat", "maxw", "launches")
+        return {k: int(v) for k, v in zip(keys, info)}
 
     def mesh_ho_lattice(self):
         """(ngl, nx, ny, nz) when the mesh is a box lattice of order ngl >= 4 that the matrix-free KLE operator accepts

@@ -1175,8 +1175,10 @@ __device__ inline double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// max that keeps a NaN of either operand (fmax drops it): the infinity norm of a vector that holds a NaN is NaN, as PETSc's is
+__device__ inline double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
 __device__ inline double wave_max(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, 64));
   return v;
 }
 
@@ -1192,7 +1194,7 @@ __global__ void __launch_bounds__(256) reduce_kernel(const double* __restrict__ 
     else if (mode == 1)
       acc += fabs(a);
     else
-      acc = fmax(acc, fabs(a));
+      acc = nan_max(acc, fabs(a));
   }
   acc = mode == 2 ? wave_max(acc) : wave_sum(acc);
   int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -1200,7 +1202,7 @@ __global__ void __launch_bounds__(256) reduce_kernel(const double* __restrict__ 
   __syncthreads();
   if (threadIdx.x == 0) {
     double r = sm[0];
-    for (int k = 1; k < 4; ++k) r = mode == 2 ? fmax(r, sm[k]) : r + sm[k];
+    for (int k = 1; k < 4; ++k) r = mode == 2 ? nan_max(r, sm[k]) : r + sm[k];
     part[blockIdx.x] = r;
   }
 }
@@ -1213,14 +1215,14 @@ __global__ void __launch_bounds__(256) finish_kernel(const double* __restrict__ 
     double acc = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += 256) {
       double v = part[s * PYN_MAX_PARTIALS + i];
-      acc = op == 1 ? fmax(acc, v) : acc + v;
+      acc = op == 1 ? nan_max(acc, v) : acc + v;
     }
     acc = op == 1 ? wave_max(acc) : wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
       double r = sm[0];
-      for (int k = 1; k < 4; ++k) r = op == 1 ? fmax(r, sm[k]) : r + sm[k];
+      for (int k = 1; k < 4; ++k) r = op == 1 ? nan_max(r, sm[k]) : r + sm[k];
       out[s] = r;
     }
     __syncthreads();

@@ -315,6 +315,7 @@ struct pyn_ctx {
   int32_t* sell_tab = nullptr;   // [npat][32] relative node offsets
   int sell_npat = 0;
   bool sell_dict_built = false;
+  int64_t prod_last[8] = {0};    // pyn_product_last: the most recent product launch (pyn_product_record)
 
   std::vector<DMat> mats;
   std::vector<DVec> vecs;
@@ -349,6 +350,18 @@ struct pyn_ctx {
 };
 
 inline int64_t n_local(const pyn_ctx* c) { return c->n_owned + c->n_ghost; }
+// host-side record of a product launch for pyn_product_last (slots as documented in include/pynama_hip.h)
+inline void pyn_product_record(pyn_ctx* c, int family, int p1, int p2, bool dot, int grid, int maxw) {
+  int64_t* r = c->prod_last;
+  r[0] = family;
+  r[1] = p1;
+  r[2] = p2;
+  r[3] = dot ? 1 : 0;
+  r[4] = grid;
+  r[5] = c->sell_npat;
+  r[6] = maxw;
+  r[7] += 1;
+}
 // kind of pyn_mesh_topology: 2 second-order lattice, 3 first-order quadrilaterals (both through the row-run view), 1 first-order
 // hexahedra, 0 no view that assembles (general connectivity, or order ngl >= 4)
 inline int pyn_lattice_kind(const pyn_ctx* c) {

@@ -573,6 +573,7 @@ int pyn_spmv_raw(pyn_ctx* c, const DMat& A, const double* x, double* y) {
   int64_t rows = c->n_owned * A.br;
   spmv_kernel<32, false><<<sgrid(rows), 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, A.val, x, y, rows, A.br, A.bc, nullptr, nullptr);
   PYN_HIP(hipGetLastError());
+  pyn_product_record(c, 1, 0, 0, false, sgrid(rows), 0);
   return PYN_OK;
 }
 
@@ -600,6 +601,7 @@ int LinOp::apply_dot(const double* x, double* y, int* grid) const {
   if (mf) return mf->spmv(c, op, x, y, true, grid);
   if (ensured) return pyn_sell_spmv(c, *A, x, y, true, grid);
   spmv_kernel<32, true><<<*grid, 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, A->val, x, y, rows, A->br, A->bc, c->d_flag, c->d_part);
+  pyn_product_record(c, 1, 0, 0, true, *grid, 0);
   return PYN_OK;
 }
 
@@ -690,6 +692,12 @@ extern "C" int pyn_mat_row_scale(pyn_ctx* c, int mat_id, int vec_id) {
   A.touch();
   int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows * 64 + 255) / 256, 8192));
   row_scale_kernel<<<grid, 256, 0, c->stream>>>(c->d_rowptr, A.val, c->vecs[vec_id].d, c->n_owned, A.br, A.bc, sbs == 1 && A.br != 1);
+  return PYN_OK;
+}
+
+extern "C" int pyn_product_last(pyn_ctx* c, int64_t* info) {
+  PYN_CHECK(c && info, "bad arguments");
+  for (int i = 0; i < 8; ++i) info[i] = c->prod_last[i];
   return PYN_OK;
 }
 

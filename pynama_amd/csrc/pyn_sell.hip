@@ -1048,6 +1048,7 @@ int pyn_sell_spmv_range(pyn_ctx* c, const DMat& A, const double* x, double* y, b
 // logical range with the hole [a1, b0) cut out
 int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const double* x, double* y, bool dot, int64_t a0, int64_t a1, int64_t b0,
                          int64_t b1, int poff, int max_grid, hipStream_t st, int* grid_out) {
+  if (const char* mg = getenv("PYNAMA_SPMV_MAX_GRID")) max_grid = std::max(1, std::min(max_grid, atoi(mg)));   // tests: persistent loops turn at small sizes
   const SellShape* S = pyn_sell_shape(c, A);
   PYN_CHECK(S && A.prod_ready, "pyn_sell_ensure first");
   PYN_CHECK(!dot || A.br == A.bc, "fused dot needs a square block shape");
@@ -1142,6 +1143,7 @@ int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const double* x, double* y, 
 #undef BCSR_SQUARE
 #undef BCSR_LAUNCH
     PYN_HIP(hipGetLastError());
+    pyn_product_record(c, 8, 1 << lg, (un == 2 || un == 3 || un == 8) ? un : 4, dot, gridb, S->maxw);
     if (grid_out) *grid_out = gridb;
     return PYN_OK;
   }
@@ -1174,6 +1176,7 @@ int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const double* x, double* y, 
     else CSRLB_LAUNCH(50, false);
 #undef CSRLB_LAUNCH
     PYN_HIP(hipGetLastError());
+    pyn_product_record(c, 7, W, 0, dot, gridc, S->maxw);
     if (grid_out) *grid_out = gridc;
     return PYN_OK;
   }
@@ -1205,6 +1208,7 @@ int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const double* x, double* y, 
     else CSRL_LAUNCH(32, false);
 #undef CSRL_LAUNCH
     PYN_HIP(hipGetLastError());
+    pyn_product_record(c, 6, W, 0, dot, gridc, S->maxw);
     if (grid_out) *grid_out = gridc;
     return PYN_OK;
   }
@@ -1232,6 +1236,10 @@ int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const double* x, double* y, 
     PYN_TRY(launch_block<6>(c, *S, A, x, y, dot, grid, s0, s1, poff, hb, hl, st));
   }
   PYN_HIP(hipGetLastError());
+  if (A.br == 1 && A.bc == 1)
+    pyn_product_record(c, c->sell_npat > 0 ? 3 : 2, 0, 0, dot, grid, S->maxw);
+  else
+    pyn_product_record(c, c->sell_npat > 0 ? 5 : 4, A.bc, 0, dot, grid, S->maxw);
   if (grid_out) *grid_out = grid;
   return PYN_OK;
 }

@@ -551,14 +551,17 @@ def test_closed_form_pattern_dictionary(lib, nelem, ngl):
             ctx.vec_set(vd, xd)
             ctx.spmv(A, v1, w1)
             ctx.spmv(K, vd, wd)
+            yd = ctx.vec_get(wd, dim)                           # K xd (the solve below overwrites wd with its iterate)
             info = ctx.solve(K, vd, wd, fixed_iters=3)          # the solver's product kernels (image / LDS-staged runs)
-            res[mode] = (ctx.vec_get(w1, 1), ctx.vec_get(wd, dim), info.rnorm)
+            res[mode] = (ctx.vec_get(w1, 1), ctx.vec_get(wd, dim), info.rnorm, yd)
             if mode == "closed":
                 SA, SK = mat_to_scipy(ctx, A, 1, 1), mat_to_scipy(ctx, K, dim, dim)
                 assert rel_err(res[mode][0], SA @ x1) < 1e-13
+                assert rel_err(yd, SK @ xd) < 1e-13
             ctx.close()
         finally:
             os.environ.pop("PYNAMA_NO_LATTICE_PATTERNS", None)
     assert rel_err(res["closed"][0], res["hash"][0]) < 1e-14
     assert rel_err(res["closed"][1], res["hash"][1]) < 1e-13
+    assert rel_err(res["closed"][3], res["hash"][3]) < 1e-13
     assert abs(res["closed"][2] - res["hash"][2]) <= 1e-12 * abs(res["hash"][2])
