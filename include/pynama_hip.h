@@ -138,8 +138,8 @@ int pyn_mesh_get(pyn_ctx* ctx, int32_t* conn, double* xyz);
  * plane and planes (2-D: nz = 1) and the atomics-free row-run kernels assemble them (pyn_assemble_ho3.hip). */
 int pyn_mesh_topology(pyn_ctx* ctx, int* kind, int* nx, int* ny, int* nz);
 /* Box meshes of order ngl >= 4 (the reference's box mesh, (ngl-1) nelem + 1 nodes per axis numbered lexicographically, or a rank's
- * slab of one) stay kind 0 above: the assemblies, the direct solves and multigrid treat them as general meshes.  They are recognised
- * all the same (every entry of the connectivity is checked) for the matrix-free KLE operator; this query reports it: *ngl = the order
+ * slab of one) stay kind 0 above: the assemblies and the direct solves treat them as general meshes.  They are recognised all the
+ * same (every entry of the connectivity is checked) for the matrix-free KLE operator and for multigrid; this query reports it: *ngl = the order
  * (0: not such a lattice, or an order above pyn_ho_matfree_max_ngl(dim)), nx, ny, nz as for kind 2. */
 int pyn_mesh_ho_lattice(pyn_ctx* ctx, int* ngl, int* nx, int* ny, int* nz);
 /* Host-side pieces of that operator (no device needed).  pyn_ho_matfree_max_ngl: the largest order with a kernel (2-D: 12, 3-D: 8).
@@ -379,7 +379,14 @@ int pyn_solve_direct_band(pyn_ctx* ctx, int mat_id, int b_vec, int x_vec, int64_
  * Chebyshev of degree smooth_degree with Jacobi scaling on [esteig_min, esteig_max] x lambda, lambda estimating lambda_max(D^-1 A)
  * from esteig_its seeded CG steps; the same polynomial before and after the coarse correction (symmetric V-cycle), decoupled rows
  * z = r / a_ii.  Coarsest level: dense LU (at most pyn_direct_max_rows() rows).  The hierarchy is cached in the matrix until its
- * values change; pyn_solve builds it with the last options (the defaults when there are none).  A zero field takes its default. */
+ * values change; pyn_solve builds it with the last options (the defaults when there are none).  A zero field takes its default.
+ * Box lattices of order ngl >= 4 (pyn_mesh_ho_lattice reports ngl > 0; kind 0, one rank) are accepted as well.  Their first step
+ * needs no even cell count: level 1 is the Q1 lattice of the same cells, E + 1 nodes per axis, coarse node I at fine node (ngl-1) I,
+ * and every later level halves as above.  P0 is, per component, the tensor product over the axes of the 1-D rule: fine node i of
+ * cell e takes (1 - xi_i) / 2 of coarse node e and (1 + xi_i) / 2 of e + 1, xi the Lobatto(ngl) nodes of pyn_ho_tables_1d (a cell
+ * vertex: its one coincident coarse node, weight 1), masked by the decoupled DOFs as P is.  Level 1 = P0^T A P0 in the same stencil
+ * format, found through 3^dim b products with the assembled matrix per build.  With matfree = PYN_MATFREE_KLE, CG and level 0 of the
+ * V-cycle multiply with the ngl >= 4 shell.  Any other kind 0 mesh is refused ("general connectivity"). */
 #define PYN_MG_MAX_LEVELS 16
 typedef struct pyn_mg_opts {
   int max_levels;        /* -pc_mg_levels: levels including the matrix itself (default PYN_MG_MAX_LEVELS) */

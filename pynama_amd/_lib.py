@@ -642,7 +642,8 @@ class Context:
         return info
 
     def mg_setup(self, mid, max_levels=0, smooth_degree=0, coarse_max_rows=0, esteig_its=0, esteig_min=0.0, esteig_max=0.0):
-        """geometric multigrid hierarchy of the matrix (PC_MG); rebuilt only when the options or the values changed.  0 = default"""
+        """geometric multigrid hierarchy of the matrix (PC_MG; lattice meshes of kinds 1, 2, 3 and box lattices of order ngl >= 4);
+        rebuilt only when the options or the values changed.  0 = default"""
         o = MgOpts(max_levels, smooth_degree, coarse_max_rows, esteig_its, esteig_min, esteig_max)
         _check(self.lib.pyn_mg_setup(self.h, mid, C.byref(o)))
 

@@ -16,6 +16,9 @@
 //            seeded CG (Lanczos) steps per level; the same polynomial before and after the coarse correction, zero start, so that the
 //            V-cycle is symmetric; decoupled rows take z = r / a_ii exactly.
 //   coarsest the dense LU of pyn_direct.hip on a dense image of the coarsest stencil.
+//   ngl >= 4 box lattices (pyn_ctx::ho_valid; pyn_mesh_topology kind 0) take one other first step: level 1 is the Q1 lattice of the same
+//            cells (coarse node I = fine node (ngl - 1) I, any cell count), P0 interpolates linearly at the GLL nodes, and
+//            S1 = P0^T A P0 is probed through 3^d b assembled products (mg_ho_probe); the mg_ho kernels are the 0 <-> 1 transfers.
 // Level 0 is multiplied by whatever the caller supplies (the assembled product or the matrix-free shell); levels >= 1 by the
 // stencil kernels below, with the Chebyshev step fused into the product, the residual into the restriction and the prolongation
 // into the add.  Everything is FP64.
@@ -97,12 +100,13 @@ __global__ void mg_decouple0_kernel(const int32_t* __restrict__ rowptr, const in
 }
 
 // coarse DOF decoupled <=> its coincident fine DOF is; its diagonal is that fine diagonal
-__global__ void mg_coarse_dec_kernel(Grid f, Grid cg, int b, const uint8_t* __restrict__ dec_f, const double* __restrict__ diag_f,
+// (coarse node I = fine node m I: m = 2 between h-levels, ngl - 1 below a high-order level 0)
+__global__ void mg_coarse_dec_kernel(Grid f, Grid cg, int b, int m, const uint8_t* __restrict__ dec_f, const double* __restrict__ diag_f,
                                      uint8_t* __restrict__ dec_c, double* __restrict__ diag_c) {
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < cg.nodes(); t += (int64_t)gridDim.x * blockDim.x) {
     int x, y, z;
     cg.lex(t, x, y, z);
-    const int64_t I = cg.id(x, y, z), i = f.id(2 * x, 2 * y, 2 * z);
+    const int64_t I = cg.id(x, y, z), i = f.id(m * x, m * y, m * z);
     for (int p = 0; p < b; ++p) {
       dec_c[I * b + p] = dec_f[i * b + p];
       diag_c[I * b + p] = diag_f[i * b + p];
@@ -410,6 +414,130 @@ __global__ void __launch_bounds__(256) mg_prolong_kernel(Grid f, Grid cg, const 
   }
 }
 
+// ---- level 0 of order ngl >= 4: transfers between the GLL node lattice (M = ngl - 1 intervals per cell) and the Q1 lattice of the
+// same cells.  1-D rule: fine node x = M e + i of cell e takes (1 - xi_i) / 2 of coarse node e and (1 + xi_i) / 2 of e + 1, i.e. the
+// hat of coarse node X at fine node M X + t is hat[M + t], |t| < M, with hat[M + i] = (1 - xi_i) / 2 and hat[i] = (1 + xi_i) / 2
+// (2 M + 1 doubles, copied to LDS by every workgroup; hat[0] = hat[2 M] = 0 are never used: a cell vertex has one parent).
+
+// One axis of r_c = P0^T (r - A z), P0 a tensor product: out[ou][X][il] = sum_{|t| < M} hat[M + t] in[ou][M X + t][il], a thread per
+// output node with its B components, the 2 M - 1 terms in ascending t.  FIRST (the x axis): `in` is r - Az at the level-0 node ids,
+// decoupled fine DOFs left out.  LAST: decoupled coarse DOFs give 0.  No atomics: the same bits every time.
+template <int B, int D, int M, bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) mg_ho_restrict_kernel(Grid f, const double* __restrict__ hatg, const double* __restrict__ in,
+                                                             const double* __restrict__ Az, const uint8_t* __restrict__ dec_f,
+                                                             const uint8_t* __restrict__ dec_c, double* __restrict__ out, int64_t ni,
+                                                             int n, int N, int64_t total) {
+  __shared__ double hat[2 * M + 1];
+  if (threadIdx.x < 2 * M + 1) hat[threadIdx.x] = hatg[threadIdx.x];
+  __syncthreads();
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t il = t % ni, q = t / ni;
+    const int X = (int)(q % N);
+    const int64_t ou = q / N;
+    double acc[B] = {};
+#pragma unroll
+    for (int dt = -(M - 1); dt <= M - 1; ++dt) {
+      const int a = M * X + dt;
+      if (a < 0 || a >= n) continue;
+      const double w = hat[M + dt];
+      if (FIRST) {   // ni == 1: ou = y + ny z
+        const int64_t i = f.id(a, (int)(ou % f.ny), (int)(ou / f.ny));
+#pragma unroll
+        for (int p = 0; p < B; ++p)
+          if (!dec_f[i * B + p]) acc[p] = fma(w, Az ? in[i * B + p] - Az[i * B + p] : in[i * B + p], acc[p]);
+      } else {
+        const double* v = in + ((ou * n + a) * ni + il) * B;
+#pragma unroll
+        for (int p = 0; p < B; ++p) acc[p] = fma(w, v[p], acc[p]);
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < B; ++p) out[t * B + p] = (LAST && dec_c[t * B + p]) ? 0.0 : acc[p];
+  }
+}
+
+// z_f += P0 e_c: one thread per fine node, its (up to 2^d) coarse parents, masked like mg_prolong_kernel
+template <int B, int D, int M>
+__global__ void __launch_bounds__(256) mg_ho_prolong_kernel(Grid f, Grid cg, const double* __restrict__ hatg, const double* __restrict__ ec,
+                                                            const uint8_t* __restrict__ dec_f, const uint8_t* __restrict__ dec_c,
+                                                            double* __restrict__ zf) {
+  __shared__ double hat[2 * M + 1];
+  if (threadIdx.x < 2 * M + 1) hat[threadIdx.x] = hatg[threadIdx.x];
+  __syncthreads();
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < f.nodes(); t += (int64_t)gridDim.x * blockDim.x) {
+    int c[3];
+    f.lex(t, c[0], c[1], c[2]);
+    const int64_t i = f.id(c[0], c[1], c[2]);
+    const int nc[3] = {cg.nx, cg.ny, cg.nz};
+    int p0[3], np[3];        // first parent and parent count per axis
+    double w[3][2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      p0[a] = 0;
+      np[a] = 1;
+      w[a][0] = 1.0;
+      w[a][1] = 0.0;
+      if (a >= D) continue;
+      const int e = min(c[a] / M, nc[a] - 2), k = c[a] - e * M;   // cell and local node 0 .. M (M: the far end of the last cell)
+      p0[a] = k == M ? e + 1 : e;
+      if (k != 0 && k != M) {
+        np[a] = 2;
+        w[a][0] = hat[M + k];
+        w[a][1] = hat[k];
+      }
+    }
+    double acc[B] = {};
+#pragma unroll
+    for (int cz = 0; cz < (D == 3 ? 2 : 1); ++cz)
+#pragma unroll
+      for (int cy = 0; cy < 2; ++cy)
+#pragma unroll
+        for (int cx = 0; cx < 2; ++cx) {
+          if (cx >= np[0] || cy >= np[1] || cz >= np[2]) continue;
+          const int64_t J = cg.id(p0[0] + cx, p0[1] + cy, p0[2] + cz);
+          const double ww = w[0][cx] * w[1][cy] * w[2][cz];
+#pragma unroll
+          for (int p = 0; p < B; ++p)
+            if (!dec_c[J * B + p]) acc[p] = fma(ww, ec[J * B + p], acc[p]);
+        }
+#pragma unroll
+    for (int p = 0; p < B; ++p)
+      if (!dec_f[i * B + p]) zf[i * B + p] += acc[p];
+  }
+}
+
+// probing S1 = P0^T A P0 through the product: the unit vectors of one colour (coarse index mod 3 per axis) and component q ...
+__global__ void mg_ho_seed_kernel(Grid cg, int b, int colour, int q, double* __restrict__ ec) {
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < cg.nodes(); t += (int64_t)gridDim.x * blockDim.x) {
+    int x, y, z;
+    cg.lex(t, x, y, z);
+    const bool on = x % 3 == colour % 3 && y % 3 == (colour / 3) % 3 && (cg.dim == 2 || z % 3 == colour / 9);
+    for (int p = 0; p < b; ++p) ec[cg.id(x, y, z) * b + p] = (on && p == q) ? 1.0 : 0.0;
+  }
+}
+
+// ... and column q of the one stencil block of every coarse row that points at a node of that colour (S zeroed before: blocks that
+// point outside the lattice stay zero); decoupled coarse rows are the coincident fine diagonal
+__global__ void mg_ho_probe_store_kernel(Grid cg, int b, int colour, int q, const double* __restrict__ rc, const uint8_t* __restrict__ dec_c,
+                                         const double* __restrict__ diag_c, double* __restrict__ S) {
+  const int nst = cg.dim == 3 ? 27 : 9;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < cg.nodes(); t += (int64_t)gridDim.x * blockDim.x) {
+    int x, y, z;
+    cg.lex(t, x, y, z);
+    const int col[3] = {colour % 3, (colour / 3) % 3, colour / 9}, c[3] = {x, y, z};
+    int o[3] = {0, 0, 0};
+    for (int a = 0; a < cg.dim; ++a) {
+      const int d = (col[a] - c[a] % 3 + 3) % 3;
+      o[a] = d == 2 ? -1 : d;
+    }
+    if (!cg.in(x + o[0], y + o[1], z + o[2])) continue;
+    const int k = (o[0] + 1) + 3 * (o[1] + 1) + (cg.dim == 3 ? 9 * (o[2] + 1) : 0);
+    const int64_t I = cg.id(x, y, z);
+    for (int p = 0; p < b; ++p)
+      S[((I * nst + k) * b + p) * b + q] = dec_c[I * b + p] ? ((k == nst / 2 && p == q) ? diag_c[I * b + p] : 0.0) : rc[I * b + p];
+  }
+}
+
 // ---- eigenvalue estimate (CG with Jacobi, Lanczos coefficients) ------------------------------------------------------------
 __global__ void __launch_bounds__(256) mg_dot_kernel(const double* __restrict__ x, const double* __restrict__ y, int64_t n, double* __restrict__ part) {
   __shared__ double sm[4];
@@ -489,7 +617,15 @@ struct MgHier {
   int64_t lu_n = 0;
   double setup_ms = 0.0;
   int builds = 0;
+  // level 0 of order ngl >= 4 (ho_m = ngl - 1 > 0): level 1 is the Q1 lattice of the same cells, the 0 <-> 1 transfers are the
+  // mg_ho kernels; 0: every step halves (kinds 1, 2, 3)
+  int ho_m = 0;
+  double* ho_hat = nullptr;                    // [2 ho_m + 1] 1-D weights
+  double* ho_tmp[2] = {nullptr, nullptr};      // stages of the axis-by-axis restriction
   void free_levels() {
+    for (void* p : {(void*)ho_hat, (void*)ho_tmp[0], (void*)ho_tmp[1]}) (void)hipFree(p);
+    ho_hat = ho_tmp[0] = ho_tmp[1] = nullptr;
+    ho_m = 0;
     for (auto& l : L) {
       for (void* p : {(void*)l.P, (void*)l.invP, (void*)l.S, (void*)l.dinv, (void*)l.diag, (void*)l.dec, (void*)l.b, (void*)l.z[0],
                       (void*)l.z[1], (void*)l.d})
@@ -548,6 +684,59 @@ static Grid grid_of(const MgHier& H, int l) {
       else { constexpr int B_ = 3, D_ = 3; CALL; }                          \
     }                                                                       \
   } while (0)
+
+// the same with the order of a high-order level 0: M_ = ngl - 1 (the orders of pyn_ho_matfree_max_ngl)
+#define PYN_MG_HO_CASE(B, D, M, CALL) case M: PYN_MG_DISPATCH_D(B, D, M, CALL); break;
+#define PYN_MG_DISPATCH_D(B, D, M, CALL)                                    \
+  do {                                                                      \
+    constexpr int M_ = M;                                                   \
+    if ((B) == 1) { constexpr int B_ = 1, D_ = D; CALL; }                   \
+    else if ((B) == 2) { constexpr int B_ = 2, D_ = D; CALL; }              \
+    else { constexpr int B_ = 3, D_ = D; CALL; }                            \
+  } while (0)
+#define PYN_MG_HO_DISPATCH(B, D, M, CALL)                                   \
+  do {                                                                      \
+    static_assert(PYN_HO_MAX_NGL_2D == 12 && PYN_HO_MAX_NGL_3D == 8, "orders of the transfer kernels"); \
+    if ((D) == 2) switch (M) {                                              \
+        PYN_MG_HO_CASE(B, 2, 3, CALL) PYN_MG_HO_CASE(B, 2, 4, CALL) PYN_MG_HO_CASE(B, 2, 5, CALL) PYN_MG_HO_CASE(B, 2, 6, CALL) \
+        PYN_MG_HO_CASE(B, 2, 7, CALL) PYN_MG_HO_CASE(B, 2, 8, CALL) PYN_MG_HO_CASE(B, 2, 9, CALL) PYN_MG_HO_CASE(B, 2, 10, CALL) \
+        PYN_MG_HO_CASE(B, 2, 11, CALL)                                      \
+      }                                                                     \
+    else switch (M) {                                                       \
+        PYN_MG_HO_CASE(B, 3, 3, CALL) PYN_MG_HO_CASE(B, 3, 4, CALL) PYN_MG_HO_CASE(B, 3, 5, CALL) PYN_MG_HO_CASE(B, 3, 6, CALL) \
+        PYN_MG_HO_CASE(B, 3, 7, CALL)                                       \
+      }                                                                     \
+  } while (0)
+
+// r_c = P0^T (in - Az) (Az null: P0^T in), axis by axis: x into ho_tmp[0], y into rc (2-D) or ho_tmp[1], z into rc
+static int mg_ho_restrict(pyn_ctx* c, MgHier& H, const double* in, const double* Az, double* rc) {
+  const MgLevel &F = H.L[0], &C = H.L[1];
+  const Grid gf = grid_of(H, 0);
+  hipStream_t s = c->stream;
+  const int b = H.b, dim = H.dim, m = H.ho_m;
+  const int64_t t0 = (int64_t)C.nx * F.ny * F.nz, t1 = (int64_t)C.nx * C.ny * F.nz, t2 = (int64_t)C.nx * C.ny * C.nz;
+  PYN_MG_HO_DISPATCH(b, dim, m, (mg_ho_restrict_kernel<B_, D_, M_, true, false><<<grid_for(t0), 256, 0, s>>>(
+                                    gf, H.ho_hat, in, Az, F.dec, nullptr, H.ho_tmp[0], 1, F.nx, C.nx, t0)));
+  if (dim == 2) {
+    PYN_MG_HO_DISPATCH(b, dim, m, (mg_ho_restrict_kernel<B_, D_, M_, false, true><<<grid_for(t1), 256, 0, s>>>(
+                                      gf, H.ho_hat, H.ho_tmp[0], nullptr, nullptr, C.dec, rc, C.nx, F.ny, C.ny, t1)));
+  } else {
+    PYN_MG_HO_DISPATCH(b, dim, m, (mg_ho_restrict_kernel<B_, D_, M_, false, false><<<grid_for(t1), 256, 0, s>>>(
+                                      gf, H.ho_hat, H.ho_tmp[0], nullptr, nullptr, nullptr, H.ho_tmp[1], C.nx, F.ny, C.ny, t1)));
+    PYN_MG_HO_DISPATCH(b, dim, m, (mg_ho_restrict_kernel<B_, D_, M_, false, true><<<grid_for(t2), 256, 0, s>>>(
+                                      gf, H.ho_hat, H.ho_tmp[1], nullptr, nullptr, C.dec, rc, (int64_t)C.nx * C.ny, F.nz, C.nz, t2)));
+  }
+  return PYN_OK;
+}
+
+// z_f += P0 e_c
+static int mg_ho_prolong(pyn_ctx* c, MgHier& H, const double* ec, double* zf) {
+  const MgLevel &F = H.L[0], &C = H.L[1];
+  const Grid gf = grid_of(H, 0), gc = grid_of(H, 1);
+  PYN_MG_HO_DISPATCH(H.b, H.dim, H.ho_m, (mg_ho_prolong_kernel<B_, D_, M_><<<grid_for(F.nn), 256, 0, c->stream>>>(gf, gc, H.ho_hat, ec, F.dec,
+                                                                                                                 C.dec, zf)));
+  return PYN_OK;
+}
 
 // the level-0 product of the set-up: the assembled matrix, through the image the CG loop uses
 static int mg_assembled_product(pyn_ctx* c, DMat& A, const double* x, double* y) {
@@ -614,15 +803,42 @@ static int mg_estimate(pyn_ctx* c, DMat& A, MgHier& H, int l, double* lam) {
   return PYN_OK;
 }
 
+// S1 = P0^T A P0 of a high-order level 0, probed through the assembled product: a fine row reaches the nodes of its own cells, so
+// coarse nodes couple at +-1 per axis and the unit vectors of one colour (index mod 3 per axis) and one component do not overlap.
+// 3^dim b products per build; every kernel of the chain has a fixed summation order, so two builds give the same bits.
+static int mg_ho_probe(pyn_ctx* c, DMat& A, MgHier& H) {
+  MgLevel &F = H.L[0], &C = H.L[1];
+  hipStream_t s = c->stream;
+  const int b = H.b, nst = H.dim == 3 ? 27 : 9;
+  const Grid gc = grid_of(H, 1);
+  const size_t nf = (size_t)F.nn * b * sizeof(double);
+  double *v = F.z[0], *y = F.d, *ec = C.z[0], *rc = C.b;   // free until the first cycle
+  LinOp op;
+  PYN_TRY(op.init(c, A, PYN_MATFREE_OFF));
+  PYN_HIP(hipMemsetAsync(C.S, 0, (size_t)C.nn * nst * b * b * sizeof(double), s));
+  for (int colour = 0; colour < nst; ++colour)
+    for (int q = 0; q < b; ++q) {
+      mg_ho_seed_kernel<<<grid_for(C.nn), 256, 0, s>>>(gc, b, colour, q, ec);
+      PYN_HIP(hipMemsetAsync(v, 0, nf, s));
+      PYN_TRY(mg_ho_prolong(c, H, ec, v));
+      PYN_TRY(op.apply(v, y));
+      PYN_TRY(mg_ho_restrict(c, H, y, nullptr, rc));
+      mg_ho_probe_store_kernel<<<grid_for(C.nn), 256, 0, s>>>(gc, b, colour, q, rc, C.dec, C.diag, C.S);
+    }
+  PYN_HIP(hipGetLastError());
+  return PYN_OK;
+}
+
 static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
   PYN_CHECK(c->nranks == 1 && c->n_ghost == 0, "multigrid: the preconditioner runs on one rank without ghost nodes (%d ranks, %lld ghosts)",
             c->nranks, (long long)c->n_ghost);
   PYN_CHECK(A.br == A.bc, "multigrid: the matrix must have square blocks (%d x %d)", A.br, A.bc);
   PYN_CHECK(A.br >= 1 && A.br <= 3, "multigrid: block size %d (1, 2 or 3 DOFs per node)", A.br);
   PYN_CHECK(!A.rhs_compact, "multigrid: a compact imposed-column matrix (pyn_mat_create_rhs) is not a system matrix");
-  // the node lattice of level 0 (pyn_mesh_topology's kinds 1, 2 and 3)
+  // the node lattice of level 0: pyn_mesh_topology's kinds 1, 2 and 3, or a box lattice of order ngl >= 4 (kind 0, pyn_ctx::ho_valid)
   const BoxLattice& B = c->box;
-  const int dim = pyn_lattice_kind(c) ? B.dim : 0, nx = B.NX, ny = B.ny(), nz = B.nz();
+  const int ho_m = (!pyn_lattice_kind(c) && c->ho_valid) ? B.ngl - 1 : 0;
+  const int dim = (pyn_lattice_kind(c) || ho_m) ? B.dim : 0, nx = B.NX, ny = B.ny(), nz = B.nz();
   const std::vector<int32_t>& P = B.P;
   PYN_CHECK(dim > 0, "multigrid: needs a structured lattice mesh (pyn_mesh_topology kind 1, 2 or 3); this mesh has general connectivity (kind 0)");
   const int planes = B.npl;
@@ -644,10 +860,11 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
   auto rows = [&](int l) { return (int64_t)dims[l][0] * dims[l][1] * dims[l][2] * b; };
   while (nlev < std::min(o.max_levels, PYN_MG_MAX_LEVELS) && rows(nlev - 1) > o.coarse_max_rows) {
     const int* d = dims[nlev - 1];
+    const int m = (nlev == 1 && ho_m) ? ho_m : 2;   // order ngl >= 4: the first step goes to the Q1 lattice of the same cells, whatever their count
     bool even = true;
-    for (int a = 0; a < dim; ++a) even = even && d[a] > 1 && (d[a] - 1) % 2 == 0;
+    for (int a = 0; a < dim; ++a) even = even && d[a] > 1 && (d[a] - 1) % m == 0;
     if (!even) break;
-    for (int a = 0; a < 3; ++a) dims[nlev][a] = a < dim ? (d[a] - 1) / 2 + 1 : 1;
+    for (int a = 0; a < 3; ++a) dims[nlev][a] = a < dim ? (d[a] - 1) / m + 1 : 1;
     ++nlev;
   }
   PYN_CHECK(nlev >= 2, "multigrid: fewer than 2 levels possible (lattice %d x %d x %d nodes, %lld rows; coarse_max_rows %d, max_levels %d: "
@@ -666,7 +883,20 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
   H.dim = dim;
   H.b = b;
   H.nlev = nlev;
+  H.ho_m = ho_m;
   hipStream_t s = c->stream;
+  if (ho_m) {   // the 1-D weights from the library's own Lobatto nodes; the stage buffers of the restriction
+    std::vector<double> xi(ho_m + 1), hat(2 * ho_m + 1);
+    PYN_TRY(pyn_ho_tables_1d(ho_m + 1, xi.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    for (int i = 0; i <= ho_m; ++i) {
+      hat[ho_m + i] = 0.5 * (1.0 - xi[i]);
+      hat[i] = 0.5 * (1.0 + xi[i]);
+    }
+    PYN_HIP(hipMalloc((void**)&H.ho_hat, hat.size() * sizeof(double)));
+    PYN_HIP(hipMemcpy(H.ho_hat, hat.data(), hat.size() * sizeof(double), hipMemcpyHostToDevice));
+    PYN_HIP(hipMalloc((void**)&H.ho_tmp[0], (size_t)dims[1][0] * ny * nz * b * sizeof(double)));
+    if (dim == 3) PYN_HIP(hipMalloc((void**)&H.ho_tmp[1], (size_t)dims[1][0] * dims[1][1] * nz * b * sizeof(double)));
+  }
   for (int l = 0; l < nlev; ++l) {
     MgLevel& L = H.L[l];
     L.nx = dims[l][0];
@@ -705,8 +935,10 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
   for (int l = 1; l < nlev; ++l) {
     MgLevel &F = H.L[l - 1], &C = H.L[l];
     const Grid gf = grid_of(H, l - 1), gc = grid_of(H, l);
-    mg_coarse_dec_kernel<<<grid_for(C.nn), 256, 0, s>>>(gf, gc, b, F.dec, F.diag, C.dec, C.diag);
-    if (l == 1)
+    mg_coarse_dec_kernel<<<grid_for(C.nn), 256, 0, s>>>(gf, gc, b, (l == 1 && ho_m) ? ho_m : 2, F.dec, F.diag, C.dec, C.diag);
+    if (l == 1 && ho_m)
+      PYN_TRY(mg_ho_probe(c, A, H));
+    else if (l == 1)
       PYN_MG_DISPATCH(b, dim, (mg_galerkin0_kernel<B_, D_><<<(int)std::min<int64_t>(C.nn, 1 << 20), 64, 0, s>>>(
                                   gf, gc, c->d_rowptr, c->d_colidx, A.val, F.dec, C.dec, C.diag, C.S, dbad.as<int>())));
     else
@@ -814,10 +1046,16 @@ int pyn_mg_vcycle(pyn_ctx* c, DMat& A, const double* r, double* z, const LinOp& 
   const Grid g = grid_of(H, 0), gc = grid_of(H, 1);
   MgLevel& C = H.L[1];
   PYN_TRY(prod0.apply(z, Az));
-  PYN_MG_DISPATCH(b, dim, (mg_restrict_kernel<B_, D_><<<grid_for(C.nn), 256, 0, s>>>(g, gc, nullptr, r, nullptr, Az, L.dec, C.dec, C.b)));
+  if (H.ho_m)
+    PYN_TRY(mg_ho_restrict(c, H, r, Az, C.b));
+  else
+    PYN_MG_DISPATCH(b, dim, (mg_restrict_kernel<B_, D_><<<grid_for(C.nn), 256, 0, s>>>(g, gc, nullptr, r, nullptr, Az, L.dec, C.dec, C.b)));
   double* ec = nullptr;
   PYN_TRY(vcycle_level(c, H, 1, &ec));
-  PYN_MG_DISPATCH(b, dim, (mg_prolong_kernel<B_, D_><<<grid_for(L.nn), 256, 0, s>>>(g, gc, ec, L.dec, C.dec, z)));
+  if (H.ho_m)
+    PYN_TRY(mg_ho_prolong(c, H, ec, z));
+  else
+    PYN_MG_DISPATCH(b, dim, (mg_prolong_kernel<B_, D_><<<grid_for(L.nn), 256, 0, s>>>(g, gc, ec, L.dec, C.dec, z)));
   for (int j = 0; j < k; ++j) {   // post-smoothing
     cheb_coef(H, L.lam, j, &rho, &c1, &c2);
     PYN_TRY(prod0.apply(z, Az));

@@ -44,7 +44,8 @@ substitute above runs; a zero pivot raises.
 coarsest level; one rank, lattice meshes).  Options: ``-pc_mg_levels`` (most levels, the matrix included), ``-mg_levels_ksp_max_it``
 (Chebyshev degree, default 2), ``-pynama_mg_coarse_max_rows`` (coarsening stops at this many rows, default 4096).  The hierarchy is
 cached in the matrix until its values change.  ``gmres`` or ``preonly`` with ``mg`` is refused in ``setUp``.  With a matrix-free tag
-CG multiplies with the shell at level 0 as with Jacobi.
+CG multiplies with the shell at level 0 as with Jacobi.  Box meshes of order ngl >= 4 are lattice meshes here too (their level 1 is
+the Q1 lattice of the same cells), with or without ``-pynama_mat_free_ho``.
 """
 import logging
 
