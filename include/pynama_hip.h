@@ -287,16 +287,27 @@ int pyn_elem_operator_local(pyn_ctx* ctx, int rule, int br, int bc, int nterms, 
 int pyn_spmv(pyn_ctx* ctx, int mat_id, int x_vec, int y_vec);
 /* Which product kernel the context launched last (pyn_spmv, the products inside pyn_solve, ...): a host-side record, for tests and
  * diagnostics (no counterpart in the reference).  info[8]:
- *   [0] family: 0 none yet, 1 32-lane block CSR (spmv_kernel), 2 sell_spmv (image, explicit columns), 3 sellp_spmv (image, column
- *       dictionary), 4 sellb_spmv with explicit columns, 5 sellb_spmv with the dictionary, 6 csrl_spmv, 7 csrlb_spmv, 8 bcsr_spmv
- *   [1] staging width W of families 6 and 7; lanes per node row G of family 8; block columns BC of families 4 and 5; else 0
- *   [2] entries per lane and trip U of family 8, else 0
+ *   [0] family, the library's ProductKind: 0 PK_NONE none yet, 1 PK_RAW 32-lane block CSR (spmv_kernel), 2 PK_SELL sell_spmv (image,
+ *       explicit columns), 3 PK_SELLP sellp_spmv (image, column dictionary), 4 PK_SELLB_X sellb_spmv with explicit columns,
+ *       5 PK_SELLB_D sellb_spmv with the dictionary, 6 PK_CSRL csrl_spmv, 7 PK_CSRLB csrlb_spmv, 8 PK_BCSR bcsr_spmv
+ *   [1] staging width W of PK_CSRL and PK_CSRLB; lanes per node row G of PK_BCSR; block columns BC of PK_SELLB_X / _D; else 0
+ *   [2] entries per lane and trip U of PK_BCSR, else 0
  *   [3] 1 when the launch carried the fused dot x.Ax
  *   [4] grid (workgroups)
  *   [5] patterns of the column dictionary (0: none)
- *   [6] longest scalar row of the matrix's block shape (0 for family 1)
+ *   [6] longest scalar row of the matrix's block shape (0 for PK_RAW)
  *   [7] product launches of this context so far (a product split around a halo exchange counts 2) */
 int pyn_product_last(pyn_ctx* ctx, int64_t* info);
+/* The rule that picks the family (host only: no context, no device) -- what the library applies whenever it resolves the product of a
+ * matrix, i.e. on every pyn_spmv and once per solve.  Facts: block shape br x bc; npat patterns of the node-level column dictionary
+ * (0: none); maxw longest scalar row; nnzb, n_owned of the graph; rhs_compact (pyn_mat_create_rhs); solver 1: the product will be
+ * repeated (Krylov loop), 0: a one-off pyn_spmv; image 1: the matrix holds a SELL image of its current values.  Knobs, as the
+ * environment variables of the same names would set them: sell_image, block_sell, no_csrlb, no_sell 0 / 1; bcsr_min_avg, bcsr_lanes,
+ * bcsr_unroll negative = not set.  Out: *kind as [0] above (0: no product for this block shape), *W of PK_CSRL / PK_CSRLB, *lanes and
+ * *unroll of PK_BCSR, 0 where they do not apply. */
+int pyn_product_choose(int br, int bc, int npat, int maxw, int64_t nnzb, int64_t n_owned, int rhs_compact, int solver, int image,
+                       int sell_image, int block_sell, int no_csrlb, int no_sell, double bcsr_min_avg, int bcsr_lanes, int bcsr_unroll,
+                       int* kind, int* W, int* lanes, int* unroll);
 /* Matrix-free operators: y = A x WITHOUT an assembled matrix (PETSc analogue: a MATSHELL).  Element matrices are recomputed
  * on the fly (Spectral.getElemKLEMatrices, spectral.py:120-153) and applied per element; needs a structured mesh, errors otherwise:
  *   Q1 hexahedra (pyn_mesh_topology == lattice)            both operators

@@ -120,6 +120,7 @@ SIGNATURES = {
     "pyn_elem_operator_local": [_P, _I, _I, _I, _I, _pi32, _pf64, _pf64, _pf64],
     "pyn_spmv": [_P, _I, _I, _I],
     "pyn_product_last": [_P, _pi64],
+    "pyn_product_choose": [_I] * 4 + [_L, _L] + [_I] * 7 + [_D, _I, _I] + [C.POINTER(_I)] * 4,
     "pyn_matfree_apply": [_P, _I, _I, _I],
     "pyn_matfree_set": [_P, _I, _D, _D],
     "pyn_solve": [_P, _I, _I, _I, C.POINTER(SolveOpts), C.POINTER(SolveInfo)],
@@ -213,6 +214,18 @@ def ho_local_lattice(ngl, dim):
     loc = np.zeros((int(ngl) ** int(dim), int(dim)), np.int32)
     _check(load_library().pyn_ho_local_lattice(int(ngl), int(dim), loc))
     return loc
+
+
+def product_choose(br, bc, npat, maxw, nnzb, n_owned, rhs_compact=False, solver=False, image=False, sell_image=False,
+                   block_sell=False, no_csrlb=False, no_sell=False, bcsr_min_avg=None, bcsr_lanes=None, bcsr_unroll=None):
+    """The product kernel the library would resolve for a matrix with these facts under these knobs (no device needed; None = knob
+    not set): (kind, W, lanes, unroll), kind as slot 0 of Context.product_last()."""
+    out = [_I(0) for _ in range(4)]
+    _check(load_library().pyn_product_choose(
+        int(br), int(bc), int(npat), int(maxw), int(nnzb), int(n_owned), int(rhs_compact), int(solver), int(image), int(sell_image),
+        int(block_sell), int(no_csrlb), int(no_sell), -1.0 if bcsr_min_avg is None else float(bcsr_min_avg),
+        -1 if bcsr_lanes is None else int(bcsr_lanes), -1 if bcsr_unroll is None else int(bcsr_unroll), *(C.byref(o) for o in out)))
+    return tuple(o.value for o in out)
 
 
 class _stdout_to_stderr:

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -76,15 +77,24 @@ struct QuadTab {
   bool const_grad = false;   // Hrs and HrsCoo identical at every point and to each other (affine simplex)
 };
 
+// How one assembled matrix is multiplied: the kernel family (the codes pyn_product_last reports) and what its launches need beyond the
+// matrix.  Filled by pyn_sell_ensure (pyn_sell.hip), the one place that chooses and the one reader of the product knobs.
+enum ProductKind { PK_NONE = 0, PK_RAW = 1, PK_SELL = 2, PK_SELLP = 3, PK_SELLB_X = 4, PK_SELLB_D = 5, PK_CSRL = 6, PK_CSRLB = 7, PK_BCSR = 8 };
+struct ProductPlan {
+  ProductKind kind = PK_NONE;
+  int W = 0;                  // PK_CSRL (27 / 32), PK_CSRLB (18 / 32 / 50): staging width the kernel is instantiated for
+  int lg = 0, unroll = 0;     // PK_BCSR: log2(lanes per node row), entries per lane and trip
+  size_t lds = 0;             // dynamic LDS bytes of a launch
+  int wg_cap = -1;            // most workgroups of a persistent launch (256 per CU x workgroups per CU); -1: the kernel's occupancy
+  int max_grid = INT32_MAX;   // PYNAMA_SPMV_MAX_GRID
+};
+
 struct DMat {
   int br = 0, bc = 0;
   double* val = nullptr;  // [nnzb*br*bc], layout in pynama_hip.h
-  double* sell_val = nullptr;  // SELL-64 image of `val` (scalar matrices, solver side)
+  double* sell_val = nullptr;  // SELL-64 image of `val` (the PK_SELL* kinds); it outlives a plan: a one-off block-CSR product keeps it
   bool sell_valid = false;     // the image holds the current values
-  bool prod_ready = false;     // pyn_sell_ensure has chosen the product kernel for the current values (image / CSR values)
-  bool csr_product = false;    // scalar dictionary-mode matrix: the product reads `val` directly (csrl_spmv_kernel), there is no image (decided in pyn_sell_ensure)
-  bool csrlb_product = false;  // 2x2-block dictionary-mode matrix: lane per scalar row over LDS-staged runs of the block-CSR values (csrlb_spmv_kernel), no image
-  bool bcsr_product = false;   // block matrix / long scalar rows: the product reads the block-CSR values directly (bcsr_spmv_kernel), no image either
+  ProductPlan plan;            // how the current values are multiplied (pyn_sell_ensure); PK_NONE: not resolved yet
   double* dinv = nullptr;      // 1 / diagonal per scalar row (Jacobi), written by the lattice assemblies in their store
   bool dinv_valid = false;     // phase, else extracted once per matrix version (pyn_dinv_ensure)
   double* lu = nullptr;        // dense LU factors of small systems (pyn_direct.hip), [n][n] row-major, multipliers in place
@@ -112,7 +122,8 @@ struct DMat {
   int32_t* c_cptr = nullptr;   // [c_nr + 1] first block of every stored row
   bool live = false;
   void touch() {               // the values are about to change
-    sell_valid = prod_ready = dinv_valid = lu_valid = band_valid = mg_valid = false;
+    sell_valid = dinv_valid = lu_valid = band_valid = mg_valid = false;
+    plan = ProductPlan();
     rhs_clean = -2;
   }
   void release_lu() {
@@ -351,7 +362,7 @@ struct pyn_ctx {
 
 inline int64_t n_local(const pyn_ctx* c) { return c->n_owned + c->n_ghost; }
 // host-side record of a product launch for pyn_product_last (slots as documented in include/pynama_hip.h)
-inline void pyn_product_record(pyn_ctx* c, int family, int p1, int p2, bool dot, int grid, int maxw) {
+inline void pyn_product_record(pyn_ctx* c, ProductKind family, int p1, int p2, bool dot, int grid, int maxw) {
   int64_t* r = c->prod_last;
   r[0] = family;
   r[1] = p1;
@@ -376,18 +387,23 @@ int pyn_halo_exchange_on(pyn_ctx* c, double* x, int bs, hipStream_t st);
 int pyn_check_mat(pyn_ctx* c, int id, const char* what);
 int pyn_check_vec(pyn_ctx* c, int id, const char* what);
 int pyn_reduce_host(pyn_ctx* c, int nslots, int nblocks, int op, double* out);  // partials -> host, allreduced
-int pyn_spmv_raw(pyn_ctx* c, const DMat& A, const double* x, double* y);        // no halo exchange
 int pyn_extract_diag_inv(pyn_ctx* c, const DMat& A, double* dinv, bool invert);
 int pyn_dinv_ensure(pyn_ctx* c, DMat& A);   // A.dinv valid for the current values (one diag_kernel per matrix version at most)
-int pyn_sell_ensure(pyn_ctx* c, DMat& A, bool solver = true);   // solver: the product will be repeated (Krylov loop), not a one-off pyn_spmv
-bool pyn_sell_supported(const DMat& A);
-int pyn_sell_spmv(pyn_ctx* c, const DMat& A, const double* x, double* y, bool dot, int* grid_out);
+// assembled products (pyn_sell.hip).  pyn_sell_ensure resolves A.plan for the current values -- solver: the product will be repeated
+// (Krylov loop), not a one-off pyn_spmv -- and the launches follow a plan: y = A x over the slices [a0, a1) U [b0, b1), a1 <= b0, in ONE
+// launch on stream `st` (the kernels walk the logical range with the hole [a1, b0) cut out), the fused dot partials in
+// d_part[poff .. poff + grid).  No halo exchange.
+int pyn_sell_ensure(pyn_ctx* c, DMat& A, bool solver = true);
+int pyn_sell_spmv(pyn_ctx* c, const DMat& A, const ProductPlan& P, const double* x, double* y, bool dot, int* grid_out);
+int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const ProductPlan& P, const double* x, double* y, bool dot, int64_t a0, int64_t a1,
+                         int64_t b0, int64_t b1, int poff, int max_grid, hipStream_t st, int* grid_out);
+inline const ProductPlan PYN_RAW_PLAN{PK_RAW};   // 32 lanes per scalar row from the block-CSR values: needs no pyn_sell_ensure
+inline int pyn_raw_grid(int64_t rows) { return (int)std::max<int64_t>(1, std::min<int64_t>((rows * 32 + 255) / 256, PYN_MAX_PARTIALS)); }
+inline int pyn_spmv_raw(pyn_ctx* c, const DMat& A, const double* x, double* y) {
+  return pyn_sell_spmv(c, A, PYN_RAW_PLAN, x, y, false, nullptr);
+}
 void pyn_sell_drop_structure(pyn_ctx* c);
 const SellShape* pyn_sell_shape(pyn_ctx* c, const DMat& A);
-int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const double* x, double* y, bool dot, int64_t a0, int64_t a1, int64_t b0,
-                         int64_t b1, int poff, int max_grid, hipStream_t st, int* grid_out);
-int pyn_sell_spmv_range(pyn_ctx* c, const DMat& A, const double* x, double* y, bool dot, int64_t s0, int64_t s1, int poff,
-                        int max_grid, hipStream_t st, int* grid_out);
 // compact imposed-column matrices (pyn_rhs.hip)
 int pyn_rhs_ensure(pyn_ctx* c, DMat& M, bool relayout = false);   // row selection + storage (values zeroed when laid out); relayout: for the CURRENT Dirichlet set
 void pyn_rhs_release(DMat& M);
@@ -444,15 +460,17 @@ const MfBackend* pyn_mf_ho();
 const MfBackend* pyn_mf_q1();
 inline const MfBackend* pyn_matfree_backend(const pyn_ctx* c) { return pyn_mf_ho3()->owns(c) ? pyn_mf_ho3() : pyn_mf_ho()->owns(c) ? pyn_mf_ho() : pyn_mf_q1(); }
 
-// "apply A" of one solve (pyn_krylov.hip): the matrix-free shell, the product chosen by pyn_sell_ensure, or 32-lane block CSR -- resolved
-// once by init, which is also the only reader of PYNAMA_NO_SELL.  No halo exchange; products run on c->stream.
+// "apply A" of one solve (pyn_krylov.hip): the matrix-free shell or the matrix's product plan, resolved once by init.  No halo
+// exchange; products run on c->stream.
+// IF_READY reads no knob: it launches from the plan an earlier resolve stored, that resolve's grid clamp and workgroup cap included
+// (the exit check of a matrix-free solve: the plan of the last pyn_spmv, else the raw product).
 struct LinOp {
-  enum Ensure { SOLVER, ONCE, IF_READY };   // pyn_sell_ensure for a repeated product / for a one-off pyn_spmv / not at all: A.prod_ready decides
+  enum Ensure { SOLVER, ONCE, IF_READY };   // pyn_sell_ensure for a repeated product / for a one-off pyn_spmv / not at all: the stored plan
   pyn_ctx* c = nullptr;
   DMat* A = nullptr;
   const MfBackend* mf = nullptr;   // the shell's backend (matfree != PYN_MATFREE_OFF)
   int op = PYN_MATFREE_OFF;
-  bool ensured = false;            // multiply through pyn_sell_spmv
+  const ProductPlan* plan = nullptr;   // without a shell: A's plan (IF_READY and none stored: the raw product)
   const SellShape* S = nullptr;
   int init(pyn_ctx* c, DMat& A, int matfree, Ensure e = SOLVER);
   int apply(const double* x, double* y) const;

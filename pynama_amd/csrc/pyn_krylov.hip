@@ -1,4 +1,4 @@
-// SpMV and Krylov solve (HOT LOOP 2).
+// Krylov solve (HOT LOOP 2); the products it applies are in pyn_sell.hip.
 //
 // Reference: FreeSlip.solveKLE (src/cases/base_problem.py:479-481): rhs = Rw*vort + Krhs*vel
 // (two MatMult + axpy) then KSP solve; KspSolver.createSolver (src/solver/ksp_solver.py:9-19)
@@ -19,43 +19,6 @@ namespace {
 enum { S_RZ = 0, S_PAP = 1, S_RZNEW = 2, S_ALPHA = 3, S_BETA = 4, S_RNORM = 5, S_RNORM0 = 6, S_TTOL = 7, S_DLIM = 8, S_ATOL = 9,
        S_TMP0 = 16, S_TMP1 = 17 };
 enum { F_DONE = 0, F_ITERS = 1, F_REASON = 2 };
-
-// ---- SpMV: LPR lanes per scalar row, rows of one node are contiguous in `val` -----------------
-// y[(i,p)] = sum_k sum_q val[(rowptr[i]*br + p*len + k)*bc + q] * x[colidx[rowptr[i]+k]*bc + q]
-template <int LPR, bool DOT>
-__global__ void __launch_bounds__(256) spmv_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
-                                                   const double* __restrict__ val, const double* __restrict__ x,
-                                                   double* __restrict__ y, int64_t n_rows, int br, int bc,
-                                                   const int* __restrict__ flag, double* __restrict__ part) {
-  if (flag && flag[F_DONE]) return;
-  const int lane = threadIdx.x % LPR;
-  const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LPR;
-  const int64_t ngrp = (int64_t)gridDim.x * blockDim.x / LPR;
-  double dot = 0.0;
-  for (int64_t r = grp; r < n_rows; r += ngrp) {
-    int64_t i = r / br;
-    int p = (int)(r - i * br);
-    int lo = rowptr[i];
-    int len = rowptr[i + 1] - lo;
-    const double* v = val + ((int64_t)lo * br + (int64_t)p * len) * bc;
-    const int n = len * bc;
-    double acc = 0.0;
-    if (bc == 1) {
-      for (int idx = lane; idx < n; idx += LPR) acc += v[idx] * x[colidx[lo + idx]];
-    } else {
-      for (int idx = lane; idx < n; idx += LPR) {
-        int k = idx / bc, q = idx - k * bc;
-        acc += v[idx] * x[(int64_t)colidx[lo + k] * bc + q];
-      }
-    }
-    for (int o = LPR / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, LPR);
-    if (lane == 0) {
-      y[r] = acc;
-      if (DOT) dot += acc * x[r];
-    }
-  }
-  if (DOT) block_partial(dot, part);
-}
 
 __global__ void diag_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                             const double* __restrict__ val, int64_t n_nodes, int br, int invert, double* __restrict__ d) {
@@ -559,7 +522,6 @@ __global__ void wmul_kernel(double* __restrict__ w, const double* __restrict__ d
 }
 
 inline int vgrid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 511) / 512, PYN_MAX_PARTIALS)); }
-inline int sgrid(int64_t rows) { return (int)std::max<int64_t>(1, std::min<int64_t>((rows * 32 + 255) / 256, PYN_MAX_PARTIALS)); }   // spmv_kernel<32>
 
 int dev_dot(pyn_ctx* c, const double* x, const double* y, int64_t n, double* out) {
   int g = vgrid(n);
@@ -569,40 +531,26 @@ int dev_dot(pyn_ctx* c, const double* x, const double* y, int64_t n, double* out
 
 }  // namespace
 
-int pyn_spmv_raw(pyn_ctx* c, const DMat& A, const double* x, double* y) {
-  int64_t rows = c->n_owned * A.br;
-  spmv_kernel<32, false><<<sgrid(rows), 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, A.val, x, y, rows, A.br, A.bc, nullptr, nullptr);
-  PYN_HIP(hipGetLastError());
-  pyn_product_record(c, 1, 0, 0, false, sgrid(rows), 0);
-  return PYN_OK;
-}
-
 // ---- LinOp: how A is applied, decided once -------------------------------------------------------------------------
 int LinOp::init(pyn_ctx* ctx, DMat& M, int matfree, Ensure e) {
   c = ctx;
   A = &M;
   op = matfree;
   mf = matfree != PYN_MATFREE_OFF ? pyn_matfree_backend(ctx) : nullptr;
-  // a compact imposed-column matrix has no other product than the one pyn_sell_ensure sets up (its stored rows, block CSR)
-  ensured = !mf && (e != IF_READY || M.prod_ready) && (M.rhs_compact || (pyn_sell_supported(M) && !getenv("PYNAMA_NO_SELL")));
-  if (ensured && e != IF_READY) PYN_TRY(pyn_sell_ensure(ctx, M, e == SOLVER));
-  S = ensured ? pyn_sell_shape(ctx, M) : nullptr;
+  if (mf) return PYN_OK;
+  if (e != IF_READY) PYN_TRY(pyn_sell_ensure(ctx, M, e == SOLVER));
+  plan = M.plan.kind != PK_NONE ? &M.plan : &PYN_RAW_PLAN;
+  if (plan->kind != PK_RAW) S = pyn_sell_shape(ctx, M);
   return PYN_OK;
 }
 
 int LinOp::apply(const double* x, double* y) const {
-  if (mf) return mf->spmv(c, op, x, y, false, nullptr);
-  return ensured ? pyn_sell_spmv(c, *A, x, y, false, nullptr) : pyn_spmv_raw(c, *A, x, y);
+  return mf ? mf->spmv(c, op, x, y, false, nullptr) : pyn_sell_spmv(c, *A, *plan, x, y, false, nullptr);
 }
 
 int LinOp::apply_dot(const double* x, double* y, int* grid) const {
-  const int64_t rows = c->n_owned * A->br;
-  *grid = sgrid(rows);
-  if (mf) return mf->spmv(c, op, x, y, true, grid);
-  if (ensured) return pyn_sell_spmv(c, *A, x, y, true, grid);
-  spmv_kernel<32, true><<<*grid, 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, A->val, x, y, rows, A->br, A->bc, c->d_flag, c->d_part);
-  pyn_product_record(c, 1, 0, 0, true, *grid, 0);
-  return PYN_OK;
+  *grid = pyn_raw_grid(c->n_owned * A->br);
+  return mf ? mf->spmv(c, op, x, y, true, grid) : pyn_sell_spmv(c, *A, *plan, x, y, true, grid);
 }
 
 // the part that reads no ghost leaves its partials in [0, g0), at most PYN_MAX_PARTIALS - 512 of them; the rest (matrix-free: the bottom
@@ -615,9 +563,9 @@ int LinOp::apply_split(const double* x, double* y, int* grid) const {
     PYN_HIP(hipStreamWaitEvent(s, c->ev_halo, 0));
     PYN_TRY(mf->part(c, op, x, y, true, 2, g0, 512, s, &g1));
   } else {
-    PYN_TRY(pyn_sell_spmv_range(c, *A, x, y, true, S->int_begin, S->int_end, 0, PYN_MAX_PARTIALS - 512, s, &g0));
+    PYN_TRY(pyn_sell_spmv_range2(c, *A, *plan, x, y, true, S->int_begin, S->int_end, S->int_end, S->int_end, 0, PYN_MAX_PARTIALS - 512, s, &g0));
     PYN_HIP(hipStreamWaitEvent(s, c->ev_halo, 0));
-    PYN_TRY(pyn_sell_spmv_range2(c, *A, x, y, true, 0, S->int_begin, S->int_end, S->ns, g0, 512, s, &g1));
+    PYN_TRY(pyn_sell_spmv_range2(c, *A, *plan, x, y, true, 0, S->int_begin, S->int_end, S->ns, g0, 512, s, &g1));
   }
   *grid = g0 + g1;
   return PYN_OK;
@@ -717,7 +665,7 @@ extern "C" int pyn_spmv(pyn_ctx* c, int mat_id, int xv, int yv) {
   }
   LinOp Aop;
   PYN_TRY(Aop.init(c, A, PYN_MATFREE_OFF, LinOp::ONCE));
-  if (Aop.ensured) PYN_HIP(hipEventRecord(c->ev0, c->stream));  // time the product, not the (one-off) conversion
+  if (Aop.plan->kind != PK_RAW) PYN_HIP(hipEventRecord(c->ev0, c->stream));  // time the product, not the (one-off) conversion
   PYN_TRY(Aop.apply(c->vecs[xv].d, c->vecs[yv].d));
   PYN_HIP(hipEventRecord(c->ev1, c->stream));
   PYN_HIP(hipStreamSynchronize(c->stream));

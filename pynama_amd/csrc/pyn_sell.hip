@@ -1,9 +1,17 @@
-// SELL-64 (sliced ELLPACK, slice height = one wavefront) copy of a scalar matrix for the Krylov
-// loop: lane == row, so every load of values / column indices is a contiguous 512 B / 256 B per
-// wave instruction, no cross-lane reduction, and on lexicographically numbered meshes the x-gather
-// of 64 consecutive rows is itself contiguous.  CSR stays the canonical storage (assembly output,
-// host access); the SELL image is a solver-side acceleration structure rebuilt when values change
-// (PETSc analogue: MatAssemblyEnd building the compressed-row / inode structures used by MatMult).
+// Every assembled product y = A x (+ the fused dot x.Ax) of the library, and the one place that chooses among them.
+//
+// CSR stays the canonical storage (assembly output, host access).  Eight kernel families multiply from it (ProductKind, pyn_internal.h):
+//   PK_RAW      spmv_kernel<32>: 32 lanes per scalar row, any block shape, needs nothing but the graph
+//   PK_SELL, PK_SELLP, PK_SELLB_X, PK_SELLB_D
+//               a SELL-64 image of the values (sliced ELLPACK, slice height = one wavefront, lane == scalar row: 512-B value loads, no
+//               cross-lane reduction), scalar / block, explicit columns / node-level column-pattern dictionary.  The image is a
+//               solver-side copy rebuilt when values change (PETSc analogue: MatAssemblyEnd building the inode structures of MatMult)
+//   PK_CSRL, PK_CSRLB
+//               lane per scalar row over LDS-staged contiguous runs of the CSR values, columns from the dictionary: no image
+//   PK_BCSR     8 .. 64 lanes per node row straight from the block-CSR values: no image, the only product of a compact matrix
+// pyn_sell_ensure resolves one ProductPlan per matrix and value version: shared structure (dictionary per graph, slices per block shape),
+// then product_choose -- a pure host function of a few facts and the knobs, the only reader of the product knobs -- then the image, if
+// the choice needs one.  pyn_sell_spmv_range2 launches from a plan: ranges, grid, one switch over the kind, the record.
 #include <hipcub/hipcub.hpp>
 
 #include "pyn_internal.h"
@@ -682,6 +690,43 @@ __global__ void __launch_bounds__(256) bcsr_spmv_kernel(const int32_t* __restric
   }
 }
 
+// Any block shape without dictionary, slices or image: LPR lanes per scalar row, rows of one node are contiguous in `val`
+// y[(i,p)] = sum_k sum_q val[(rowptr[i]*br + p*len + k)*bc + q] * x[colidx[rowptr[i]+k]*bc + q]
+template <int LPR, bool DOT>
+__global__ void __launch_bounds__(256) spmv_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                                                   const double* __restrict__ val, const double* __restrict__ x,
+                                                   double* __restrict__ y, int64_t n_rows, int br, int bc,
+                                                   const int* __restrict__ flag, double* __restrict__ part) {
+  if (flag && flag[0]) return;   // slot 0: the solver's done flag
+  const int lane = threadIdx.x % LPR;
+  const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LPR;
+  const int64_t ngrp = (int64_t)gridDim.x * blockDim.x / LPR;
+  double dot = 0.0;
+  for (int64_t r = grp; r < n_rows; r += ngrp) {
+    int64_t i = r / br;
+    int p = (int)(r - i * br);
+    int lo = rowptr[i];
+    int len = rowptr[i + 1] - lo;
+    const double* v = val + ((int64_t)lo * br + (int64_t)p * len) * bc;
+    const int n = len * bc;
+    double acc = 0.0;
+    if (bc == 1) {
+      for (int idx = lane; idx < n; idx += LPR) acc += v[idx] * x[colidx[lo + idx]];
+    } else {
+      for (int idx = lane; idx < n; idx += LPR) {
+        int k = idx / bc, q = idx - k * bc;
+        acc += v[idx] * x[(int64_t)colidx[lo + k] * bc + q];
+      }
+    }
+    for (int o = LPR / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, LPR);
+    if (lane == 0) {
+      y[r] = acc;
+      if (DOT) dot += acc * x[r];
+    }
+  }
+  if (DOT) block_partial(dot, part);
+}
+
 }  // namespace
 
 namespace {
@@ -845,8 +890,6 @@ static int build_pattern_dictionary(pyn_ctx* c, int maxw) {
   return PYN_OK;
 }
 
-// (re)build the SELL image of a matrix; the structure (slice pointers, widths, explicit columns) is
-// shared by all matrices of the same block shape, the column-pattern dictionary by all of them
 // slice s needs ghost entries of x iff one of its nodes has a column >= n_owned (rows are sorted: the last one)
 __global__ void slice_ghost_flag_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx, int64_t n_owned,
                                         int br, int64_t ns, int* __restrict__ flags) {
@@ -858,35 +901,96 @@ __global__ void slice_ghost_flag_kernel(const int32_t* __restrict__ rowptr, cons
   }
 }
 
-// Scalar matrices whose rows follow the column-pattern dictionary (rows of at most PAT_W entries) are multiplied straight from their CSR
-// values (csrl_spmv_kernel): no SELL image, no refresh after an assembly.  PYNAMA_SELL_IMAGE=1 keeps the image-based kernel.
-static bool csr_product(const pyn_ctx* c, const DMat& A, const SellShape* S) {
-  return A.br == 1 && A.bc == 1 && c->sell_npat > 0 && S && S->maxw <= PAT_W && !getenv("PYNAMA_SELL_IMAGE");
+// ---- the choice ---------------------------------------------------------------------------------------------------------------------
+// Every rule that picks a family and its launch shape is in product_choose: a host function of a few facts about the matrix and of
+// the knobs, without a HIP call (exported as pyn_product_choose, so it is tested without a device).
+struct ProductFacts {
+  int br, bc, npat, maxw;    // block shape, patterns of the node dictionary (0: none), longest scalar row
+  int64_t nnzb, n_owned;
+  bool rhs_compact, solver, image;   // solver: the product will be repeated; image: a SELL image of the current values exists
+};
+struct ProductKnobs {   // the environment, read once per resolve; an integer knob that is not set is -1
+  bool sell_image, block_sell, no_csrlb, no_sell;
+  double bcsr_min_avg;
+  int bcsr_lanes, bcsr_unroll, bcsr_wgs, csrlb_wgs, csr_wgs, max_grid;
+};
+static int env_int(const char* name) {
+  const char* e = getenv(name);
+  return e ? std::max(0, atoi(e)) : -1;
+}
+static ProductKnobs read_knobs() {
+  const char* avg = getenv("PYNAMA_BCSR_MIN_AVG");
+  return {getenv("PYNAMA_SELL_IMAGE") != nullptr, getenv("PYNAMA_BLOCK_SELL") != nullptr, getenv("PYNAMA_NO_CSRLB") != nullptr,
+          getenv("PYNAMA_NO_SELL") != nullptr, avg ? atof(avg) : 128.0, env_int("PYNAMA_BCSR_LANES"), env_int("PYNAMA_BCSR_UNROLL"),
+          env_int("PYNAMA_BCSR_WGS_PER_CU"), env_int("PYNAMA_CSRLB_WGS_PER_CU"), env_int("PYNAMA_CSR_SPMV_WGS_PER_CU"),
+          env_int("PYNAMA_SPMV_MAX_GRID")};   // (the last one, tests: persistent loops turn at small sizes)
 }
 
-// Block matrices, and scalar matrices whose rows are too long for the dictionary (second-order elements: up to 125 entries), are
-// multiplied straight from the block-CSR values as well (bcsr_spmv_kernel).  PYNAMA_BLOCK_SELL=1 keeps the SELL image (A/B, tests).
+static bool sell_shape(int bc) { return bc == 1 || bc == 2 || bc == 3 || bc == 6; }
 static bool bcsr_shape(int br, int bc) {
   return (br == bc && (br == 1 || br == 2 || br == 3)) || (bc == 1 && (br == 2 || br == 3)) || (br == 1 && (bc == 2 || bc == 3)) ||
          (br == 3 && bc == 2) || (br == 2 && bc == 3) || (br == 6 && bc == 3) || (br == 3 && bc == 6);
 }
-// 1: every product of A reads the CSR values (long rows: the SELL image would carry 20 % of padding and cost a refresh per assembly);
-// 2: only one-off products do (pyn_spmv of a matrix without a current image: Krhs v, Rw w, the operators -- a refresh costs three
-// products), solvers build the image, whose lane-per-row kernel is 20-25 % faster on the short rows of first-order elements; 0: never
-static int bcsr_mode(const pyn_ctx* c, const DMat& A) {
-  if (getenv("PYNAMA_BLOCK_SELL") || !bcsr_shape(A.br, A.bc)) return 0;
-  const char* e = getenv("PYNAMA_BCSR_MIN_AVG");
-  const double min_avg = e ? atof(e) : 128.0;
-  const double avg = (double)c->nnzb * A.bc / (double)std::max<int64_t>(1, c->n_owned);   // entries per scalar row
-  return avg >= min_avg ? 1 : 2;
+// the 32-lane kernel needs neither dictionary nor slices: decided from the block shape and PYNAMA_NO_SELL alone
+static bool raw_only(const ProductFacts& f, const ProductKnobs& k) { return !f.rhs_compact && (k.no_sell || !sell_shape(f.bc)); }
+
+// kind (PK_NONE: no product for this block shape), W, lg and unroll of the plan; *keep_image false: never an image, every product of
+// the matrix reads A.val
+static ProductPlan product_choose(const ProductFacts& f, const ProductKnobs& k, bool* keep_image) {
+  auto pick = [&](ProductPlan p, bool keep) { *keep_image = keep; return p; };   // p: {kind, W, lg, unroll}
+  const double avg = (double)f.nnzb * f.bc / (double)std::max<int64_t>(1, f.n_owned);   // entries per scalar row
+  auto bcsr = [&](bool keep) {
+    // measured (tools/block_spmv_case.py): 16 lanes for 81 .. 375 entries per scalar row, 8 below; 32 / 64 lanes lose 5-10 % even on
+    // the longest rows (fewer node rows, i.e. fewer independent load streams, per wave)
+    const int g = k.bcsr_lanes, lg = g >= 0 ? (g >= 64 ? 6 : g >= 32 ? 5 : g >= 16 ? 4 : 3) : (avg >= 56.0 ? 4 : 3);
+    const int u = k.bcsr_unroll >= 0 ? k.bcsr_unroll : (avg >= 24.0 ? 8 : 4);   // whole rows in one trip where the registers allow
+    return pick({PK_BCSR, 0, lg, (u == 2 || u == 3 || u == 8) ? u : 4}, keep);
+  };
+  const bool scalar = f.br == 1 && f.bc == 1;
+  if (f.rhs_compact) return bcsr_shape(f.br, f.bc) ? bcsr(true) : pick({}, true);   // stored rows only, from their block-CSR values
+  if (raw_only(f, k)) return pick({PK_RAW}, true);
+  // Scalar matrices whose rows follow the dictionary (at most PAT_W entries) are multiplied straight from their CSR values: no SELL
+  // image, no refresh after an assembly.  PYNAMA_SELL_IMAGE=1 keeps the image-based kernel.
+  if (scalar && f.npat > 0 && f.maxw <= PAT_W && !k.sell_image) return pick({PK_CSRL, f.maxw <= 27 ? 27 : 32}, false);
+  // 2x2 blocks in dictionary mode: lane per scalar row over LDS-staged runs of the block-CSR values
+  if (f.br == 2 && f.bc == 2 && f.npat > 0 && f.maxw <= 50 && !k.block_sell && !k.no_csrlb)
+    return pick({PK_CSRLB, f.maxw <= 18 ? 18 : (f.maxw <= 32 ? 32 : 50)}, false);
+  // Block matrices, and scalar matrices whose rows are too long for the dictionary (second-order elements: up to 125 entries), are
+  // multiplied from the block-CSR values as well.  1: every product of A (long rows: the SELL image would carry 20 % of padding and
+  // cost a refresh per assembly); 2: only one-off products (pyn_spmv of a matrix without a current image: Krhs v, Rw w, the operators
+  // -- a refresh costs three products), solvers build the image, whose lane-per-row kernel is 20-25 % faster on the short rows of
+  // first-order elements; 0: never (PYNAMA_BLOCK_SELL=1: A/B, tests).  Scalar rows inside the dictionary's width keep their kernels.
+  int bm = (k.block_sell || !bcsr_shape(f.br, f.bc)) ? 0 : (avg >= k.bcsr_min_avg ? 1 : 2);
+  if (scalar && !(f.maxw > PAT_W && !k.sell_image)) bm = 0;
+  if (bm == 1) return bcsr(false);
+  if (bm == 2 && !f.solver && !f.image) return bcsr(true);
+  return pick({scalar ? (f.npat > 0 ? PK_SELLP : PK_SELL) : (f.npat > 0 ? PK_SELLB_D : PK_SELLB_X)}, true);
 }
 
-int pyn_sell_ensure(pyn_ctx* c, DMat& A, bool solver) {
-  PYN_CHECK(pyn_sell_supported(A), "no SELL kernel for block shape %dx%d", A.br, A.bc);
+extern "C" int pyn_product_choose(int br, int bc, int npat, int maxw, int64_t nnzb, int64_t n_owned, int rhs_compact, int solver,
+                                  int image, int sell_image, int block_sell, int no_csrlb, int no_sell, double bcsr_min_avg,
+                                  int bcsr_lanes, int bcsr_unroll, int* kind, int* W, int* lanes, int* unroll) {
+  PYN_CHECK(kind && W && lanes && unroll, "pyn_product_choose: NULL output");
+  PYN_CHECK(br > 0 && bc > 0 && npat >= 0 && maxw >= 0 && nnzb >= 0 && n_owned >= 0, "pyn_product_choose: bad argument");
+  const ProductKnobs k{sell_image != 0, block_sell != 0, no_csrlb != 0, no_sell != 0, bcsr_min_avg >= 0.0 ? bcsr_min_avg : 128.0,
+                       std::max(-1, bcsr_lanes), std::max(-1, bcsr_unroll), -1, -1, -1, -1};
+  bool keep_image;
+  const ProductPlan ch = product_choose({br, bc, npat, maxw, nnzb, n_owned, rhs_compact != 0, solver != 0, image != 0}, k, &keep_image);
+  *kind = ch.kind;
+  *W = ch.W;
+  *lanes = ch.kind == PK_BCSR ? 1 << ch.lg : 0;
+  *unroll = ch.unroll;
+  return PYN_OK;
+}
+
+// ---- shared structure ---------------------------------------------------------------------------------------------------------------
+// The node-level dictionary once per graph, and per block shape the slice pointers and widths (the explicit columns come with the first
+// image that needs them) and the interior slice range.
+static int sell_structure(pyn_ctx* c, const DMat& A, SellShape** out) {
   hipStream_t s = c->stream;
   const int64_t n = c->n_owned * A.br;  // scalar rows
   const int64_t ns = (n + SH - 1) / SH;
-  if (!c->sell_dict_built) {  // node-level dictionary, once per graph
+  if (!c->sell_dict_built) {
     std::vector<int32_t> rp((size_t)c->n_owned + 1);
     PYN_HIP(hipMemcpyAsync(rp.data(), c->d_rowptr, (c->n_owned + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     PYN_HIP(hipStreamSynchronize(s));
@@ -895,140 +999,120 @@ int pyn_sell_ensure(pyn_ctx* c, DMat& A, bool solver) {
     PYN_TRY(build_pattern_dictionary(c, maxlen));
     c->sell_dict_built = true;
   }
-  SellShape* S = nullptr;
-  for (auto& q : c->sell_shapes)
-    if (q.br == A.br && q.bc == A.bc) S = &q;
-  bool fresh = false;
-  if (!S) {
-    SellShape q;
-    q.br = A.br;
-    q.bc = A.bc;
-    q.ns = ns;
-    PYN_HIP(hipMalloc((void**)&q.w, ns * sizeof(int)));
-    sell_width_kernel<<<(int)std::min<int64_t>((ns + 255) / 256, 4096), 256, 0, s>>>(c->d_rowptr, n, A.br, A.bc, ns, q.w);
-    std::vector<int> w((size_t)ns);
-    PYN_HIP(hipMemcpyAsync(w.data(), q.w, ns * sizeof(int), hipMemcpyDeviceToHost, s));
+  *out = const_cast<SellShape*>(pyn_sell_shape(c, A));
+  if (*out) return PYN_OK;
+  SellShape q;
+  q.br = A.br;
+  q.bc = A.bc;
+  q.ns = ns;
+  PYN_HIP(hipMalloc((void**)&q.w, ns * sizeof(int)));
+  sell_width_kernel<<<(int)std::min<int64_t>((ns + 255) / 256, 4096), 256, 0, s>>>(c->d_rowptr, n, A.br, A.bc, ns, q.w);
+  std::vector<int> w((size_t)ns);
+  PYN_HIP(hipMemcpyAsync(w.data(), q.w, ns * sizeof(int), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipStreamSynchronize(s));
+  std::vector<int64_t> ptr((size_t)ns + 1);
+  ptr[0] = 0;
+  for (int64_t i = 0; i < ns; ++i) {
+    ptr[i + 1] = ptr[i] + (int64_t)w[i] * SH;
+    q.maxw = std::max(q.maxw, w[i]);
+  }
+  q.total = ptr[ns];
+  PYN_HIP(hipMalloc((void**)&q.ptr, (ns + 1) * sizeof(int64_t)));
+  PYN_HIP(hipMemcpyAsync(q.ptr, ptr.data(), (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  PYN_HIP(hipStreamSynchronize(s));
+  if (c->n_ghost > 0) {
+    // interior slices (no ghost columns) can be multiplied while the halo exchange is in flight: usable when
+    // they form ONE contiguous range (z-slabs: everything between the first and the last node plane)
+    DevTmp tf;
+    PYN_HIP(tf.alloc(ns * sizeof(int)));
+    slice_ghost_flag_kernel<<<(int)std::min<int64_t>((ns + 255) / 256, 4096), 256, 0, s>>>(c->d_rowptr, c->d_colidx, c->n_owned, A.br,
+                                                                                       ns, tf.as<int>());
+    std::vector<int> fl((size_t)ns);
+    PYN_HIP(hipMemcpyAsync(fl.data(), tf.p, ns * sizeof(int), hipMemcpyDeviceToHost, s));
     PYN_HIP(hipStreamSynchronize(s));
-    std::vector<int64_t> ptr((size_t)ns + 1);
-    ptr[0] = 0;
-    for (int64_t i = 0; i < ns; ++i) {
-      ptr[i + 1] = ptr[i] + (int64_t)w[i] * SH;
-      q.maxw = std::max(q.maxw, w[i]);
+    int64_t i0 = 0, i1 = ns;
+    while (i0 < ns && fl[i0]) ++i0;
+    while (i1 > i0 && fl[i1 - 1]) --i1;
+    bool contiguous = i1 > i0;
+    for (int64_t i = i0; i < i1 && contiguous; ++i) contiguous = !fl[i];
+    if (contiguous) {
+      q.int_begin = i0;
+      q.int_end = i1;
     }
-    q.total = ptr[ns];
-    PYN_HIP(hipMalloc((void**)&q.ptr, (ns + 1) * sizeof(int64_t)));
-    PYN_HIP(hipMemcpyAsync(q.ptr, ptr.data(), (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    PYN_HIP(hipStreamSynchronize(s));
-    // explicit columns (no dictionary): allocated with the first IMAGE of this shape -- matrices multiplied from their CSR values never need them
-    if (c->n_ghost > 0) {
-      // interior slices (no ghost columns) can be multiplied while the halo exchange is in flight: usable when
-      // they form ONE contiguous range (z-slabs: everything between the first and the last node plane)
-      DevTmp tf;
-      PYN_HIP(tf.alloc(ns * sizeof(int)));
-      slice_ghost_flag_kernel<<<(int)std::min<int64_t>((ns + 255) / 256, 4096), 256, 0, s>>>(c->d_rowptr, c->d_colidx, c->n_owned, A.br,
-                                                                                         ns, tf.as<int>());
-      std::vector<int> fl((size_t)ns);
-      PYN_HIP(hipMemcpyAsync(fl.data(), tf.p, ns * sizeof(int), hipMemcpyDeviceToHost, s));
-      PYN_HIP(hipStreamSynchronize(s));
-      int64_t i0 = 0, i1 = ns;
-      while (i0 < ns && fl[i0]) ++i0;
-      while (i1 > i0 && fl[i1 - 1]) --i1;
-      bool contiguous = i1 > i0;
-      for (int64_t i = i0; i < i1 && contiguous; ++i) contiguous = !fl[i];
-      if (contiguous) {
-        q.int_begin = i0;
-        q.int_end = i1;
-      }
-    }
-    c->sell_shapes.push_back(q);
-    S = &c->sell_shapes.back();
-    fresh = true;
   }
-  A.csr_product = csr_product(c, A, S);
-  A.bcsr_product = false;
-  if (A.rhs_compact) {   // stored rows only, from their block-CSR values
-    PYN_CHECK(bcsr_shape(A.br, A.bc), "no block-CSR product for block shape %dx%d", A.br, A.bc);
-    A.csr_product = A.csrlb_product = false;
-    A.bcsr_product = true;
-    A.prod_ready = true;
-    return PYN_OK;
-  }
-  A.csrlb_product = !A.csr_product && A.br == 2 && A.bc == 2 && c->sell_npat > 0 && S->maxw <= 50 && !getenv("PYNAMA_BLOCK_SELL") &&
-                    !getenv("PYNAMA_NO_CSRLB");
-  int bm = 0;
-  if (!A.csr_product && !A.csrlb_product) {
-    bm = bcsr_mode(c, A);
-    if (A.br == 1 && A.bc == 1 && !(S->maxw > PAT_W && !getenv("PYNAMA_SELL_IMAGE"))) bm = 0;   // scalar rows inside the dictionary's width keep their kernels
-    A.bcsr_product = bm == 1 || (bm == 2 && !solver && !(A.sell_val && A.sell_valid));
-  }
-  if (A.csr_product || A.csrlb_product || bm == 1) {   // never an image: the products read A.val
-    if (A.sell_val) {
-      (void)hipFree(A.sell_val);
-      A.sell_val = nullptr;
-    }
-    A.sell_valid = false;
-  }
-  if (A.csr_product || A.csrlb_product || A.bcsr_product) {
-    A.prod_ready = true;
-    return PYN_OK;
-  }
+  c->sell_shapes.push_back(q);
+  *out = &c->sell_shapes.back();
+  return PYN_OK;
+}
+
+// the SELL image of A holds the current values (the structure is shared by all matrices of the block shape)
+static int sell_image(pyn_ctx* c, DMat& A, SellShape* S, bool fresh) {
+  hipStream_t s = c->stream;
+  const int64_t n = c->n_owned * A.br, ns = S->ns;
   if (!A.sell_val) {
     PYN_HIP(hipMalloc((void**)&A.sell_val, S->total * sizeof(double)));
     A.sell_valid = false;
   }
   const bool cols = c->sell_npat == 0 && !S->col;   // this image also writes the shape's explicit column array
   if (cols) PYN_HIP(hipMalloc((void**)&S->col, S->total * sizeof(int32_t)));
-  if (!A.sell_valid || fresh || cols) {
-    if (A.br == 1 && A.bc == 1 && (size_t)SH * S->maxw * 12 <= 64 * 1024) {
-      const size_t lds = (size_t)SH * S->maxw * (cols ? 12 : 8);
-      const int grid = (int)std::min<int64_t>(ns, 256 * 32);
-      if (cols)
-        sell_fill_kernel<true><<<grid, 64, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, ns, S->ptr, S->w, S->maxw, A.sell_val, S->col);
-      else
-        sell_fill_kernel<false><<<grid, 64, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, ns, S->ptr, S->w, S->maxw, A.sell_val, nullptr);
-    } else if ((size_t)SH * S->maxw * sizeof(double) <= 96 * 1024 && !getenv("PYNAMA_SELL_FILL_STRIDED")) {
-      const size_t lds = (size_t)SH * S->maxw * sizeof(double);
-      const int grid = (int)std::min<int64_t>(ns, 256 * 8);
-      PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sell_fill_block_lds_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sell_fill_block_lds_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      if (cols)
-        sell_fill_block_lds_kernel<true><<<grid, 256, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, S->col);
-      else
-        sell_fill_block_lds_kernel<false><<<grid, 256, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, nullptr);
-    } else {
-      const int grid = (int)std::min<int64_t>((ns + 3) / 4, 256 * 16);
-      if (cols)
-        sell_fill_block_kernel<true><<<grid, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, S->col);
-      else
-        sell_fill_block_kernel<false><<<grid, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, nullptr);
-    }
-    PYN_HIP(hipGetLastError());
-    A.sell_valid = true;
+  if (A.sell_valid && !fresh && !cols) return PYN_OK;
+  if (A.br == 1 && A.bc == 1 && (size_t)SH * S->maxw * 12 <= 64 * 1024) {
+    const size_t lds = (size_t)SH * S->maxw * (cols ? 12 : 8);
+    const int grid = (int)std::min<int64_t>(ns, 256 * 32);
+    auto fill = cols ? sell_fill_kernel<true> : sell_fill_kernel<false>;
+    fill<<<grid, 64, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, ns, S->ptr, S->w, S->maxw, A.sell_val, cols ? S->col : nullptr);
+  } else if ((size_t)SH * S->maxw * sizeof(double) <= 96 * 1024 && !getenv("PYNAMA_SELL_FILL_STRIDED")) {
+    const size_t lds = (size_t)SH * S->maxw * sizeof(double);
+    const int grid = (int)std::min<int64_t>(ns, 256 * 8);
+    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sell_fill_block_lds_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sell_fill_block_lds_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    auto fill = cols ? sell_fill_block_lds_kernel<true> : sell_fill_block_lds_kernel<false>;
+    fill<<<grid, 256, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, cols ? S->col : nullptr);
+  } else {
+    const int grid = (int)std::min<int64_t>((ns + 3) / 4, 256 * 16);
+    auto fill = cols ? sell_fill_block_kernel<true> : sell_fill_block_kernel<false>;
+    fill<<<grid, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, cols ? S->col : nullptr);
   }
-  A.prod_ready = true;
+  PYN_HIP(hipGetLastError());
+  A.sell_valid = true;
   return PYN_OK;
 }
 
-bool pyn_sell_supported(const DMat& A) { return A.bc == 1 || A.bc == 2 || A.bc == 3 || A.bc == 6; }
-
-template <int BC>
-static int launch_block(pyn_ctx* c, const SellShape& S, const DMat& A, const double* x, double* y, bool dot, int grid,
-                        int64_t s0, int64_t s1, int poff, int64_t hb, int64_t hl, hipStream_t st) {
-  const int64_t n = c->n_owned * A.br;
-  const size_t lds = (size_t)(c->sell_npat + 1) * PAT_W * sizeof(int32_t);
-  const bool pat = c->sell_npat > 0;
-  if (pat && dot)
-    sellb_spmv_kernel<BC, true, true><<<grid, 256, lds, st>>>(S.ptr, S.w, c->sell_pid, c->sell_tab, c->sell_npat, nullptr,
-                                                                     A.sell_val, x, y, n, A.br, s1, c->d_flag, c->d_part, s0, poff, hb, hl);
-  else if (pat)
-    sellb_spmv_kernel<BC, true, false><<<grid, 256, lds, st>>>(S.ptr, S.w, c->sell_pid, c->sell_tab, c->sell_npat, nullptr,
-                                                                      A.sell_val, x, y, n, A.br, s1, nullptr, nullptr, s0, poff, hb, hl);
-  else if (dot)
-    sellb_spmv_kernel<BC, false, true><<<grid, 256, 0, st>>>(S.ptr, S.w, nullptr, nullptr, 0, S.col, A.sell_val, x, y, n,
-                                                                    A.br, s1, c->d_flag, c->d_part, s0, poff, hb, hl);
-  else
-    sellb_spmv_kernel<BC, false, false><<<grid, 256, 0, st>>>(S.ptr, S.w, nullptr, nullptr, 0, S.col, A.sell_val, x, y, n,
-                                                                     A.br, s1, nullptr, nullptr, s0, poff, hb, hl);
+// ---- resolve: facts -> choice -> A.plan (and the image, where the choice is an image kernel) ----------------------------------------
+int pyn_sell_ensure(pyn_ctx* c, DMat& A, bool solver) {
+  const ProductKnobs k = read_knobs();
+  ProductFacts f{A.br, A.bc, 0, 0, c->nnzb, c->n_owned, A.rhs_compact, solver, A.sell_val && A.sell_valid};
+  SellShape* S = nullptr;
+  const size_t shapes = c->sell_shapes.size();
+  if (!raw_only(f, k)) {
+    PYN_CHECK(sell_shape(A.bc), "no SELL kernel for block shape %dx%d", A.br, A.bc);
+    PYN_TRY(sell_structure(c, A, &S));
+    f.npat = c->sell_npat;
+    f.maxw = S->maxw;
+  }
+  bool keep_image;
+  ProductPlan P = product_choose(f, k, &keep_image);
+  PYN_CHECK(P.kind != PK_NONE, "no block-CSR product for block shape %dx%d", A.br, A.bc);
+  if (!keep_image) {   // the products read A.val
+    if (A.sell_val) {
+      (void)hipFree(A.sell_val);
+      A.sell_val = nullptr;
+    }
+    A.sell_valid = false;
+  }
+  if (P.kind >= PK_SELL && P.kind <= PK_SELLB_D) PYN_TRY(sell_image(c, A, S, c->sell_shapes.size() != shapes));
+  // what the launches need beyond the choice: LDS (staged runs, dictionary), the resident-workgroup cap, the grid clamp
+  const int waves = P.kind == PK_CSRL ? CSRL_WAVES : (P.kind == PK_CSRLB ? CSRLB_WAVES : 0);
+  if (waves || P.kind == PK_SELLP || P.kind == PK_SELLB_D)
+    P.lds = (size_t)waves * 64 * P.W * sizeof(double) + (size_t)(c->sell_npat + 1) * PAT_W * sizeof(int32_t);
+  // csrl: persistent waves, exactly the workgroups that are resident together (LDS: 160 KB per CU; 160-190 VGPRs: three / two waves per
+  // SIMD), so that every wave walks the same number of slices -- a grid of 1.6 x that capacity runs 20 % longer
+  const int csrl_per_cu = std::max(1, std::min((int)(163840 / (P.lds + 64)), 8 / CSRL_WAVES));   // eight waves per CU (ten: +3 %, twelve: +12 %)
+  const int wgs = P.kind == PK_CSRL ? (k.csr_wgs >= 0 ? k.csr_wgs : csrl_per_cu)
+                                    : (P.kind == PK_CSRLB ? k.csrlb_wgs : (P.kind == PK_BCSR ? k.bcsr_wgs : -1));
+  if (wgs >= 0) P.wg_cap = 256 * wgs;   // else: what the occupancy query of the kernel says (csrlb, bcsr)
+  if (k.max_grid >= 0) P.max_grid = std::max(1, k.max_grid);
+  A.plan = P;
   return PYN_OK;
 }
 
@@ -1038,216 +1122,209 @@ const SellShape* pyn_sell_shape(pyn_ctx* c, const DMat& A) {
   return nullptr;
 }
 
-// y = A x over the slices [s0, s1) on stream `st`; the fused dot partials go to d_part[poff .. poff + grid)
-int pyn_sell_spmv_range(pyn_ctx* c, const DMat& A, const double* x, double* y, bool dot, int64_t s0, int64_t s1, int poff,
-                        int max_grid, hipStream_t st, int* grid_out) {
-  return pyn_sell_spmv_range2(c, A, x, y, dot, s0, s1, s1, s1, poff, max_grid, st, grid_out);
+// ---- launchers: one per family ------------------------------------------------------------------------------------------------------
+namespace {
+struct Launch {   // one product launch: the logical range [s0, s1) with the hole [hb, hb + hl) cut out -- slices; PK_BCSR: node rows
+  pyn_ctx* c;
+  const DMat& A;
+  const SellShape* S;
+  const ProductPlan& P;
+  const double* x;
+  double* y;
+  const int* flag;   // fused dot: the solver's done flag and the partials (c->d_flag, c->d_part), else null
+  double* part;
+  int64_t s0, s1, hb, hl;
+  int poff, max_grid;
+  hipStream_t st;
+};
+
+// persistent waves: at most the workgroups that are resident together (a grid of 1.6 x that capacity runs a second, half-empty round)
+int persistent_grid(const Launch& L, int64_t want, int resident) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, L.max_grid), L.P.wg_cap >= 0 ? L.P.wg_cap : resident));
 }
 
-// the same over [a0, a1) U [b0, b1), a1 <= b0, in ONE launch (a rank's bottom and top boundary slices): the kernels walk the
-// logical range with the hole [a1, b0) cut out
-int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const double* x, double* y, bool dot, int64_t a0, int64_t a1, int64_t b0,
-                         int64_t b1, int poff, int max_grid, hipStream_t st, int* grid_out) {
-  if (const char* mg = getenv("PYNAMA_SPMV_MAX_GRID")) max_grid = std::max(1, std::min(max_grid, atoi(mg)));   // tests: persistent loops turn at small sizes
+template <bool DOT>
+int launch_raw(const Launch& L, int* grid) {
+  const int64_t rows = L.c->n_owned * L.A.br;
+  *grid = pyn_raw_grid(rows);
+  spmv_kernel<32, DOT><<<*grid, 256, 0, L.st>>>(L.c->d_rowptr, L.c->d_colidx, L.A.val, L.x, L.y, rows, L.A.br, L.A.bc, L.flag, L.part);
+  return PYN_OK;
+}
+
+template <bool DOT>
+int launch_sell(const Launch& L, int grid) {   // scalar image
+  pyn_ctx* c = L.c;
+  const SellShape& S = *L.S;
+  if (L.P.kind == PK_SELLP)
+    sellp_spmv_kernel<DOT><<<grid, 256, L.P.lds, L.st>>>(S.ptr, S.w, c->sell_pid, c->sell_tab, c->sell_npat, L.A.sell_val, L.x, L.y, c->n_owned,
+                                                         L.s1, L.flag, L.part, L.s0, L.poff, L.hb, L.hl);
+  else
+    sell_spmv_kernel<DOT><<<grid, 256, 0, L.st>>>(S.ptr, S.w, S.col, L.A.sell_val, L.x, L.y, c->n_owned, L.s1, L.flag, L.part, L.s0, L.poff, L.hb,
+                                                  L.hl);
+  return PYN_OK;
+}
+
+template <int BC, bool DOT>
+int launch_sellb(const Launch& L, int grid) {   // block image
+  pyn_ctx* c = L.c;
+  const SellShape& S = *L.S;
+  const int64_t n = c->n_owned * L.A.br;
+  if (L.P.kind == PK_SELLB_D)
+    sellb_spmv_kernel<BC, true, DOT><<<grid, 256, L.P.lds, L.st>>>(S.ptr, S.w, c->sell_pid, c->sell_tab, c->sell_npat, nullptr, L.A.sell_val, L.x,
+                                                                   L.y, n, L.A.br, L.s1, L.flag, L.part, L.s0, L.poff, L.hb, L.hl);
+  else
+    sellb_spmv_kernel<BC, false, DOT><<<grid, 256, 0, L.st>>>(S.ptr, S.w, nullptr, nullptr, 0, S.col, L.A.sell_val, L.x, L.y, n, L.A.br, L.s1,
+                                                              L.flag, L.part, L.s0, L.poff, L.hb, L.hl);
+  return PYN_OK;
+}
+
+template <int W, bool DOT>
+int launch_csrl(const Launch& L, int* grid) {
+  static bool attr = false;
+  if (!attr) {
+    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(csrl_spmv_kernel<W, DOT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(CSRL_WAVES * 64 * W * sizeof(double) + (PAT_MAX + 1) * PAT_W * sizeof(int32_t))));
+    attr = true;
+  }
+  pyn_ctx* c = L.c;
+  *grid = persistent_grid(L, (L.s1 - L.s0 + CSRL_WAVES - 1) / CSRL_WAVES, 0);   // (the plan always carries the cap of this family)
+  PYN_CHECK(L.poff + *grid <= PYN_MAX_PARTIALS, "partial buffer overflow");
+  csrl_spmv_kernel<W, DOT><<<*grid, 64 * CSRL_WAVES, L.P.lds, L.st>>>(c->d_rowptr, c->sell_pid, c->sell_tab, c->sell_npat, L.A.val, L.x, L.y,
+                                                                      c->n_owned, L.s1, L.flag, L.part, L.s0, L.poff, L.hb, L.hl);
+  return PYN_OK;
+}
+
+template <int W, bool DOT>
+int launch_csrlb(const Launch& L, int* grid) {
+  constexpr bool GL = W > 32;
+  static int per_cu = 0;
+  if (!per_cu) {
+    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(csrlb_spmv_kernel<W, 2, 2, GL, DOT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(CSRLB_WAVES * 64 * W * sizeof(double) + (PAT_MAX + 1) * PAT_W * sizeof(int32_t))));
+    PYN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, csrlb_spmv_kernel<W, 2, 2, GL, DOT>, 64 * CSRLB_WAVES, L.P.lds));
+    per_cu = std::max(1, per_cu);
+  }
+  pyn_ctx* c = L.c;
+  *grid = persistent_grid(L, (L.s1 - L.s0 + CSRLB_WAVES - 1) / CSRLB_WAVES, 256 * per_cu);
+  PYN_CHECK(L.poff + *grid <= PYN_MAX_PARTIALS, "partial buffer overflow");
+  csrlb_spmv_kernel<W, 2, 2, GL, DOT><<<*grid, 64 * CSRLB_WAVES, L.P.lds, L.st>>>(c->d_rowptr, c->sell_pid, c->sell_tab, c->sell_npat, L.A.val,
+                                                                                  L.x, L.y, c->n_owned * L.A.br, L.s1, L.flag, L.part, L.s0,
+                                                                                  L.poff, L.hb, L.hl);
+  return PYN_OK;
+}
+
+// block-CSR values, G lanes per node row
+template <int BR, int BC, int U, bool DOT>
+int launch_bcsr_u(const Launch& L, int* grid) {
+  static int per_cu = 0;
+  if (!per_cu) {
+    PYN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bcsr_spmv_kernel<BR, BC, U, DOT>, 256, 0));
+    per_cu = std::max(1, std::min(per_cu, 8));
+  }
+  pyn_ctx* c = L.c;
+  const int npw = 64 >> L.P.lg;
+  *grid = persistent_grid(L, (L.s1 - L.s0 + 4 * npw - 1) / (4 * npw), 256 * per_cu);
+  PYN_CHECK(L.poff + *grid <= PYN_MAX_PARTIALS, "partial buffer overflow");
+  bcsr_spmv_kernel<BR, BC, U, DOT><<<*grid, 256, 0, L.st>>>(c->d_rowptr, c->d_colidx, L.A.val, L.x, L.y, L.P.lg, L.s0, L.s1, L.hb, L.hl, L.flag,
+                                                            L.part, L.poff, L.A.rhs_compact ? L.A.c_rsel : nullptr,
+                                                            L.A.rhs_compact ? L.A.c_cptr : nullptr);
+  return PYN_OK;
+}
+template <int BR, int BC, bool DOT>
+int launch_bcsr(const Launch& L, int* grid) {
+  switch (L.P.unroll) {
+    case 2: return launch_bcsr_u<BR, BC, 2, DOT>(L, grid);
+    case 3: return launch_bcsr_u<BR, BC, 3, DOT>(L, grid);
+    case 8: return launch_bcsr_u<BR, BC, 8, DOT>(L, grid);
+    default: return launch_bcsr_u<BR, BC, 4, DOT>(L, grid);
+  }
+}
+}  // namespace
+
+// Every assembled product launch: range checks and hole arithmetic, the grid, the family's launcher, the record.
+int pyn_sell_spmv_range2(pyn_ctx* c, const DMat& A, const ProductPlan& P, const double* x, double* y, bool dot, int64_t a0, int64_t a1,
+                         int64_t b0, int64_t b1, int poff, int max_grid, hipStream_t st, int* grid_out) {
   const SellShape* S = pyn_sell_shape(c, A);
-  PYN_CHECK(S && A.prod_ready, "pyn_sell_ensure first");
+  const int64_t ns = (c->n_owned * A.br + SH - 1) / SH;
+  PYN_CHECK(P.kind == PK_RAW || (P.kind != PK_NONE && S), "pyn_sell_ensure first");
   PYN_CHECK(!dot || A.br == A.bc, "fused dot needs a square block shape");
-  PYN_CHECK(a0 >= 0 && a0 <= a1 && a1 <= b0 && b0 <= b1 && b1 <= S->ns, "bad slice ranges");
+  PYN_CHECK(a0 >= 0 && a0 <= a1 && a1 <= b0 && b0 <= b1 && b1 <= ns, "bad slice ranges");
   const int64_t hb = a1, hl = b0 - a1;        // hole in logical coordinates
   const int64_t s0 = a0, s1 = b1 - hl;        // logical range
-  if (s0 == s1) {
-    if (grid_out) *grid_out = 0;
-    return PYN_OK;
-  }
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((s1 - s0 + 3) / 4, max_grid));
+  if (grid_out) *grid_out = 0;
+  if (s0 == s1 && P.kind != PK_RAW) return PYN_OK;   // (the raw product of an empty rank keeps its one workgroup: a zero partial)
+  max_grid = std::min(max_grid, P.max_grid);
+  int grid = (int)std::max<int64_t>(1, std::min<int64_t>((s1 - s0 + 3) / 4, max_grid));   // the image kernels: four slices per workgroup
   PYN_CHECK(poff + grid <= PYN_MAX_PARTIALS, "partial buffer overflow");
-  if (A.bcsr_product) {   // block-CSR values, G lanes per node row; slice boundaries become node boundaries (floor: a node that straddles
-                          // an interior and a boundary slice has no ghost column, either side may take it)
-    auto node_of = [&](int64_t sl) { return std::min<int64_t>(c->n_owned, sl * SH / A.br); };
-    int64_t na0 = node_of(a0), na1 = node_of(a1), nb0 = node_of(b0), nb1 = node_of(b1);
-    if (A.rhs_compact) {   // whole products only (a right-hand-side operator is never split for a halo overlap): all stored rows
-      PYN_CHECK(a0 == 0 && b1 == S->ns && a1 == b0 && !dot, "compact imposed-column matrix: whole products only");
-      na0 = 0;
-      na1 = nb0 = nb1 = A.c_nr;
+  Launch L{c, A, S, P, x, y, dot ? c->d_flag : nullptr, dot ? c->d_part : nullptr, s0, s1, hb, hl, poff, max_grid, st};
+  int p1 = P.W, rc = PYN_OK;
+  switch (P.kind) {
+    case PK_RAW:
+      PYN_CHECK(s0 == 0 && s1 == ns && poff == 0, "32-lane block-CSR product: whole products only");
+      rc = dot ? launch_raw<true>(L, &grid) : launch_raw<false>(L, &grid);
+      break;
+    case PK_SELL:
+    case PK_SELLP: rc = dot ? launch_sell<true>(L, grid) : launch_sell<false>(L, grid); break;
+    case PK_SELLB_X:
+    case PK_SELLB_D:
+      p1 = A.bc;
+      switch (A.bc) {
+        case 1: rc = dot ? launch_sellb<1, true>(L, grid) : launch_sellb<1, false>(L, grid); break;
+        case 2: rc = dot ? launch_sellb<2, true>(L, grid) : launch_sellb<2, false>(L, grid); break;
+        case 3: rc = dot ? launch_sellb<3, true>(L, grid) : launch_sellb<3, false>(L, grid); break;
+        default: rc = dot ? launch_sellb<6, true>(L, grid) : launch_sellb<6, false>(L, grid);
+      }
+      break;
+    case PK_CSRL:
+      rc = P.W == 27 ? (dot ? launch_csrl<27, true>(L, &grid) : launch_csrl<27, false>(L, &grid))
+                     : (dot ? launch_csrl<32, true>(L, &grid) : launch_csrl<32, false>(L, &grid));
+      break;
+    case PK_CSRLB:
+      rc = P.W == 18   ? (dot ? launch_csrlb<18, true>(L, &grid) : launch_csrlb<18, false>(L, &grid))
+           : P.W == 32 ? (dot ? launch_csrlb<32, true>(L, &grid) : launch_csrlb<32, false>(L, &grid))
+                       : (dot ? launch_csrlb<50, true>(L, &grid) : launch_csrlb<50, false>(L, &grid));
+      break;
+    case PK_BCSR: {
+      // slice boundaries become node boundaries (floor: a node that straddles an interior and a boundary slice has no ghost column,
+      // either side may take it)
+      auto node_of = [&](int64_t sl) { return std::min<int64_t>(c->n_owned, sl * SH / A.br); };
+      int64_t na0 = node_of(a0), na1 = node_of(a1), nb0 = node_of(b0), nb1 = node_of(b1);
+      if (A.rhs_compact) {   // whole products only (a right-hand-side operator is never split for a halo overlap): all stored rows
+        PYN_CHECK(a0 == 0 && b1 == S->ns && a1 == b0 && !dot, "compact imposed-column matrix: whole products only");
+        na0 = 0;
+        na1 = nb0 = nb1 = A.c_nr;
+      }
+      L.s0 = na0, L.s1 = nb1 - (nb0 - na1), L.hb = na1, L.hl = nb0 - na1;   // node rows from here on
+      if (L.s0 >= L.s1) return PYN_OK;
+      p1 = 1 << P.lg;
+      switch (A.br * 8 + A.bc) {
+        case 1 * 8 + 1: rc = dot ? launch_bcsr<1, 1, true>(L, &grid) : launch_bcsr<1, 1, false>(L, &grid); break;
+        case 2 * 8 + 2: rc = dot ? launch_bcsr<2, 2, true>(L, &grid) : launch_bcsr<2, 2, false>(L, &grid); break;
+        case 3 * 8 + 3: rc = dot ? launch_bcsr<3, 3, true>(L, &grid) : launch_bcsr<3, 3, false>(L, &grid); break;
+        case 2 * 8 + 1: rc = launch_bcsr<2, 1, false>(L, &grid); break;
+        case 3 * 8 + 1: rc = launch_bcsr<3, 1, false>(L, &grid); break;
+        case 1 * 8 + 2: rc = launch_bcsr<1, 2, false>(L, &grid); break;
+        case 1 * 8 + 3: rc = launch_bcsr<1, 3, false>(L, &grid); break;
+        case 3 * 8 + 2: rc = launch_bcsr<3, 2, false>(L, &grid); break;
+        case 2 * 8 + 3: rc = launch_bcsr<2, 3, false>(L, &grid); break;
+        case 6 * 8 + 3: rc = launch_bcsr<6, 3, false>(L, &grid); break;
+        case 3 * 8 + 6: rc = launch_bcsr<3, 6, false>(L, &grid); break;
+        default: PYN_CHECK(false, "no block-CSR product for block shape %dx%d", A.br, A.bc);
+      }
+      break;
     }
-    const int64_t nhb = na1, nhl = nb0 - na1, n0 = na0, n1 = nb1 - nhl;
-    if (n0 >= n1) {
-      if (grid_out) *grid_out = 0;
-      return PYN_OK;
-    }
-    const char* ge = getenv("PYNAMA_BCSR_LANES");
-    int lg;
-    if (ge) {
-      const int gg = atoi(ge);
-      lg = gg >= 64 ? 6 : gg >= 32 ? 5 : gg >= 16 ? 4 : 3;
-    } else {
-      const double avg = (double)c->nnzb * A.bc / (double)std::max<int64_t>(1, c->n_owned);   // entries per scalar row
-      lg = avg >= 56.0 ? 4 : 3;   // measured (tools/block_spmv_case.py): 16 lanes for 81 .. 375 entries per scalar row, 8 below; 32 / 64 lanes lose
-                                  // 5-10 % even on the longest rows (fewer node rows, i.e. fewer independent load streams, per wave)
-    }
-    const char* ue = getenv("PYNAMA_BCSR_UNROLL");
-    const double avg_row = (double)c->nnzb * A.bc / (double)std::max<int64_t>(1, c->n_owned);
-    const int un = ue ? atoi(ue) : (avg_row >= 24.0 ? 8 : 4);   // entries per lane and trip: whole rows in one trip where the registers allow
-    const int npw = 64 >> lg;
-    const char* wcu = getenv("PYNAMA_BCSR_WGS_PER_CU");
-    const int64_t want = (n1 - n0 + 4 * npw - 1) / (4 * npw);
-    int gridb = 1;
-  // persistent waves: exactly the workgroups that are resident together (a grid of 1.6 x that capacity runs a second, half-empty round)
-#define BCSR_LAUNCH_U(RR, CC, UU, DD)                                                                                                      \
-  do {                                                                                                                                     \
-    static int per_cu = 0;                                                                                                                 \
-    if (!per_cu) {                                                                                                                         \
-      PYN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bcsr_spmv_kernel<RR, CC, UU, DD>, 256, 0));                            \
-      per_cu = std::max(1, std::min(per_cu, 8));                                                                                           \
-    }                                                                                                                                      \
-    gridb = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(want, max_grid), 256 * (wcu ? atoi(wcu) : per_cu)));             \
-    PYN_CHECK(poff + gridb <= PYN_MAX_PARTIALS, "partial buffer overflow");                                                                \
-    bcsr_spmv_kernel<RR, CC, UU, DD><<<gridb, 256, 0, st>>>(c->d_rowptr, c->d_colidx, A.val, x, y, lg, n0, n1, nhb, nhl,                   \
-                                                            DD ? c->d_flag : nullptr, DD ? c->d_part : nullptr, poff,                     \
-                                                            A.rhs_compact ? A.c_rsel : nullptr, A.rhs_compact ? A.c_cptr : nullptr);      \
-  } while (0)
-#define BCSR_LAUNCH(RR, CC, DD)                 \
-  do {                                          \
-    if (un == 2)                                \
-      BCSR_LAUNCH_U(RR, CC, 2, DD);             \
-    else if (un == 3)                           \
-      BCSR_LAUNCH_U(RR, CC, 3, DD);             \
-    else if (un == 8)                           \
-      BCSR_LAUNCH_U(RR, CC, 8, DD);             \
-    else                                        \
-      BCSR_LAUNCH_U(RR, CC, 4, DD);             \
-  } while (0)
-#define BCSR_SQUARE(NN)          \
-  do {                           \
-    if (dot)                     \
-      BCSR_LAUNCH(NN, NN, true); \
-    else                         \
-      BCSR_LAUNCH(NN, NN, false); \
-  } while (0)
-    const int shape = A.br * 8 + A.bc;
-    switch (shape) {
-      case 1 * 8 + 1: BCSR_SQUARE(1); break;
-      case 2 * 8 + 2: BCSR_SQUARE(2); break;
-      case 3 * 8 + 3: BCSR_SQUARE(3); break;
-      case 2 * 8 + 1: BCSR_LAUNCH(2, 1, false); break;
-      case 3 * 8 + 1: BCSR_LAUNCH(3, 1, false); break;
-      case 1 * 8 + 2: BCSR_LAUNCH(1, 2, false); break;
-      case 1 * 8 + 3: BCSR_LAUNCH(1, 3, false); break;
-      case 3 * 8 + 2: BCSR_LAUNCH(3, 2, false); break;
-      case 2 * 8 + 3: BCSR_LAUNCH(2, 3, false); break;
-      case 6 * 8 + 3: BCSR_LAUNCH(6, 3, false); break;
-      case 3 * 8 + 6: BCSR_LAUNCH(3, 6, false); break;
-      default: PYN_CHECK(false, "no block-CSR product for block shape %dx%d", A.br, A.bc);
-    }
-#undef BCSR_LAUNCH_U
-#undef BCSR_SQUARE
-#undef BCSR_LAUNCH
-    PYN_HIP(hipGetLastError());
-    pyn_product_record(c, 8, 1 << lg, (un == 2 || un == 3 || un == 8) ? un : 4, dot, gridb, S->maxw);
-    if (grid_out) *grid_out = gridb;
-    return PYN_OK;
+    case PK_NONE: break;
   }
-  if (A.csrlb_product) {   // 2x2 blocks in dictionary mode: lane per scalar row over LDS-staged runs of the block-CSR values
-    const int W = S->maxw <= 18 ? 18 : (S->maxw <= 32 ? 32 : 50);
-    const size_t lds = (size_t)CSRLB_WAVES * 64 * W * sizeof(double) + (size_t)(c->sell_npat + 1) * PAT_W * sizeof(int32_t);
-    const char* gcu = getenv("PYNAMA_CSRLB_WGS_PER_CU");
-#define CSRLB_LAUNCH(WW, DD)                                                                                                              \
-  do {                                                                                                                                    \
-    static int per_cu = 0;                                                                                                                \
-    if (!per_cu) {                                                                                                                        \
-      PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(csrlb_spmv_kernel<WW, 2, 2, (WW > 32), DD>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)(CSRLB_WAVES * 64 * WW * sizeof(double) + (PAT_MAX + 1) * PAT_W * sizeof(int32_t))));             \
-      PYN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, csrlb_spmv_kernel<WW, 2, 2, (WW > 32), DD>, 64 * CSRLB_WAVES, lds));            \
-      per_cu = std::max(1, per_cu);                                                                                                       \
-    }                                                                                                                                     \
-    gridc = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((s1 - s0 + CSRLB_WAVES - 1) / CSRLB_WAVES, max_grid),         \
-                                                        256 * (gcu ? atoi(gcu) : per_cu)));                                              \
-    PYN_CHECK(poff + gridc <= PYN_MAX_PARTIALS, "partial buffer overflow");                                                               \
-    csrlb_spmv_kernel<WW, 2, 2, (WW > 32), DD><<<gridc, 64 * CSRLB_WAVES, lds, st>>>(c->d_rowptr, c->sell_pid, c->sell_tab, c->sell_npat, A.val, x, y, \
-                                                                          c->n_owned * A.br, s1, DD ? c->d_flag : nullptr,                \
-                                                                          DD ? c->d_part : nullptr, s0, poff, hb, hl);                    \
-  } while (0)
-    int gridc = 1;
-    if (W == 18 && dot) CSRLB_LAUNCH(18, true);
-    else if (W == 18) CSRLB_LAUNCH(18, false);
-    else if (W == 32 && dot) CSRLB_LAUNCH(32, true);
-    else if (W == 32) CSRLB_LAUNCH(32, false);
-    else if (dot) CSRLB_LAUNCH(50, true);
-    else CSRLB_LAUNCH(50, false);
-#undef CSRLB_LAUNCH
-    PYN_HIP(hipGetLastError());
-    pyn_product_record(c, 7, W, 0, dot, gridc, S->maxw);
-    if (grid_out) *grid_out = gridc;
-    return PYN_OK;
-  }
-  if (A.csr_product) {   // straight from the CSR values (decided once per pyn_sell_ensure, not per launch)
-    const int W = S->maxw <= 27 ? 27 : 32;
-    const size_t lds = (size_t)CSRL_WAVES * 64 * W * sizeof(double) + (size_t)(c->sell_npat + 1) * PAT_W * sizeof(int32_t);
-    // persistent waves: exactly the workgroups that are resident together (LDS: 160 KB per CU; 160-190 VGPRs: three / two waves per
-    // SIMD), so that every wave walks the same number of slices -- a grid of 1.6 x that capacity runs 20 % longer
-    const int per_cu = std::max(1, std::min((int)(163840 / (lds + 64)), 8 / CSRL_WAVES));   // eight waves per CU (ten: +3 %, twelve: +12 %)
-    const char* gcu = getenv("PYNAMA_CSR_SPMV_WGS_PER_CU");
-    const int resident = 256 * (gcu ? atoi(gcu) : per_cu);
-    const int gridc = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((s1 - s0 + CSRL_WAVES - 1) / CSRL_WAVES, max_grid), resident));
-#define CSRL_LAUNCH(WW, DD)                                                                                                             \
-  do {                                                                                                                                  \
-    static bool attr = false;                                                                                                           \
-    if (!attr) {                                                                                                                        \
-      PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(csrl_spmv_kernel<WW, DD>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)(CSRL_WAVES * 64 * WW * sizeof(double) + (PAT_MAX + 1) * PAT_W * sizeof(int32_t))));             \
-      attr = true;                                                                                                                      \
-    }                                                                                                                                   \
-    csrl_spmv_kernel<WW, DD><<<gridc, 64 * CSRL_WAVES, lds, st>>>(c->d_rowptr, c->sell_pid, c->sell_tab, c->sell_npat, A.val, x, y,     \
-                                                                  c->n_owned, s1, DD ? c->d_flag : nullptr, DD ? c->d_part : nullptr,  \
-                                                                  s0, poff, hb, hl);                                                    \
-  } while (0)
-    PYN_CHECK(poff + gridc <= PYN_MAX_PARTIALS, "partial buffer overflow");
-    if (W == 27 && dot) CSRL_LAUNCH(27, true);
-    else if (W == 27) CSRL_LAUNCH(27, false);
-    else if (dot) CSRL_LAUNCH(32, true);
-    else CSRL_LAUNCH(32, false);
-#undef CSRL_LAUNCH
-    PYN_HIP(hipGetLastError());
-    pyn_product_record(c, 6, W, 0, dot, gridc, S->maxw);
-    if (grid_out) *grid_out = gridc;
-    return PYN_OK;
-  }
-  if (A.br == 1 && A.bc == 1) {  // scalar fast paths
-    if (c->sell_npat > 0) {
-      const size_t lds = (size_t)(c->sell_npat + 1) * PAT_W * sizeof(int32_t);
-      if (dot)
-        sellp_spmv_kernel<true><<<grid, 256, lds, st>>>(S->ptr, S->w, c->sell_pid, c->sell_tab, c->sell_npat, A.sell_val, x, y,
-                                                        c->n_owned, s1, c->d_flag, c->d_part, s0, poff, hb, hl);
-      else
-        sellp_spmv_kernel<false><<<grid, 256, lds, st>>>(S->ptr, S->w, c->sell_pid, c->sell_tab, c->sell_npat, A.sell_val, x, y,
-                                                         c->n_owned, s1, nullptr, nullptr, s0, poff, hb, hl);
-    } else if (dot) {
-      sell_spmv_kernel<true><<<grid, 256, 0, st>>>(S->ptr, S->w, S->col, A.sell_val, x, y, c->n_owned, s1, c->d_flag, c->d_part, s0, poff, hb, hl);
-    } else {
-      sell_spmv_kernel<false><<<grid, 256, 0, st>>>(S->ptr, S->w, S->col, A.sell_val, x, y, c->n_owned, s1, nullptr, nullptr, s0, poff, hb, hl);
-    }
-  } else if (A.bc == 1) {
-    PYN_TRY(launch_block<1>(c, *S, A, x, y, dot, grid, s0, s1, poff, hb, hl, st));
-  } else if (A.bc == 2) {
-    PYN_TRY(launch_block<2>(c, *S, A, x, y, dot, grid, s0, s1, poff, hb, hl, st));
-  } else if (A.bc == 3) {
-    PYN_TRY(launch_block<3>(c, *S, A, x, y, dot, grid, s0, s1, poff, hb, hl, st));
-  } else {
-    PYN_TRY(launch_block<6>(c, *S, A, x, y, dot, grid, s0, s1, poff, hb, hl, st));
-  }
+  PYN_TRY(rc);
   PYN_HIP(hipGetLastError());
-  if (A.br == 1 && A.bc == 1)
-    pyn_product_record(c, c->sell_npat > 0 ? 3 : 2, 0, 0, dot, grid, S->maxw);
-  else
-    pyn_product_record(c, c->sell_npat > 0 ? 5 : 4, A.bc, 0, dot, grid, S->maxw);
+  pyn_product_record(c, P.kind, p1, P.unroll, dot, grid, P.kind == PK_RAW ? 0 : S->maxw);
   if (grid_out) *grid_out = grid;
   return PYN_OK;
 }
 
-int pyn_sell_spmv(pyn_ctx* c, const DMat& A, const double* x, double* y, bool dot, int* grid_out) {
-  const SellShape* S = pyn_sell_shape(c, A);
-  PYN_CHECK(S, "pyn_sell_ensure first");
-  return pyn_sell_spmv_range(c, A, x, y, dot, 0, S->ns, 0, PYN_MAX_PARTIALS, c->stream, grid_out);
+int pyn_sell_spmv(pyn_ctx* c, const DMat& A, const ProductPlan& P, const double* x, double* y, bool dot, int* grid_out) {
+  const int64_t ns = (c->n_owned * A.br + SH - 1) / SH;
+  return pyn_sell_spmv_range2(c, A, P, x, y, dot, 0, ns, ns, ns, 0, PYN_MAX_PARTIALS, c->stream, grid_out);
 }
 
 void pyn_sell_drop_structure(pyn_ctx* c) {

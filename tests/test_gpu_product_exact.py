@@ -2,9 +2,9 @@
 
 Matrices and vectors hold small integers (tests/product_exact.py), so y = A x and the fused dot p.Ap have ONE correct bit pattern
 whatever the summation order: every comparison is `==`.  Each case also asserts, from Context.product_last(), WHICH kernel ran, so
-that a heuristic that moves cannot silently move a test onto another path.  The expected families were read off pyn_sell_ensure /
-pyn_sell_spmv_range2; PYNAMA_SPMV_MAX_GRID=1 makes one workgroup walk every slice, i.e. the persistent loops (and their row-pointer
-prefetch) turn several times at these sizes."""
+that a heuristic that moves cannot silently move a test onto another path.  The expected families were read off product_choose
+(pyn_sell.hip; tests/test_product_exact_host.py asserts them on the host); PYNAMA_SPMV_MAX_GRID=1 makes one workgroup walk every
+slice, i.e. the persistent loops (and their row-pointer prefetch) turn several times at these sizes."""
 import os
 from contextlib import contextmanager
 
@@ -67,7 +67,7 @@ def _setup(ctx, block, fold=None, host_graph=None):
 
 
 def _bcsr_defaults(ex):
-    """lanes per node row and unroll that pyn_sell_spmv_range2 picks without knobs, from the entries per scalar row"""
+    """lanes per node row and unroll that product_choose (pyn_sell.hip) picks without knobs, from the entries per scalar row"""
     avg = ex.colidx.size * ex.bc / (ex.rowptr.size - 1)
     return (16 if avg >= 56.0 else 8), (8 if avg >= 24.0 else 4)
 
