@@ -308,6 +308,33 @@ int pyn_product_last(pyn_ctx* ctx, int64_t* info);
 int pyn_product_choose(int br, int bc, int npat, int maxw, int64_t nnzb, int64_t n_owned, int rhs_compact, int solver, int image,
                        int sell_image, int block_sell, int no_csrlb, int no_sell, double bcsr_min_avg, int bcsr_lanes, int bcsr_unroll,
                        int* kind, int* W, int* lanes, int* unroll);
+/* Which kernel family the context's most recent numeric assembly ran (pyn_assemble_kle, pyn_assemble_kle_noslip, pyn_assemble_scalar,
+ * pyn_assemble_operator): a host-side record of what was launched, for tests and diagnostics (no counterpart in the reference).
+ * info[8]:
+ *   [0] kind, the library's AssemblyKind: 0 AK_NONE nothing assembled yet, 1 AK_GENERIC assemble_generic_kernel and its high-order
+ *       staged / MFMA variants, 2 AK_P1 assemble_p1_laplace_kernel, 3 AK_PATCH the patch-plan kernels (Q1 hex scalar, P1 tets, KLE
+ *       tiled, and their affine forms), 4 AK_LATTICE assemble_q1_hex_lattice_kernel, 5 AK_MARCH assemble_q1_hex_march_kernel,
+ *       6 AK_KLE_LATTICE assemble_q1_hex_kle_lattice_kernel, 7 AK_ROWRUN assemble_ho3_lattice_kernel (K, Rw, Laplacian, operators)
+ *   [1] tile / shape id as PYNAMA_LATTICE_TILE (0..9), PYNAMA_MARCH_TILE (0..14), PYNAMA_KLE_LATTICE_TILE (0..4) number them (an id
+ *       the table does not number: 0, its default shape; the general-geometry KLE lattice kernel has one shape, 0); rows per run
+ *       of AK_ROWRUN; else 0
+ *   [2] 1: the K target (A of a scalar form, M of an operator) took the closed forms of affine cells; 0: quadrature, or no K target
+ *   [3] the same for the Rw target
+ *   [4] AK_GENERIC: 1 64 threads per element, 2 256 threads with the point data in LDS, 3 ... in global scratch, 4 ... and the Gauss
+ *       points staged through LDS, 5 the FP64 matrix cores; else 0
+ *   [5] 1 when a compact Krhs / Arhs was completed through the generic kernel over the elements with an imposed node
+ *   [6] 1 when 1 / diagonal was written with the rows
+ *   [7] assemblies of this context so far */
+int pyn_assemble_last(pyn_ctx* ctx, int64_t* info);
+/* The rule that picks the family (host only: no context, no device, no environment) -- what every assembly applies, once, to its
+ * request, the facts of the context and the PYNAMA_* switches of the moment.  The three arrays hold plain integers in the order
+ * pyn_assemble_choose_layout writes into buf ("request:a,b,..;facts:..;knobs:.."): request = form, variant, which of K / Krhs / Rw /
+ * Rd are asked for, whether Krhs is compact, rule and term count of an operator; facts = mesh, tables, views and patch plans
+ * (mesh_affine, lat_std_ok, ho3_affine: 1 yes, 0 no, -1 not checked); knobs = flags 0 / 1 and integers, negative = not set.
+ * out[8]: [0]..[3] as pyn_assemble_last, [4] the generic sub-variant, [5] 1: a compact Krhs is left to the completion pass,
+ * [6] 1: 1 / diagonal is emitted, [7] 1: the request is one PYNAMA_HO3_REQUIRE insists on AK_ROWRUN for. */
+int pyn_assemble_choose(const int64_t* request, const int64_t* facts, const int64_t* knobs, int64_t* out);
+int pyn_assemble_choose_layout(char* buf, int len);
 /* Matrix-free operators: y = A x WITHOUT an assembled matrix (PETSc analogue: a MATSHELL).  Element matrices are recomputed
  * on the fly (Spectral.getElemKLEMatrices, spectral.py:120-153) and applied per element; needs a structured mesh, errors otherwise:
  *   Q1 hexahedra (pyn_mesh_topology == lattice)            both operators

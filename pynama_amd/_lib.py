@@ -18,7 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 
 # enums of include/pynama_hip.h
 Q_FULL, Q_RED, Q_NODAL = 0, 1, 2
-FORM_LAPLACE, FORM_MASS_NODAL, FORM_MASS_FULL, FORM_KLE = 0, 1, 2, 3
+FORM_LAPLACE, FORM_MASS_NODAL, FORM_MASS_FULL, FORM_KLE, FORM_OPERATOR = 0, 1, 2, 3, 4
 KSP_CG, KSP_GMRES = 0, 1
 MATFREE_OFF, MATFREE_LAPLACE, MATFREE_KLE = 0, 1, 2
 PC_NONE, PC_JACOBI, PC_MG = 0, 1, 2
@@ -121,6 +121,9 @@ SIGNATURES = {
     "pyn_spmv": [_P, _I, _I, _I],
     "pyn_product_last": [_P, _pi64],
     "pyn_product_choose": [_I] * 4 + [_L, _L] + [_I] * 7 + [_D, _I, _I] + [C.POINTER(_I)] * 4,
+    "pyn_assemble_last": [_P, _pi64],
+    "pyn_assemble_choose": [_pi64, _pi64, _pi64, _pi64],
+    "pyn_assemble_choose_layout": [C.c_char_p, _I],
     "pyn_matfree_apply": [_P, _I, _I, _I],
     "pyn_matfree_set": [_P, _I, _D, _D],
     "pyn_solve": [_P, _I, _I, _I, C.POINTER(SolveOpts), C.POINTER(SolveInfo)],
@@ -226,6 +229,36 @@ def product_choose(br, bc, npat, maxw, nnzb, n_owned, rhs_compact=False, solver=
         int(block_sell), int(no_csrlb), int(no_sell), -1.0 if bcsr_min_avg is None else float(bcsr_min_avg),
         -1 if bcsr_lanes is None else int(bcsr_lanes), -1 if bcsr_unroll is None else int(bcsr_unroll), *(C.byref(o) for o in out)))
     return tuple(o.value for o in out)
+
+
+ASSEMBLY_KINDS = ("none", "generic", "p1", "patch", "lattice", "march", "kle_lattice", "rowrun")
+AK_NONE, AK_GENERIC, AK_P1, AK_PATCH, AK_LATTICE, AK_MARCH, AK_KLE_LATTICE, AK_ROWRUN = range(8)
+_ASM_LAST_KEYS = ("kind", "shape", "k_closed", "rw_closed", "generic", "krhs_completed", "dinv", "count")
+
+
+def assemble_choose_layout():
+    """{'request': names, 'facts': names, 'knobs': names}: the order of the three integer arrays of pyn_assemble_choose"""
+    buf = C.create_string_buffer(4096)
+    _check(load_library().pyn_assemble_choose_layout(buf, len(buf)))
+    return {part.split(":")[0]: tuple(n for n in part.split(":")[1].split(",") if n) for part in buf.value.decode().split(";")}
+
+
+def assemble_choose(request, facts, knobs=None):
+    """The kernel family the library would resolve for an assembly request (dict: form, variant, K, Krhs, Rw, Rd, krhs_compact,
+    op_rule, op_nterms; variant defaults to 1, the rest to 0) on a context with these facts (dict, missing = 0) under these knobs
+    (dict, missing = not set; flags True / 1).  No device needed.  Returns the slots 'kind' .. 'dinv' of Context.assemble_last()
+    ('krhs_completed': left to the completion pass) + 'rowrun_candidate'."""
+    layout = assemble_choose_layout()
+    given = {"request": dict({"variant": 1}, **request), "facts": dict(facts), "knobs": dict(knobs or {})}
+    arrays = {}
+    for part, names in layout.items():
+        unknown = set(given[part]) - set(names)
+        if unknown:
+            raise PynamaHipError(f"assemble_choose: unknown {part} {sorted(unknown)}")
+        arrays[part] = np.array([int(given[part].get(n, -1 if part == "knobs" else 0)) for n in names], np.int64)
+    out = np.zeros(8, np.int64)
+    _check(load_library().pyn_assemble_choose(arrays["request"], arrays["facts"], arrays["knobs"], out))
+    return dict({k: int(v) for k, v in zip(_ASM_LAST_KEYS[:7], out)}, rowrun_candidate=int(out[7]))
 
 
 class _stdout_to_stderr:
@@ -603,6 +636,13 @@ class Context:
         _check(self.lib.pyn_product_last(self.h, info))
         keys = ("family", "param", "unroll", "dot", "grid", "npat", "maxw", "launches")
         return {k: int(v) for k, v in zip(keys, info)}
+
+    def assemble_last(self):
+        """what the most recent numeric assembly of this context launched: {'kind' (index into ASSEMBLY_KINDS), 'shape' (tile id, or
+        rows per run), 'k_closed', 'rw_closed', 'generic' (sub-variant), 'krhs_completed', 'dinv', 'count' (running count)}"""
+        info = np.zeros(8, np.int64)
+        _check(self.lib.pyn_assemble_last(self.h, info))
+        return {k: int(v) for k, v in zip(_ASM_LAST_KEYS, info)}
 
     def mesh_ho_lattice(self):
         """(ngl, nx, ny, nz) when the mesh is a box lattice of order ngl >= 4 that the matrix-free KLE operator accepts

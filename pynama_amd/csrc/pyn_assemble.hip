@@ -11,6 +11,8 @@
 //   Rw[(a,p),(b,k)] = sum_full c H_a curlsel(p,k;G_b) + sum_red alpha_w c curlsel(k,p;G_a)^T H_b
 //   Rd[(a,p), b   ] = -sum_full c H_a G_pb + sum_red alpha_d c G_pa H_b
 // where curlsel encodes (curl w)_p = eps_pmk d_m w_k (3D) and (d_y w, -d_x w) (2D).
+#include <cstring>
+
 #include "pyn_internal.h"
 
 namespace {
@@ -941,13 +943,43 @@ __global__ void __launch_bounds__(256) assemble_kle_ho_mfma_kernel(AsmArgs A, in
   }
 }
 
-size_t generic_smem(const pyn_ctx* c, int ngt, bool pt_lds) {
-  size_t s = (size_t)c->nc * c->dim * sizeof(double) + (size_t)((c->nn + 1) & ~1) * sizeof(int32_t);
-  if (pt_lds) s += (size_t)ngt * (c->dim * c->dim + 1 + c->dim * c->nn) * sizeof(double);
+size_t generic_smem(int dim, int nn, int nc, int ngt, bool pt_lds) {
+  size_t s = (size_t)nc * dim * sizeof(double) + (size_t)((nn + 1) & ~1) * sizeof(int32_t);
+  if (pt_lds) s += (size_t)ngt * (dim * dim + 1 + dim * nn) * sizeof(double);
   return s;
 }
 
+// Which form of the generic kernel an element of nn nodes with ngt points in flight takes (AsmPlan::generic): 1 64 threads, 2 256
+// threads with the point data in LDS, 3 ... in global scratch, 4 ... and the Gauss points staged through LDS in chunks of `ch`
+// (high-order KLE elements; stageable: plain KLE targets of an assembly), 5 the FP64 matrix cores with chunks of `ch_mfma`
+struct GenericPick {
+  int sub = 0, ch = 0, ch_mfma = 0;
+  bool pt_lds = false;
+};
+GenericPick generic_pick(int dim, int nn, int nc, int ngt, bool stageable, const AsmKnobs& k) {
+  GenericPick g;
+  g.pt_lds = (size_t)ngt * (dim * dim + 1 + dim * nn) * sizeof(double) <= 40 * 1024;
+  if (stageable && !g.pt_lds && !k.no_ho) {
+    const size_t cs = (size_t)((dim * nn + nn + 1 + 1) & ~1) * sizeof(double);
+    g.ch = (int)std::max<size_t>(1, std::min<size_t>(16, (48 * 1024) / cs));
+  }
+  if (g.ch > 0 && nn >= 48 && !k.no_ho_mfma) {
+    // dense enough for the FP64 matrix cores: largest chunk of points (multiple of 4) whose staging fits the LDS
+    const size_t nn16 = (size_t)((nn + 15) & ~15);
+    for (int q = 16; q >= 4 && !g.ch_mfma; q -= 4)
+      if (generic_smem(dim, nn, nc, ngt, false) + ((size_t)(dim + 1) * q * nn16 + q) * sizeof(double) <= 96 * 1024) g.ch_mfma = q;
+  }
+  g.sub = g.ch_mfma ? 5 : (nn <= 8 ? 1 : (g.pt_lds ? 2 : (g.ch ? 4 : 3)));
+  return g;
+}
+
+int ngt_of(const int* ngp, int form, int op_rule) {
+  const int qa = form == PYN_FORM_OPERATOR ? op_rule : (form == PYN_FORM_MASS_NODAL ? 2 : 0);
+  return ngp[qa] + (form == PYN_FORM_KLE ? ngp[1] : 0);
+}
+
 int fill_args(pyn_ctx* c, AsmArgs& A, int form) {
+  A = AsmArgs();   // no mask, no target, no subset, no scratch
   A.conn = c->d_conn;
   A.xyz = c->d_xyz;
   A.n_elem = c->n_elem;
@@ -964,20 +996,7 @@ int fill_args(pyn_ctx* c, AsmArgs& A, int form) {
   }
   A.rowptr = c->d_rowptr;
   A.colidx = c->d_colidx;
-  A.bcmask = nullptr;
   A.form = form;
-  A.alpha_d = A.alpha_w = 0.0;
-  A.K = A.Krhs = A.Rw = A.Rd = nullptr;
-  A.Kfs = A.Krhsfs = A.Rwfs = A.Rdfs = nullptr;
-  A.rcrow = A.rcrow_fs = A.esel = nullptr;
-  A.corners = nullptr;
-  A.out0 = A.out1 = A.out2 = nullptr;
-  A.gscratch = nullptr;
-  A.gscratch_stride = 0;
-  A.ho_chunk = 0;
-  A.op_rule = A.op_br = A.op_bc = A.op_nterms = 0;
-  A.op_terms = nullptr;
-  A.op_coef = nullptr;
   if (form == PYN_FORM_OPERATOR) return PYN_OK;  // rule checked by the caller
   const int qa = form == PYN_FORM_MASS_NODAL ? 2 : 0;
   PYN_CHECK(c->quad[qa].ngp > 0, "element tables for rule %d not set", qa);
@@ -986,53 +1005,39 @@ int fill_args(pyn_ctx* c, AsmArgs& A, int form) {
 }
 
 template <bool DENSE>
-int launch_generic(pyn_ctx* c, AsmArgs& A, int64_t n_work) {
-  const int qa = A.form == PYN_FORM_OPERATOR ? A.op_rule : (A.form == PYN_FORM_MASS_NODAL ? 2 : 0);
-  const int ngt = A.ngp[qa] + (A.form == PYN_FORM_KLE ? A.ngp[1] : 0);
+int launch_generic(pyn_ctx* c, const AsmKnobs& k, AsmArgs& A, int64_t n_work, int* sub = nullptr) {
+  const int ngt = ngt_of(A.ngp, A.form, A.op_rule);
   const size_t pt_bytes = (size_t)ngt * (c->dim * c->dim + 1 + c->dim * c->nn) * sizeof(double);
-  const bool pt_lds = pt_bytes <= 40 * 1024;
+  const bool stageable = !DENSE && A.form == PYN_FORM_KLE && !A.Kfs && !A.Krhsfs && !A.Rwfs && !A.Rdfs;
+  const GenericPick g = generic_pick(c->dim, c->nn, c->nc, ngt, stageable, k);
+  if (sub) *sub = g.sub;
   const bool small = c->nn <= 8;
   int grid = (int)std::min<int64_t>(n_work, small ? 256 * 32 : 256 * 4);
-  if (!pt_lds) {
+  if (!g.pt_lds) {
     A.gscratch_stride = (int64_t)(pt_bytes / sizeof(double));
     PYN_TRY(pyn_ensure_work(c, (size_t)grid * pt_bytes));
     A.gscratch = c->d_work;
   }
-  size_t smem = generic_smem(c, ngt, pt_lds);
-  // high-order KLE elements (point data in global scratch): stage the Gauss points through LDS, see the kernel
-  if (!DENSE && !pt_lds && A.form == PYN_FORM_KLE && !A.Kfs && !A.Krhsfs && !A.Rwfs && !A.Rdfs && !getenv("PYNAMA_NO_HO")) {
+  size_t smem = generic_smem(c->dim, c->nn, c->nc, ngt, g.pt_lds);
+  if (g.ch > 0) {   // high-order KLE elements (point data in global scratch): stage the Gauss points through LDS, see the kernel
     const size_t cs = (size_t)((c->dim * c->nn + c->nn + 1 + 1) & ~1) * sizeof(double);
-    const int ch = (int)std::max<size_t>(1, std::min<size_t>(16, (48 * 1024) / cs));
-    PYN_CHECK(smem + ch * cs <= 160 * 1024, "element too large for the high-order staging buffer");
-    A.ho_chunk = ch;
-    smem += ch * cs;
+    PYN_CHECK(smem + g.ch * cs <= 160 * 1024, "element too large for the high-order staging buffer");
+    A.ho_chunk = g.ch;
+    smem += g.ch * cs;
   }
-  if (A.ho_chunk > 0 && c->nn >= 48 && !getenv("PYNAMA_NO_HO_MFMA")) {
-    // dense enough for the FP64 matrix cores: largest chunk of points (multiple of 4) whose staging fits the LDS
+  if (g.ch_mfma > 0) {
     const size_t nn16 = (size_t)((c->nn + 15) & ~15);
-    const size_t fixed = generic_smem(c, ngt, false);
-    int ch = 0;
-    for (int k = 16; k >= 4; k -= 4)
-      if (fixed + ((size_t)(c->dim + 1) * k * nn16 + k) * sizeof(double) <= 96 * 1024) {
-        ch = k;
-        break;
-      }
-    if (ch > 0) {
-      const size_t lds = fixed + ((size_t)(c->dim + 1) * ch * nn16 + ch) * sizeof(double);
-      PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_kle_ho_mfma_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      assemble_kle_ho_mfma_kernel<<<grid, 256, lds, c->stream>>>(A, ch);
-      PYN_HIP(hipGetLastError());
-      return PYN_OK;
-    }
+    const size_t lds = generic_smem(c->dim, c->nn, c->nc, ngt, false) + ((size_t)(c->dim + 1) * g.ch_mfma * nn16 + g.ch_mfma) * sizeof(double);
+    // (a size that follows the element: set at every launch, another context of the device may have set less)
+    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_kle_ho_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    assemble_kle_ho_mfma_kernel<<<grid, 256, lds, c->stream>>>(A, g.ch_mfma);
+    PYN_HIP(hipGetLastError());
+    return PYN_OK;
   }
-  if (smem > 64 * 1024) {
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_generic_kernel<256, false, DENSE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-  }
+  if (smem > 64 * 1024) PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_generic_kernel<256, false, DENSE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
   if (small) {
     assemble_generic_kernel<64, true, DENSE><<<grid, 64, smem, c->stream>>>(A);
-  } else if (pt_lds) {
+  } else if (g.pt_lds) {
     assemble_generic_kernel<256, true, DENSE><<<grid, 256, smem, c->stream>>>(A);
   } else {
     assemble_generic_kernel<256, false, DENSE><<<grid, 256, smem, c->stream>>>(A);
@@ -1041,22 +1046,192 @@ int launch_generic(pyn_ctx* c, AsmArgs& A, int64_t n_work) {
   return PYN_OK;
 }
 
+// ---- pieces every entry point shares -------------------------------------------------------------------------------------------
+int zero_blocks(pyn_ctx* c, double* val, int64_t blocks, int br, int bc) {
+  if (val) PYN_HIP(hipMemsetAsync(val, 0, (size_t)blocks * br * bc * sizeof(double), c->stream));
+  return PYN_OK;
+}
+
+// identity rows / zero rows of the imposed DOFs in K (and Kfs), Krhs (and Krhsfs)
+void launch_bc_identity(pyn_ctx* c, int ndof, double* K, double* Krhs, double* Kfs, double* Krhsfs, const int32_t* rcrow,
+                        const int32_t* rcrow_fs) {
+  const int64_t n = c->n_owned * ndof;
+  const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  bc_identity_kernel<<<grid, 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, c->d_bcmask, c->n_owned, ndof, K, Krhs, Kfs, Krhsfs, rcrow, rcrow_fs);
+}
+
+// end of the timed numeric phase (it began with the record of c->ev0) + the record pyn_assemble_last reports
+int asm_finish(pyn_ctx* c, const AsmPlan& P, const AsmRequest& rq) {
+  PYN_HIP(hipEventRecord(c->ev1, c->stream));
+  PYN_HIP(hipStreamSynchronize(c->stream));
+  float ms = 0;
+  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  c->timers[PYN_T_ASSEMBLE] = ms;
+  const int64_t r[7] = {P.kind, P.shape, P.k_closed, P.rw_closed, P.kind == AK_GENERIC ? rq.generic : 0, rq.krhs_completed, rq.dinv_written};
+  std::copy(r, r + 7, c->asm_last);
+  c->asm_last[7] += 1;
+  return PYN_OK;
+}
+
+// ---- the choice ------------------------------------------------------------------------------------------------------------------
+// The static halves of the three structured families: what must hold before the device facts they read are worth gathering
+// (asm_facts) and before they can be chosen (asm_choose).
+bool rowrun_asked(const AsmRequest& rq) {   // K (+ Krhs, Rw) or Rw alone of the KLE form, the scalar Laplacian
+  if (rq.variant == 0 || rq.Rd) return false;
+  return rq.form == PYN_FORM_KLE ? rq.K || (rq.Rw && !rq.Krhs) : rq.form == PYN_FORM_LAPLACE && rq.K && !rq.Rw;
+}
+bool rowrun_static(const AsmRequest& rq, const AsmFacts& f, const AsmKnobs& k) {
+  if (!f.ho3_valid || f.ho3_tabs_nn != f.nn || f.ngp0 < 1) return false;
+  if (rq.form == PYN_FORM_OPERATOR)
+    return rq.op_rule == PYN_Q_NODAL && f.ho3_tabs_ok2 && rq.op_nterms <= PYN_HO3_MAX_TERMS && !k.no_ho3_operator;
+  return rowrun_asked(rq) && f.ho3_tabs_ok0 && !(f.ngl == 2 && f.dim == 3) && (rq.form != PYN_FORM_KLE || f.ho3_tabs_ok1);
+}
+bool lattice_static(const AsmRequest& rq, const AsmFacts& f) {
+  return rq.variant != 0 && rq.form == PYN_FORM_LAPLACE && rq.K && !rq.Rw && !rq.Rd && f.lat_valid && !f.plan0_user && f.ngp0 == 8;
+}
+bool kle_lattice_static(const AsmRequest& rq, const AsmFacts& f, const AsmKnobs& k) {   // (Rw alone is a legal request of the ABI)
+  return rq.variant != 0 && rq.form == PYN_FORM_KLE && (rq.K || (rq.Rw && !rq.Krhs)) && !rq.Rd && !f.plan1_user && f.lat_valid &&
+         f.ngp0 == 8 && f.ngp1 == 1 && !k.no_kle_lattice;
+}
+// the patch-plan kernels fit the request and the element (a plan is another matter)
+bool patch_static(const AsmRequest& rq, const AsmFacts& f, const AsmKnobs& k) {
+  if (rq.variant == 0 || !rq.K || rq.Rd || f.dim != 3) return false;
+  if (rq.form == PYN_FORM_KLE) return f.nn == 8 && f.ngp0 == 8 && f.ngp1 == 1;
+  return rq.form == PYN_FORM_LAPLACE && !rq.Rw && ((f.nn == 4 && f.const_grad && !k.no_p1_tiled) || (f.nn == 8 && f.ngp0 == 8));
+}
+int table_id(int id, int last) { return id >= 1 && id <= last ? id : 0; }   // ids a PYNAMA_*_TILE table does not number: its default arm
+
 }  // namespace
 
-int pyn_assemble_q1_tiled(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw,
-                          double* Rd, bool* handled);
+#define PYN_F(f, e) k.f = getenv(e) != nullptr;
+// (negative stands for "not set" where being set matters -- d < 0: a negative value that IS set reads as 0, which every such switch
+// treats as that value: the default arm of a tile table, at least one workgroup)
+#define PYN_I(f, e, d) \
+  if (const char* v = getenv(e)) k.f = d < 0 ? std::max(atoi(v), 0) : atoi(v);
+AsmKnobs asm_knobs() { AsmKnobs k; PYN_ASM_KNOBS(PYN_F, PYN_I) return k; }
+AsmKnobs lat_fill_knobs() { AsmKnobs k; PYN_LAT_FILL_KNOBS(PYN_F, PYN_I) return k; }
+#undef PYN_F
+#undef PYN_I
+
+// Today's cascade, once: row-run view -> lattice / march -> KLE lattice -> patch plan -> P1 -> generic.  Host only.
+AsmPlan asm_choose(const AsmRequest& rq, const AsmFacts& f, const AsmKnobs& k) {
+  AsmPlan P;
+  const bool kle = rq.form == PYN_FORM_KLE, op = rq.form == PYN_FORM_OPERATOR;
+  const bool aff = f.mesh_affine == 1 && !k.no_affine;   // every element a parallelepiped and the shortcut tables in use
+  P.rowrun_candidate = f.ho3_valid && rowrun_asked(rq);
+  if (rowrun_static(rq, f, k) && f.ho3_affine == 1 && !k.no_ho3_lattice) {
+    P.kind = AK_ROWRUN;
+    P.shape = pyn_ho3_run_length(f.dim, f.ngl, op, k.ho3_run);
+    P.k_closed = rq.K != nullptr;
+    P.rw_closed = rq.Rw != nullptr;
+    return P;
+  }
+  const bool compact = rq.Krhs && rq.rcrow;   // lattice, march and patch kernels cannot address a compact target: krhs_pending
+  if (lattice_static(rq, f)) {
+    P.krhs_pending = compact;
+    P.k_closed = aff && f.aff_standard;
+    P.dinv = !k.no_dinv;
+    if (!P.k_closed && f.q1_gauss_standard && f.lat_std_ok == 1 && k.lattice_tile < 0 && !k.no_march) {   // general geometry: FP64-bound
+      P.kind = AK_MARCH;
+      P.shape = k.march_tile == 4 ? 0 : table_id(k.march_tile, 14);
+    } else {
+      P.kind = AK_LATTICE;
+      P.shape = table_id(k.lattice_tile >= 0 ? k.lattice_tile : (P.k_closed ? 0 : 1), 9);
+    }
+    return P;
+  }
+  if (kle_lattice_static(rq, f, k)) {
+    const bool affine = aff && f.aff_standard && f.aff_rw_standard;
+    if (affine || (f.q1_gauss_standard && f.q1_red_standard && !k.no_kle_general)) {
+      P.kind = AK_KLE_LATTICE;
+      P.shape = affine ? table_id(k.kle_lattice_tile, 4) : 0;
+      P.kle_general = !affine;
+      P.k_closed = affine && rq.K;
+      P.rw_closed = affine && rq.Rw;
+      return P;
+    }
+  }
+  // a graph without a plan gets the automatic one whenever its elements are the patch kernels' (fitting tables or not, as ever)
+  const bool plan = kle ? f.plan1_present : f.plan0_present;
+  P.want_plan = !plan && !(kle ? f.plan1_unfit : f.plan0_unfit) && rq.variant != 0 && rq.K && !rq.Rd && f.dim == 3 &&
+                (kle ? f.nn == 8 : rq.form == PYN_FORM_LAPLACE && !rq.Rw && (f.nn == 8 || (f.nn == 4 && f.const_grad)));
+  if (patch_static(rq, f, k) && (plan || P.want_plan)) {
+    P.kind = AK_PATCH;
+    P.krhs_pending = compact;
+    if (kle) {
+      P.k_closed = aff && f.aff_standard;
+      P.rw_closed = rq.Rw && aff && f.aff_rw_standard;
+    } else {
+      P.k_closed = f.nn == 8 && aff && f.aff_standard && !k.tiled_ablate && !k.no_lean_plan;
+    }
+    return P;
+  }
+  const int ngp[3] = {f.ngp0, f.ngp1, f.ngp2};
+  if (rq.form == PYN_FORM_LAPLACE && f.nn == f.dim + 1 && f.const_grad && !k.no_p1)
+    P.kind = AK_P1;
+  else
+    P.generic = generic_pick(f.dim, f.nn, f.nc, ngt_of(ngp, rq.form, rq.op_rule), kle, k).sub;
+  return P;
+}
+
+// The facts of the context.  Device work only where the static facts make its reader a candidate: the geometry pre-pass of the row-run
+// kernels (every row-run assembly, part of the timed phase), the two lattice checks and the all-affine check of the patch kernels
+// (cached per mesh / graph; the patch kernels' only once a plan exists, as the automatic plan is built first).
+int asm_facts(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, AsmFacts* f) {
+  f->dim = c->dim;
+  f->nn = c->nn;
+  f->nc = c->nc;
+  f->ngl = c->box.ngl;
+  f->ngp0 = c->quad[0].ngp;
+  f->ngp1 = c->quad[1].ngp;
+  f->ngp2 = c->quad[2].ngp;
+  f->const_grad = c->quad[0].const_grad;
+  f->q1_gauss_standard = c->q1_gauss_standard;
+  f->q1_red_standard = c->q1_red_standard;
+  f->aff_standard = c->aff_standard;
+  f->aff_rw_standard = c->aff_rw_standard;
+  f->lat_valid = c->lat.valid;
+  f->ho3_valid = c->ho3.valid;
+  f->ho3_tabs_nn = c->ho3_tabs_nn;
+  f->ho3_tabs_ok0 = c->ho3_tabs_ok[0];
+  f->ho3_tabs_ok1 = c->ho3_tabs_ok[1];
+  f->ho3_tabs_ok2 = c->ho3_tabs_ok[2];
+  f->plan0_present = c->plan[0].npatch > 0;
+  f->plan1_present = c->plan[1].npatch > 0;
+  f->plan0_user = c->plan[0].user;
+  f->plan1_user = c->plan[1].user;
+  f->plan0_unfit = c->plan_unfit[0] || f->plan_declined;
+  f->plan1_unfit = c->plan_unfit[1] || f->plan_declined;
+  if (rowrun_static(rq, *f, k) && !f->geom_done) {
+    PYN_TRY(pyn_ho3_prepare(c));
+    f->geom_done = true;
+  }
+  f->ho3_affine = c->ho3.affine;
+  const bool kle = rq.form == PYN_FORM_KLE;
+  if (lattice_static(rq, *f) || kle_lattice_static(rq, *f, k)) PYN_TRY(pyn_lattice_checks(c, k));
+  if (patch_static(rq, *f, k) && (kle ? f->plan1_present : f->plan0_present) && !k.no_affine &&
+      (kle ? c->aff_standard || (rq.Rw && c->aff_rw_standard) : c->nn == 8 && c->aff_standard && !k.tiled_ablate && !k.no_lean_plan)) {
+    int all_aff = 0;
+    PYN_TRY(pyn_mesh_all_affine(c, &all_aff));
+  }
+  f->mesh_affine = c->mesh_affine;
+  f->lat_std_ok = c->lat.std_ok;
+  return PYN_OK;
+}
+
+namespace {
 
 // Does the imposed-column matrix `id` already hold zeros wherever the current Dirichlet set leaves zeros (DMat::rhs_clean)?  Read
 // BEFORE mat_ptr marks the matrix as changing.
-static bool rhs_is_clean(pyn_ctx* c, int id) {
-  if (id < 0 || id >= (int)c->mats.size() || !c->mats[id].live || getenv("PYNAMA_RHS_FULL_WRITE")) return false;
+bool rhs_is_clean(pyn_ctx* c, const AsmKnobs& k, int id) {
+  if (id < 0 || id >= (int)c->mats.size() || !c->mats[id].live || k.rhs_full_write) return false;
   const int64_t s = c->mats[id].rhs_clean;
   return s == PYN_RHS_ANY || s == c->bc_stamp;
 }
 
 // crow != null: the argument may be a compact imposed-column matrix (Krhs, Krhsfs, Arhs); its row selection is brought to the current
 // Dirichlet set (values zeroed when it had to be rebuilt) and handed back, null for a matrix with the graph's full pattern
-static int mat_ptr(pyn_ctx* c, int id, int br, int bc, const char* name, double** out, const int32_t** crow = nullptr) {
+int mat_ptr(pyn_ctx* c, int id, int br, int bc, const char* name, double** out, const int32_t** crow = nullptr) {
   *out = nullptr;
   if (crow) *crow = nullptr;
   if (id < 0) return PYN_OK;
@@ -1074,98 +1249,107 @@ static int mat_ptr(pyn_ctx* c, int id, int br, int bc, const char* name, double*
 }
 
 // blocks stored by the matrix behind a raw value pointer of this assembly (the compact Krhs target, or the graph's count)
-static int64_t rhs_blocks(const pyn_ctx* c, int id) { return id >= 0 ? pyn_mat_blocks(c, c->mats[id]) : c->nnzb; }
+int64_t rhs_blocks(const pyn_ctx* c, int id) { return id >= 0 ? pyn_mat_blocks(c, c->mats[id]) : c->nnzb; }
 
-static int run_assembly(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw,
-                        double* Rd, int variant, int64_t krhs_blocks) {
+// The actor: facts, choice, one switch onto the launchers, completion of a compact Krhs, record.  op_terms / op_coef: the device
+// copies of an operator's terms.
+int asm_run(pyn_ctx* c, AsmRequest& rq, const AsmKnobs& k, const int32_t* op_terms = nullptr, const double* op_coef = nullptr) {
   PYN_CHECK(c->d_rowptr, "pyn_csr_symbolic first");
-  const int ndof = form == PYN_FORM_KLE ? c->dim : 1;
-  if (c->d_bcmask) PYN_CHECK(c->bc_ndof == ndof, "bc mask has ndof=%d, form needs %d", c->bc_ndof, ndof);
+  const bool kle = rq.form == PYN_FORM_KLE, op = rq.form == PYN_FORM_OPERATOR;
+  const int ndof = kle ? c->dim : 1, dw = c->dim == 2 ? 1 : 3;
+  if (c->d_bcmask && !op) PYN_CHECK(c->bc_ndof == ndof, "bc mask has ndof=%d, form needs %d", c->bc_ndof, ndof);
   AsmArgs A;
-  PYN_TRY(fill_args(c, A, form));
-  A.bcmask = c->d_bcmask;
-  A.alpha_d = alpha_d;
-  A.alpha_w = alpha_w;
-  A.K = K;
-  A.Krhs = Krhs;
-  A.Rw = Rw;
-  A.Rd = Rd;
-  A.rcrow = c->asm_rcrow;
+  PYN_TRY(fill_args(c, A, rq.form));
+  A.bcmask = op ? nullptr : c->d_bcmask;
+  A.alpha_d = rq.alpha_d;
+  A.alpha_w = rq.alpha_w;
+  A.K = rq.K;
+  A.Krhs = rq.Krhs;
+  A.Rw = rq.Rw;
+  A.Rd = rq.Rd;
+  A.rcrow = rq.rcrow;
+  A.op_rule = rq.op_rule;
+  A.op_br = rq.op_br;
+  A.op_bc = rq.op_bc;
+  A.op_nterms = rq.op_nterms;
+  A.op_terms = op_terms;
+  A.op_coef = op_coef;
   PYN_HIP(hipEventRecord(c->ev0, c->stream));
-  bool handled = false;
-  c->asm_krhs_pending = false;
-  if (variant != 0) PYN_TRY(pyn_assemble_q1_tiled(c, form, alpha_d, alpha_w, K, Krhs, Rw, Rd, &handled));
-  if (handled && c->asm_krhs_pending) {
+  AsmFacts f;
+  AsmPlan P;
+  for (;;) {   // the one loop-back: the patch kernels' turn without a plan builds the automatic one, which may not fit (or be switched off)
+    PYN_TRY(asm_facts(c, rq, k, &f));
+    P = asm_choose(rq, f, k);
+    if (!P.want_plan) break;
+    PYN_TRY(pyn_patch_plan_default(c, kle));
+    f.plan_declined = !c->plan[kle].npatch;
+  }
+  PYN_CHECK(!(k.ho3_require && P.rowrun_candidate && P.kind != AK_ROWRUN),
+            "PYNAMA_HO3_REQUIRE: the ngl = 3 lattice kernels declined this assembly (non-affine cell or tables missing)");
+  switch (P.kind) {
+    case AK_ROWRUN: PYN_TRY(pyn_assemble_ho3_lattice(c, rq, k, P)); break;   // no atomics, every row written once
+    case AK_LATTICE:
+    case AK_MARCH: PYN_TRY(pyn_assemble_lattice(c, rq, k, P)); break;
+    case AK_KLE_LATTICE: PYN_TRY(pyn_assemble_kle_lattice(c, rq, k, P)); break;
+    case AK_PATCH: PYN_TRY(pyn_assemble_patch(c, rq, k, P)); break;
+    default: {   // scatter-add path: values start from zero (the other families write every entry themselves)
+      const int br = op ? rq.op_br : ndof, bc = op ? rq.op_bc : ndof;
+      PYN_TRY(zero_blocks(c, rq.K, c->nnzb, br, bc));
+      PYN_TRY(zero_blocks(c, rq.Krhs, rq.krhs_blocks, ndof, ndof));
+      PYN_TRY(zero_blocks(c, rq.Rw, c->nnzb, ndof, dw));
+      PYN_TRY(zero_blocks(c, rq.Rd, c->nnzb, ndof, 1));
+      if (P.kind == AK_P1) {
+        const QuadTab& q0 = c->quad[0];
+        const auto p1 = c->dim == 3 ? assemble_p1_laplace_kernel<3> : assemble_p1_laplace_kernel<2>;
+        p1<<<(int)((c->n_elem + 255) / 256), 256, 0, c->stream>>>(c->d_conn, c->d_xyz, c->n_elem, c->n_owned, c->d_rowptr, c->d_colidx,
+                                                                   c->d_bcmask, q0.Hrs, q0.wsum, rq.K, rq.Krhs, rq.rcrow);
+        PYN_HIP(hipGetLastError());
+      } else {
+        PYN_TRY(launch_generic<false>(c, k, A, c->n_elem, &rq.generic));
+      }
+      if (!op && c->d_bcmask && (rq.K || rq.Krhs)) launch_bc_identity(c, ndof, rq.K, rq.Krhs, nullptr, nullptr, rq.rcrow, nullptr);
+    }
+  }
+  if (P.krhs_pending) {
     // the kernel family that took K cannot address a compact Krhs: -K_e[free, bc] comes from the elements that hold an imposed node
     // (a few per cent of the mesh) through the generic kernel, into the zeroed compact matrix
     PYN_TRY(pyn_bc_elements(c));
-    PYN_HIP(hipMemsetAsync(Krhs, 0, (size_t)krhs_blocks * ndof * ndof * sizeof(double), c->stream));
+    PYN_TRY(zero_blocks(c, rq.Krhs, rq.krhs_blocks, ndof, ndof));
     if (c->n_esel > 0) {
       AsmArgs B = A;
       B.K = B.Rw = B.Rd = nullptr;
       B.esel = c->d_esel;
       B.n_elem = c->n_esel;
-      PYN_TRY(launch_generic<false>(c, B, c->n_esel));
+      PYN_TRY(launch_generic<false>(c, k, B, c->n_esel));
     }
-    if (c->d_bcmask) {
-      int64_t n = c->n_owned * ndof;
-      int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-      bc_identity_kernel<<<grid, 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, c->d_bcmask, c->n_owned, ndof, nullptr, Krhs, nullptr, nullptr,
-                                                    c->asm_rcrow, nullptr);
-    }
-    c->asm_krhs_pending = false;
+    if (c->d_bcmask) launch_bc_identity(c, ndof, nullptr, rq.Krhs, nullptr, nullptr, rq.rcrow, nullptr);
+    rq.krhs_completed = true;
   }
-  if (!handled) {  // scatter-add path: values start from zero (the tiled path writes every entry itself)
-    const int dw = c->dim == 2 ? 1 : 3;
-    const size_t nb = (size_t)c->nnzb * sizeof(double);
-    if (K) PYN_HIP(hipMemsetAsync(K, 0, nb * ndof * ndof, c->stream));
-    if (Krhs) PYN_HIP(hipMemsetAsync(Krhs, 0, (size_t)krhs_blocks * ndof * ndof * sizeof(double), c->stream));
-    if (Rw) PYN_HIP(hipMemsetAsync(Rw, 0, nb * ndof * dw, c->stream));
-    if (Rd) PYN_HIP(hipMemsetAsync(Rd, 0, nb * ndof, c->stream));
-    const QuadTab& q0 = c->quad[0];
-    if (form == PYN_FORM_LAPLACE && c->nn == c->dim + 1 && q0.const_grad && !getenv("PYNAMA_NO_P1")) {
-      const int grid = (int)((c->n_elem + 255) / 256);
-      if (c->dim == 3)
-        assemble_p1_laplace_kernel<3><<<grid, 256, 0, c->stream>>>(c->d_conn, c->d_xyz, c->n_elem, c->n_owned, c->d_rowptr,
-                                                                  c->d_colidx, c->d_bcmask, q0.Hrs, q0.wsum, K, Krhs, c->asm_rcrow);
-      else
-        assemble_p1_laplace_kernel<2><<<grid, 256, 0, c->stream>>>(c->d_conn, c->d_xyz, c->n_elem, c->n_owned, c->d_rowptr,
-                                                                  c->d_colidx, c->d_bcmask, q0.Hrs, q0.wsum, K, Krhs, c->asm_rcrow);
-      PYN_HIP(hipGetLastError());
-    } else {
-      PYN_TRY(launch_generic<false>(c, A, c->n_elem));
-    }
-  }
-  if (!handled && c->d_bcmask && (K || Krhs)) {
-    int64_t n = c->n_owned * ndof;
-    int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    bc_identity_kernel<<<grid, 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, c->d_bcmask, c->n_owned, ndof, K, Krhs, nullptr, nullptr,
-                                                    c->asm_rcrow, nullptr);
-  }
-  PYN_HIP(hipEventRecord(c->ev1, c->stream));
-  PYN_HIP(hipStreamSynchronize(c->stream));
-  float ms = 0;
-  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->timers[PYN_T_ASSEMBLE] = ms;
-  return PYN_OK;
+  return asm_finish(c, P, rq);
 }
+
+}  // namespace
 
 extern "C" int pyn_assemble_kle(pyn_ctx* c, double alpha_d, double alpha_w, int K, int Krhs, int Rw, int Rd, int variant) {
   PYN_CHECK(c, "ctx is NULL");
   PYN_HIP(hipSetDevice(c->device));
   const int dim = c->dim, dw = dim == 2 ? 1 : 3;
-  double *pK, *pKr, *pRw, *pRd;
-  PYN_TRY(mat_ptr(c, K, dim, dim, "K", &pK));
-  c->asm_rhs_clean = Krhs != K && rhs_is_clean(c, Krhs);   // (read before mat_ptr marks the matrix as changing)
-  PYN_TRY(mat_ptr(c, Krhs, dim, dim, "Krhs", &pKr, &c->asm_rcrow));
-  if (c->asm_rcrow) c->asm_rhs_clean = false;              // a compact matrix has no zero blocks to skip: every stored row is written
-  PYN_TRY(mat_ptr(c, Rw, dim, dw, "Rw", &pRw));
-  PYN_TRY(mat_ptr(c, Rd, dim, 1, "Rd", &pRd));
-  const int rc = run_assembly(c, PYN_FORM_KLE, alpha_d, alpha_w, pK, pKr, pRw, pRd, variant, rhs_blocks(c, Krhs));
-  c->asm_rhs_clean = false;
-  c->asm_rcrow = nullptr;
-  if (rc == PYN_OK && pKr && pK) c->mats[Krhs].rhs_clean = c->bc_stamp;   // exactly the imposed-column matrix of this Dirichlet set
-  return rc;
+  const AsmKnobs k = asm_knobs();
+  AsmRequest rq;
+  rq.form = PYN_FORM_KLE;
+  rq.variant = variant;
+  rq.alpha_d = alpha_d;
+  rq.alpha_w = alpha_w;
+  PYN_TRY(mat_ptr(c, K, dim, dim, "K", &rq.K));
+  rq.rhs_clean = Krhs != K && rhs_is_clean(c, k, Krhs);   // (read before mat_ptr marks the matrix as changing)
+  PYN_TRY(mat_ptr(c, Krhs, dim, dim, "Krhs", &rq.Krhs, &rq.rcrow));
+  if (rq.rcrow) rq.rhs_clean = false;                     // a compact matrix has no zero blocks to skip: every stored row is written
+  PYN_TRY(mat_ptr(c, Rw, dim, dw, "Rw", &rq.Rw));
+  PYN_TRY(mat_ptr(c, Rd, dim, 1, "Rd", &rq.Rd));
+  rq.krhs_blocks = rhs_blocks(c, Krhs);
+  PYN_TRY(asm_run(c, rq, k));
+  if (rq.Krhs && rq.K) c->mats[Krhs].rhs_clean = c->bc_stamp;   // exactly the imposed-column matrix of this Dirichlet set
+  return PYN_OK;
 }
 
 extern "C" int pyn_assemble_kle_noslip(pyn_ctx* c, double alpha_d, double alpha_w, const int* mat_ids /*[8]*/) {
@@ -1176,67 +1360,99 @@ extern "C" int pyn_assemble_kle_noslip(pyn_ctx* c, double alpha_d, double alpha_
   const int dim = c->dim, dw = dim == 2 ? 1 : 3;
   const int shapes[8][2] = {{dim, dim}, {dim, dim}, {dim, dw}, {dim, 1}, {dim, dim}, {dim, dim}, {dim, dw}, {dim, 1}};
   const char* names[8] = {"K", "Krhs", "Rw", "Rd", "Kfs", "Krhsfs", "Rwfs", "Rdfs"};
-  double* ptr[8];
-  const int32_t* crow[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int k = 0; k < 8; ++k) {
-    const bool rhs = k == 1 || k == 5;       // Krhs, Krhsfs may be compact imposed-column matrices
-    PYN_TRY(mat_ptr(c, mat_ids[k], shapes[k][0], shapes[k][1], names[k], &ptr[k], rhs ? &crow[k] : nullptr));
-    if (ptr[k])
-      PYN_HIP(hipMemsetAsync(ptr[k], 0, (size_t)rhs_blocks(c, mat_ids[k]) * shapes[k][0] * shapes[k][1] * sizeof(double), c->stream));
-  }
   AsmArgs A;
   PYN_TRY(fill_args(c, A, PYN_FORM_KLE));
   A.bcmask = c->d_bcmask;
   A.alpha_d = alpha_d;
   A.alpha_w = alpha_w;
-  A.K = ptr[0];
-  A.Krhs = ptr[1];
-  A.Rw = ptr[2];
-  A.Rd = ptr[3];
-  A.Kfs = ptr[4];
-  A.Krhsfs = ptr[5];
-  A.Rwfs = ptr[6];
-  A.Rdfs = ptr[7];
-  A.rcrow = crow[1];
-  A.rcrow_fs = crow[5];
+  double** const ptr[8] = {&A.K, &A.Krhs, &A.Rw, &A.Rd, &A.Kfs, &A.Krhsfs, &A.Rwfs, &A.Rdfs};
+  const int32_t** const crow[8] = {nullptr, &A.rcrow, nullptr, nullptr, nullptr, &A.rcrow_fs, nullptr, nullptr};   // compact: Krhs, Krhsfs
+  for (int i = 0; i < 8; ++i) {
+    PYN_TRY(mat_ptr(c, mat_ids[i], shapes[i][0], shapes[i][1], names[i], ptr[i], crow[i]));
+    PYN_TRY(zero_blocks(c, *ptr[i], rhs_blocks(c, mat_ids[i]), shapes[i][0], shapes[i][1]));
+  }
+  AsmRequest rq;   // the split has the generic kernel only
   PYN_HIP(hipEventRecord(c->ev0, c->stream));
-  PYN_TRY(launch_generic<false>(c, A, c->n_elem));
-  int64_t n = c->n_owned * dim;
-  int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  bc_identity_kernel<<<grid, 256, 0, c->stream>>>(c->d_rowptr, c->d_colidx, c->d_bcmask, c->n_owned, dim, A.K, A.Krhs, A.Kfs, A.Krhsfs, A.rcrow,
-                                                A.rcrow_fs);
-  PYN_HIP(hipEventRecord(c->ev1, c->stream));
-  PYN_HIP(hipStreamSynchronize(c->stream));
-  float ms = 0;
-  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->timers[PYN_T_ASSEMBLE] = ms;
-  return PYN_OK;
+  PYN_TRY(launch_generic<false>(c, asm_knobs(), A, c->n_elem, &rq.generic));
+  launch_bc_identity(c, dim, A.K, A.Krhs, A.Kfs, A.Krhsfs, A.rcrow, A.rcrow_fs);
+  return asm_finish(c, AsmPlan(), rq);
 }
 
 extern "C" int pyn_assemble_scalar(pyn_ctx* c, int form, int Aid, int Arhs, int variant) {
   PYN_CHECK(c, "ctx is NULL");
   PYN_CHECK(form == PYN_FORM_LAPLACE || form == PYN_FORM_MASS_NODAL || form == PYN_FORM_MASS_FULL, "bad scalar form");
   PYN_HIP(hipSetDevice(c->device));
-  double *pA, *pAr;
-  c->asm_rhs_clean = Arhs != Aid && rhs_is_clean(c, Arhs);
-  PYN_TRY(mat_ptr(c, Aid, 1, 1, "A", &pA));
-  PYN_TRY(mat_ptr(c, Arhs, 1, 1, "Arhs", &pAr, &c->asm_rcrow));
-  if (c->asm_rcrow) c->asm_rhs_clean = false;
+  const AsmKnobs k = asm_knobs();
+  AsmRequest rq;
+  rq.form = form;
+  rq.variant = variant;
+  rq.rhs_clean = Arhs != Aid && rhs_is_clean(c, k, Arhs);
+  PYN_TRY(mat_ptr(c, Aid, 1, 1, "A", &rq.K));
+  PYN_TRY(mat_ptr(c, Arhs, 1, 1, "Arhs", &rq.Krhs, &rq.rcrow));
+  if (rq.rcrow) rq.rhs_clean = false;
+  rq.krhs_blocks = rhs_blocks(c, Arhs);
   // the Jacobi data of A: kernels that see whole rows (lattice store phases) write 1 / diagonal on the way out
-  c->asm_dinv = nullptr;
-  c->asm_dinv_written = false;
-  if (Aid >= 0 && form == PYN_FORM_LAPLACE && !getenv("PYNAMA_NO_ASM_DINV")) {
+  if (Aid >= 0 && form == PYN_FORM_LAPLACE && !k.no_dinv) {
     DMat& m = c->mats[Aid];
     if (!m.dinv) PYN_HIP(hipMalloc((void**)&m.dinv, (size_t)c->n_owned * sizeof(double)));
-    c->asm_dinv = m.dinv;
+    rq.dinv = m.dinv;
   }
-  const int rc = run_assembly(c, form, 0.0, 0.0, pA, pAr, nullptr, nullptr, variant, rhs_blocks(c, Arhs));
-  if (rc == PYN_OK && c->asm_dinv && c->asm_dinv_written) c->mats[Aid].dinv_valid = true;
-  c->asm_dinv = nullptr;
-  c->asm_rhs_clean = false;
-  c->asm_rcrow = nullptr;
-  if (rc == PYN_OK && pAr && pA) c->mats[Arhs].rhs_clean = c->bc_stamp;
-  return rc;
+  PYN_TRY(asm_run(c, rq, k));
+  if (rq.dinv_written) c->mats[Aid].dinv_valid = true;
+  if (rq.Krhs && rq.K) c->mats[Arhs].rhs_clean = c->bc_stamp;
+  return PYN_OK;
+}
+
+extern "C" int pyn_assemble_last(pyn_ctx* c, int64_t* info) {
+  PYN_CHECK(c && info, "NULL argument");
+  std::copy(c->asm_last, c->asm_last + 8, info);
+  return PYN_OK;
+}
+
+// request slots, then the facts and the knobs in the order of their tables in pyn_internal.h
+#define PYN_ASM_REQUEST "form,variant,K,Krhs,Rw,Rd,krhs_compact,op_rule,op_nterms"
+extern "C" int pyn_assemble_choose_layout(char* buf, int len) {
+#define PYN_X(f) #f ","
+#define PYN_F(f, e) #f ","
+#define PYN_I(f, e, d) #f ","
+  const char* layout = "request:" PYN_ASM_REQUEST ";facts:" PYN_ASM_FACTS(PYN_X) ";knobs:" PYN_ASM_KNOBS(PYN_F, PYN_I);
+#undef PYN_X
+#undef PYN_F
+#undef PYN_I
+  PYN_CHECK(buf && len > (int)strlen(layout), "pyn_assemble_choose_layout: the buffer needs %zu bytes", strlen(layout) + 1);
+  strcpy(buf, layout);
+  return PYN_OK;
+}
+
+extern "C" int pyn_assemble_choose(const int64_t* request, const int64_t* facts, const int64_t* knobs, int64_t* out) {
+  PYN_CHECK(request && facts && knobs && out, "pyn_assemble_choose: NULL argument");
+  static double target;
+  static const int32_t crow = 0;
+  AsmRequest rq;
+  rq.form = (int)request[0];
+  rq.variant = (int)request[1];
+  rq.K = request[2] ? &target : nullptr;
+  rq.Krhs = request[3] ? &target : nullptr;
+  rq.Rw = request[4] ? &target : nullptr;
+  rq.Rd = request[5] ? &target : nullptr;
+  rq.rcrow = request[6] ? &crow : nullptr;
+  rq.op_rule = (int)request[7];
+  rq.op_nterms = (int)request[8];
+  AsmFacts f;
+  AsmKnobs k;
+#define PYN_X(m) f.m = (int)*facts++;
+#define PYN_F(m, e) k.m = *knobs++ > 0;
+#define PYN_I(m, e, d) \
+  if (*knobs++ >= 0) k.m = (int)knobs[-1];
+  PYN_ASM_FACTS(PYN_X)
+  PYN_ASM_KNOBS(PYN_F, PYN_I)
+#undef PYN_X
+#undef PYN_F
+#undef PYN_I
+  const AsmPlan P = asm_choose(rq, f, k);
+  const int64_t r[8] = {P.kind, P.shape, P.k_closed, P.rw_closed, P.generic, P.krhs_pending, P.dinv, P.rowrun_candidate};
+  std::copy(r, r + 8, out);
+  return PYN_OK;
 }
 
 extern "C" int pyn_elem_local(pyn_ctx* c, int form, double alpha_d, double alpha_w, const double* corners, double* out0,
@@ -1250,13 +1466,7 @@ extern "C" int pyn_elem_local(pyn_ctx* c, int form, double alpha_d, double alpha
   size_t n1 = kle ? (size_t)dim * nn * dw * nn : 0;
   size_t n2 = kle ? (size_t)dim * nn * nn : 0;
   size_t ncor = (size_t)c->nc * dim;
-  size_t need = (n0 + n1 + n2 + ncor) * sizeof(double);
-  if (need > c->eloc_bytes) {
-    if (c->d_eloc) PYN_HIP(hipFree(c->d_eloc));
-    c->d_eloc = nullptr;
-    PYN_HIP(hipMalloc((void**)&c->d_eloc, need));
-    c->eloc_bytes = need;
-  }
+  PYN_TRY(pyn_grow(&c->d_eloc, &c->eloc_bytes, (n0 + n1 + n2 + ncor) * sizeof(double)));
   double* d_cor = c->d_eloc;
   double* d0 = d_cor + ncor;
   double* d1 = d0 + n0;
@@ -1270,7 +1480,7 @@ extern "C" int pyn_elem_local(pyn_ctx* c, int form, double alpha_d, double alpha
   A.out0 = out0 ? d0 : nullptr;
   A.out1 = (kle && out1) ? d1 : nullptr;
   A.out2 = (kle && out2) ? d2 : nullptr;
-  PYN_TRY(launch_generic<true>(c, A, 1));
+  PYN_TRY(launch_generic<true>(c, asm_knobs(), A, 1));
   if (out0) PYN_HIP(hipMemcpyAsync(out0, d0, n0 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (kle && out1) PYN_HIP(hipMemcpyAsync(out1, d1, n1 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (kle && out2) PYN_HIP(hipMemcpyAsync(out2, d2, n2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1307,28 +1517,17 @@ extern "C" int pyn_assemble_operator(pyn_ctx* c, int rule, int nterms, const int
   int32_t* dt = nullptr;
   double* dc = nullptr;
   PYN_TRY(upload_terms(c, nterms, terms, coef, &dt, &dc));
-  AsmArgs A;
-  PYN_TRY(fill_args(c, A, PYN_FORM_OPERATOR));
-  A.op_rule = rule;
-  A.op_br = M.br;
-  A.op_bc = M.bc;
-  A.op_nterms = nterms;
-  A.op_terms = dt;
-  A.op_coef = dc;
-  A.K = M.val;
+  AsmRequest rq;
+  rq.form = PYN_FORM_OPERATOR;
+  rq.op_rule = rule;
+  rq.op_br = M.br;
+  rq.op_bc = M.bc;
+  rq.op_nterms = nterms;
+  rq.op_terms = terms;
+  rq.op_coef = coef;
+  rq.K = M.val;
   M.touch();
-  PYN_HIP(hipEventRecord(c->ev0, c->stream));
-  bool handled = false;   // structured meshes of parallelepipeds: the row-run kernels (no atomics, every row written once)
-  PYN_TRY(pyn_assemble_ho3_operator(c, rule, M.br, M.bc, nterms, terms, coef, M.val, &handled));
-  if (!handled) {
-    PYN_HIP(hipMemsetAsync(M.val, 0, (size_t)c->nnzb * M.br * M.bc * sizeof(double), c->stream));
-    PYN_TRY(launch_generic<false>(c, A, c->n_elem));
-  }
-  PYN_HIP(hipEventRecord(c->ev1, c->stream));
-  PYN_HIP(hipStreamSynchronize(c->stream));
-  float ms = 0;
-  PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->timers[PYN_T_ASSEMBLE] = ms;
+  PYN_TRY(asm_run(c, rq, asm_knobs(), dt, dc));   // structured meshes of parallelepipeds: the row-run kernels, else scatter-add
   PYN_HIP(hipFree(dt));
   PYN_HIP(hipFree(dc));
   return PYN_OK;
@@ -1340,13 +1539,7 @@ extern "C" int pyn_elem_operator_local(pyn_ctx* c, int rule, int br, int bc, int
   PYN_TRY(check_operator(c, rule, br, bc, nterms, terms, coef));
   PYN_HIP(hipSetDevice(c->device));
   const size_t n0 = (size_t)br * c->nn * bc * c->nn, ncor = (size_t)c->nc * c->dim;
-  const size_t need = (n0 + ncor) * sizeof(double);
-  if (need > c->eloc_bytes) {
-    if (c->d_eloc) PYN_HIP(hipFree(c->d_eloc));
-    c->d_eloc = nullptr;
-    PYN_HIP(hipMalloc((void**)&c->d_eloc, need));
-    c->eloc_bytes = need;
-  }
+  PYN_TRY(pyn_grow(&c->d_eloc, &c->eloc_bytes, (n0 + ncor) * sizeof(double)));
   int32_t* dt = nullptr;
   double* dc = nullptr;
   PYN_TRY(upload_terms(c, nterms, terms, coef, &dt, &dc));
@@ -1361,7 +1554,7 @@ extern "C" int pyn_elem_operator_local(pyn_ctx* c, int rule, int br, int bc, int
   A.op_coef = dc;
   A.corners = c->d_eloc;
   A.out0 = c->d_eloc + ncor;
-  PYN_TRY(launch_generic<true>(c, A, 1));
+  PYN_TRY(launch_generic<true>(c, asm_knobs(), A, 1));
   PYN_HIP(hipMemcpyAsync(out, A.out0, n0 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   PYN_HIP(hipStreamSynchronize(c->stream));
   PYN_HIP(hipFree(dt));

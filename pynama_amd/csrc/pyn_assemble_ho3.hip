@@ -50,7 +50,7 @@ struct LocalOrder {
 };
 
 enum { M_K = 0, M_RW = 1, M_LAP = 2, M_OP = 3 };
-constexpr int MAX_TERMS = 32;
+constexpr int MAX_TERMS = PYN_HO3_MAX_TERMS;
 
 struct Ho3Args {
   int EX, EY, EZ, NX, NY, npl, p_own0, n_own;
@@ -973,9 +973,10 @@ __global__ void ho3_columns_kernel(Ho3Args T, int dim, int ngl, int64_t n_rows, 
   }
 }
 
-void fill_lattice_args(const pyn_ctx* c, Ho3Args& T) {
+void fill_lattice_args(const pyn_ctx* c, const AsmKnobs& k, Ho3Args& T) {
   const BoxLattice& L = c->box;
   const bool d3 = L.dim == 3;
+  T = Ho3Args();   // no Dirichlet bits, no target, no operator terms
   T.EX = L.EX;
   T.EY = d3 ? L.EY : L.EL;   // 2-D: the element rows are the layers, EZ and NY stay 0
   T.EZ = d3 ? L.EL : 0;
@@ -986,43 +987,24 @@ void fill_lattice_args(const pyn_ctx* c, Ho3Args& T) {
   T.n_own = L.n_own;
   T.P = L.d_P;
   T.rowptr = c->d_rowptr;
-  T.nbits = nullptr;
-  T.runflag = nullptr;
   T.geom = c->ho3.d_geom;
   T.tabs = c->d_ho3_tabs;
   T.tabs1d = c->ho3_tens_ok ? c->d_ho3_t1d : nullptr;
-  T.alpha_d = T.alpha_w = 0.0;
-  T.A = T.Arhs = nullptr;
-  T.rhs_clean = 0;
-  T.rcrow = nullptr;
-  T.par_y = T.par_z = 0;
-  T.nruns = T.nly = T.nwork = 0;
-  T.so0 = 0;
-  T.img_len = 0;
   T.step = L.ngl == 3 ? 2 : 1;
-  T.diag = c->ho3.diag == 1 && !getenv("PYNAMA_HO3_NO_DIAG");
-  T.pstd = !getenv("PYNAMA_HO3_NO_PSTD") && L.plane() * L.npl < (int64_t)INT32_MAX && L.slab_order();
-  {
-    const char* ab = getenv("PYNAMA_HO3_ABLATE");
-    T.ablate = ab ? atoi(ab) : 0;
-  }
+  T.diag = c->ho3.diag == 1 && !k.ho3_no_diag;
+  T.pstd = !k.ho3_no_pstd && L.plane() * L.npl < (int64_t)INT32_MAX && L.slab_order();
+  T.ablate = k.ho3_ablate;
   T.obr = T.obc = 1;
-  T.nterms = 0;
 }
 
 template <int DIM, int NGL, int MAT, int R, bool DG>
-int launch_ho3_g(pyn_ctx* c, Ho3Args T) {
+int launch_ho3_g(pyn_ctx* c, const AsmKnobs& k, Ho3Args T) {
   const int BR = MAT == M_OP ? T.obr : (MAT == M_LAP ? 1 : DIM);
   const int BC = MAT == M_OP ? T.obc : (MAT == M_K ? DIM : (MAT == M_RW ? (DIM == 3 ? 3 : 1) : 1));
   const BoxLattice& L = c->box;
   Ho3View& V = c->ho3;
   T.nruns = (L.NX + R - 1) / R;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_ho3_lattice_kernel<DIM, NGL, MAT, R, DG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    attr_done = true;
-  }
+  PYN_TRY(pyn_kernel_lds(c, assemble_ho3_lattice_kernel<DIM, NGL, MAT, R, DG>, 128 * 1024));
   T.runflag = nullptr;
   if (T.nbits) {   // which runs see an imposed DOF: once per Dirichlet set and run length
     if (V.runflag_stamp != c->bc_stamp || V.runflag_R != R) {
@@ -1063,18 +1045,12 @@ int launch_ho3_g(pyn_ctx* c, Ho3Args T) {
       const size_t lds = (size_t)T.img_len * sizeof(double);
       PYN_CHECK(lds <= 128 * 1024, "lattice row-run assembly: %zu B of LDS per run", lds);
       // as many workgroups as the device holds at once; each walks its share of the runs (PYNAMA_HO3_WGS_PER_CU: fewer / more)
-      static size_t occ_lds[4] = {0, 0, 0, 0};
-      static int occ_wgs[4] = {0, 0, 0, 0};
-      const int cls = 2 * pz + py;
-      if (occ_lds[cls] != lds || !occ_wgs[cls]) {
-        PYN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_wgs[cls], assemble_ho3_lattice_kernel<DIM, NGL, MAT, R, DG>, 256, lds));
-        occ_lds[cls] = lds;
-      }
-      int per_cu = std::max(1, occ_wgs[cls]);
-      if (const char* e = getenv("PYNAMA_HO3_WGS_PER_CU")) per_cu = std::max(1, atoi(e));
+      int per_cu = 0;
+      PYN_TRY(pyn_kernel_occupancy(c, reinterpret_cast<const void*>(assemble_ho3_lattice_kernel<DIM, NGL, MAT, R, DG>), 256, lds, &per_cu));
+      per_cu = std::max(1, k.ho3_wgs_per_cu >= 0 ? k.ho3_wgs_per_cu : per_cu);
       T.nwork = (int)grid;
       int64_t launch = std::min<int64_t>(grid, (int64_t)per_cu * 256);   // 256 CUs (gfx950)
-      if (const char* e = getenv("PYNAMA_HO3_GRID")) launch = std::min<int64_t>(grid, std::max(1, atoi(e)));   // tests: many runs per workgroup
+      if (k.ho3_grid >= 0) launch = std::min<int64_t>(grid, std::max(1, k.ho3_grid));   // tests: many runs per workgroup
       assemble_ho3_lattice_kernel<DIM, NGL, MAT, R, DG><<<(int)launch, 256, lds, c->stream>>>(T);
     }
   PYN_HIP(hipGetLastError());
@@ -1083,35 +1059,45 @@ int launch_ho3_g(pyn_ctx* c, Ho3Args T) {
 
 // axis-aligned boxes with verified 1-D factors take the kernels that build the blocks straight from them
 template <int DIM, int NGL, int MAT, int R>
-int launch_ho3(pyn_ctx* c, const Ho3Args& T) {
-  if (T.diag && T.tabs1d) return launch_ho3_g<DIM, NGL, MAT, R, true>(c, T);
-  return launch_ho3_g<DIM, NGL, MAT, R, false>(c, T);
+int launch_ho3(pyn_ctx* c, const AsmKnobs& k, const Ho3Args& T) {
+  if (T.diag && T.tabs1d) return launch_ho3_g<DIM, NGL, MAT, R, true>(c, k, T);
+  return launch_ho3_g<DIM, NGL, MAT, R, false>(c, k, T);
 }
 
-// rows per run: tuned on 1024^2 / 64^3 (ngl 3); PYNAMA_HO3_RUN overrides (tests walk every length)
+// the instantiation of the plan's rows per run (pyn_ho3_run_length)
 template <int DIM, int MAT>
-int launch_ho3_r(pyn_ctx* c, const Ho3Args& T) {
-  const char* e = getenv("PYNAMA_HO3_RUN");
-  const int r = e ? atoi(e) : 0;
+int launch_ho3_r(pyn_ctx* c, const AsmKnobs& k, const Ho3Args& T, int R) {
   if (c->box.ngl == 2) {
-    if (DIM == 3) return launch_ho3<3, 2, MAT, 8>(c, T);
-    return launch_ho3<2, 2, MAT, 32>(c, T);
+    if (DIM == 3) return launch_ho3<3, 2, MAT, 8>(c, k, T);
+    return launch_ho3<2, 2, MAT, 32>(c, k, T);
   }
   if (DIM == 3) {
-    if (MAT == M_OP) return launch_ho3<3, 3, MAT, 2>(c, T);      // up to 6 x 3 values per graph edge: two rows per run fill the LDS
-    if (r == 2) return launch_ho3<3, 3, MAT, 2>(c, T);
-    if (r == 8) return launch_ho3<3, 3, MAT, 8>(c, T);
-    return launch_ho3<3, 3, MAT, 4>(c, T);
+    if (R == 2) return launch_ho3<3, 3, MAT, 2>(c, k, T);
+    if (R == 8) return launch_ho3<3, 3, MAT, 8>(c, k, T);
+    return launch_ho3<3, 3, MAT, 4>(c, k, T);
   }
-  if (MAT == M_OP) return launch_ho3<2, 3, MAT, 16>(c, T);
-  if (r == 16) return launch_ho3<2, 3, MAT, 16>(c, T);
-  if (r == 64) return launch_ho3<2, 3, MAT, 64>(c, T);
-  return launch_ho3<2, 3, MAT, 32>(c, T);
+  if (R == 16) return launch_ho3<2, 3, MAT, 16>(c, k, T);
+  if (R == 64) return launch_ho3<2, 3, MAT, 64>(c, k, T);
+  return launch_ho3<2, 3, MAT, 32>(c, k, T);
 }
 
-// geometry pre-pass (+ the once-per-mesh check that every cell is a parallelogram / parallelepiped); *ok = the closed forms apply
-int ho3_prepare(pyn_ctx* c, bool* ok) {
-  *ok = false;
+template <int MAT>
+int launch_ho3_d(pyn_ctx* c, const AsmKnobs& k, const Ho3Args& T, int R) {
+  return c->dim == 3 ? launch_ho3_r<3, MAT>(c, k, T, R) : launch_ho3_r<2, MAT>(c, k, T, R);
+}
+
+}  // namespace
+
+// rows per run: tuned on 1024^2 / 64^3 (ngl 3); PYNAMA_HO3_RUN (`knob`, 0: not set) overrides (tests walk every length); operators
+// carry up to 6 x 3 values per graph edge: two rows per run fill the LDS
+int pyn_ho3_run_length(int dim, int ngl, bool op, int knob) {
+  if (ngl == 2) return dim == 3 ? 8 : 32;
+  if (dim == 3) return op || knob == 2 ? 2 : (knob == 8 ? 8 : 4);
+  return op || knob == 16 ? 16 : (knob == 64 ? 64 : 32);
+}
+
+// geometry pre-pass (+ the once-per-mesh check that every cell is a parallelogram / parallelepiped: the closed forms apply)
+int pyn_ho3_prepare(pyn_ctx* c) {
   Ho3View& L = c->ho3;
   hipStream_t s = c->stream;
   const int gs = c->dim == 3 ? 10 : 6;
@@ -1137,11 +1123,8 @@ int ho3_prepare(pyn_ctx* c, bool* ok) {
     L.affine = h[0] ? 0 : 1;
     L.diag = (h[0] || h[1]) ? 0 : 1;
   }
-  *ok = L.affine == 1 && !getenv("PYNAMA_NO_HO3_LATTICE");
   return PYN_OK;
 }
-
-}  // namespace
 
 // For the matrix-free KLE operator (pyn_matfree_ho3.hip): is every cell a parallelogram / parallelepiped, and axis-aligned?  hc[r][bits]:
 // derivative along reference axis r of the Q1 function of the corner at lattice offsets 2 * bit d (HrsCoo at the first full-rule point)
@@ -1149,8 +1132,7 @@ int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]) {
   *affine = *diag = false;
   const Ho3View& L = c->ho3;
   if (!L.valid || c->box.ngl != 3 || c->quad[0].ngp < 1 || !c->quad[0].HrsCoo) return PYN_OK;
-  bool ok = false;
-  PYN_TRY(ho3_prepare(c, &ok));
+  PYN_TRY(pyn_ho3_prepare(c));
   *affine = L.affine == 1;
   *diag = L.diag == 1;
   const int dim = c->dim, nc = 1 << dim;
@@ -1306,7 +1288,7 @@ int pyn_ho3_symbolic(pyn_ctx* c, bool* done) {
   if (!c->ho3.valid || getenv("PYNAMA_NO_HO3_SYMBOLIC")) return PYN_OK;
   hipStream_t s = c->stream;
   Ho3Args T;
-  fill_lattice_args(c, T);
+  fill_lattice_args(c, asm_knobs(), T);   // (PYNAMA_HO3_NO_PSTD reaches the symbolic kernels too)
   const int64_t n = c->n_owned;
   DevTmp tlen, tmp;
   PYN_HIP(tlen.alloc((n + 1) * sizeof(int32_t)));
@@ -1340,94 +1322,46 @@ int pyn_ho3_symbolic(pyn_ctx* c, bool* done) {
 
 // K (+ Krhs), Rw of pyn_assemble_kle and the scalar Laplacian of pyn_assemble_scalar on a structured mesh of parallelograms /
 // parallelepipeds: second-order cells (ngl 3) in 2-D and 3-D, first-order quadrilaterals (3-D first-order cells have kernels of their
-// own, pyn_assemble_lattice.hip).  *handled stays false when the mesh or the tables do not fit (the caller falls back).
-int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled) {
-  *handled = false;
+// own, pyn_assemble_lattice.hip); and the first-order operators SrT / DivSrT / Curl (pyn_assemble_operator at the nodal rule) on any
+// structured mesh of these cells, 3-D first-order included.  The geometry pre-pass has run (asm_facts).
+int pyn_assemble_ho3_lattice(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P) {
   Ho3View& L = c->ho3;
-  if (!L.valid || c->ho3_tabs_nn != c->nn || !c->ho3_tabs_ok[0] || c->quad[0].ngp < 1) return PYN_OK;
-  if (c->box.ngl == 2 && c->dim == 3) return PYN_OK;
-  if (form == PYN_FORM_KLE && !c->ho3_tabs_ok[1]) return PYN_OK;
-  if (form != PYN_FORM_KLE && form != PYN_FORM_LAPLACE) return PYN_OK;
-  hipStream_t s = c->stream;
-  bool ok = false;
-  PYN_TRY(ho3_prepare(c, &ok));
-  if (!ok) return PYN_OK;
   Ho3Args T;
-  fill_lattice_args(c, T);
+  fill_lattice_args(c, k, T);
+  T.A = rq.K;
+  if (rq.form == PYN_FORM_OPERATOR) {
+    T.obr = rq.op_br;
+    T.obc = rq.op_bc;
+    T.nterms = rq.op_nterms;
+    for (int t = 0; t < rq.op_nterms; ++t) {
+      T.t_row[t] = rq.op_terms[3 * t];
+      T.t_col[t] = rq.op_terms[3 * t + 1];
+      T.t_der[t] = rq.op_terms[3 * t + 2];
+      T.t_coef[t] = rq.op_coef[t];
+    }
+    return launch_ho3_d<M_OP>(c, k, T, P.shape);
+  }
   if (c->d_bcmask) {
     if (L.nbits_stamp != c->bc_stamp) {
       if (!L.d_nbits) PYN_HIP(hipMalloc((void**)&L.d_nbits, (size_t)c->n_node));
-      ho3_pack_bits_kernel<<<(int)((c->n_node + 255) / 256), 256, 0, s>>>(c->d_bcmask, c->n_node, c->bc_ndof, L.d_nbits);
+      ho3_pack_bits_kernel<<<(int)((c->n_node + 255) / 256), 256, 0, c->stream>>>(c->d_bcmask, c->n_node, c->bc_ndof, L.d_nbits);
       L.nbits_stamp = c->bc_stamp;
     }
     T.nbits = L.d_nbits;
   }
-  T.alpha_d = alpha_d;
-  T.alpha_w = alpha_w;
-  if (form == PYN_FORM_LAPLACE) {
-    PYN_CHECK(K, "scalar assembly without a target");
-    T.A = K;
-    T.Arhs = Krhs;
-    T.rhs_clean = c->asm_rhs_clean ? 1 : 0;
-    T.rcrow = c->asm_rcrow;
-    if (c->dim == 3)
-      PYN_TRY((launch_ho3_r<3, M_LAP>(c, T)));
-    else
-      PYN_TRY((launch_ho3_r<2, M_LAP>(c, T)));
-    *handled = true;
-    return PYN_OK;
-  }
-  if (K) {
-    T.A = K;
-    T.Arhs = Krhs;
-    T.rhs_clean = c->asm_rhs_clean ? 1 : 0;
-    T.rcrow = c->asm_rcrow;
-    if (c->dim == 3)
-      PYN_TRY((launch_ho3_r<3, M_K>(c, T)));
-    else
-      PYN_TRY((launch_ho3_r<2, M_K>(c, T)));
-  }
-  if (Rw) {
-    T.A = Rw;
+  T.alpha_d = rq.alpha_d;
+  T.alpha_w = rq.alpha_w;
+  T.Arhs = rq.Krhs;
+  T.rhs_clean = rq.rhs_clean ? 1 : 0;
+  T.rcrow = rq.rcrow;
+  if (rq.form == PYN_FORM_LAPLACE) return launch_ho3_d<M_LAP>(c, k, T, P.shape);
+  if (rq.K) PYN_TRY(launch_ho3_d<M_K>(c, k, T, P.shape));
+  if (rq.Rw) {
+    T.A = rq.Rw;
     T.Arhs = nullptr;
     T.rhs_clean = 0;
     T.rcrow = nullptr;
-    if (c->dim == 3)
-      PYN_TRY((launch_ho3_r<3, M_RW>(c, T)));
-    else
-      PYN_TRY((launch_ho3_r<2, M_RW>(c, T)));
+    PYN_TRY(launch_ho3_d<M_RW>(c, k, T, P.shape));
   }
-  *handled = true;
-  return PYN_OK;
-}
-
-// The first-order operators SrT / DivSrT / Curl (pyn_assemble_operator at the nodal rule) on any structured mesh the row-run kernels
-// know: ngl 2 / 3, 2-D / 3-D, parallelograms / parallelepipeds.
-int pyn_assemble_ho3_operator(pyn_ctx* c, int rule, int br, int bc, int nterms, const int32_t* terms, const double* coef, double* M,
-                              bool* handled) {
-  *handled = false;
-  if (!c->ho3.valid || rule != PYN_Q_NODAL || c->ho3_tabs_nn != c->nn || !c->ho3_tabs_ok[2] || c->quad[0].ngp < 1 || nterms > MAX_TERMS ||
-      getenv("PYNAMA_NO_HO3_OPERATOR"))
-    return PYN_OK;
-  bool ok = false;
-  PYN_TRY(ho3_prepare(c, &ok));
-  if (!ok) return PYN_OK;
-  Ho3Args T;
-  fill_lattice_args(c, T);
-  T.A = M;
-  T.obr = br;
-  T.obc = bc;
-  T.nterms = nterms;
-  for (int t = 0; t < nterms; ++t) {
-    T.t_row[t] = terms[3 * t];
-    T.t_col[t] = terms[3 * t + 1];
-    T.t_der[t] = terms[3 * t + 2];
-    T.t_coef[t] = coef[t];
-  }
-  if (c->dim == 3)
-    PYN_TRY((launch_ho3_r<3, M_OP>(c, T)));
-  else
-    PYN_TRY((launch_ho3_r<2, M_OP>(c, T)));
-  *handled = true;
   return PYN_OK;
 }

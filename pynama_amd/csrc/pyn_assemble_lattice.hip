@@ -1516,14 +1516,8 @@ static int launch_lattice(pyn_ctx* c, LatArgs& T, bool affine) {
   T.nty = (T.ny + TY - 1) / TY;
   const int ntz = (T.n_own + TZ - 1) / TZ;
   const int n_tiles = T.ntx * T.nty * ntz;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_lattice_kernel<TX, TY, TZ, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)LT::BYTES));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_lattice_kernel<TX, TY, TZ, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)LT::BYTES));
-    attr_done = true;
-  }
+  PYN_TRY(pyn_kernel_lds(c, assemble_q1_hex_lattice_kernel<TX, TY, TZ, false>, LT::BYTES));
+  PYN_TRY(pyn_kernel_lds(c, assemble_q1_hex_lattice_kernel<TX, TY, TZ, true>, LT::BYTES));
   if (affine)
     assemble_q1_hex_lattice_kernel<TX, TY, TZ, true><<<n_tiles, TILE_THREADS, LT::BYTES, c->stream>>>(T);
   else
@@ -1532,46 +1526,45 @@ static int launch_lattice(pyn_ctx* c, LatArgs& T, bool affine) {
   return PYN_OK;
 }
 
-// lattice descriptor -> kernel arguments (+ the one-off verification that index arithmetic may replace the loads)
-static int lat_fill_args(pyn_ctx* c, LatArgs& T, double* A, double* Arhs, int* mesh_aff) {
-  Lattice& L = c->lat;
+// lattice descriptor -> kernel arguments; the targets and the compact / clean facts of an assembly's Arhs are the caller's
+static void lat_fill(const pyn_ctx* c, const AsmKnobs& k, LatArgs& T) {
   const BoxLattice& B = c->box;
+  T = LatArgs();   // no target, every tile layer
   T.xyz = c->d_xyz;
   T.rowptr = c->d_rowptr;
   T.bcmask = c->d_bcmask;
   T.P = B.d_P;
-  T.zord = L.d_zord;
+  T.zord = c->lat.d_zord;
   T.nx = B.NX;
   T.ny = B.NY;
   T.npl = B.npl;
   T.p_own0 = B.p_own0;
   T.n_own = B.n_own;
-  T.ntx = T.nty = 0;
-  T.bz0 = 0;
   T.bzs = 1;
-  T.std_lat = 0;
-  T.q = TileArgs();
+  T.std_lat = c->lat.std_ok == 1;
   T.q.w = c->quad[0].w;
   T.q.hrs = c->quad[0].Hrs;
   T.q.hcoo = c->quad[0].HrsCoo;
-  T.q.aff = getenv("PYNAMA_NO_AFFINE") ? nullptr : c->d_aff;
-  T.A = A;
-  T.Arhs = Arhs;
-  T.dinv = nullptr;
-  T.rhs_clean = c->asm_rhs_clean ? 1 : 0;
-  T.rcrow = c->asm_rcrow;
-  const char* ab = getenv("PYNAMA_LATTICE_ABLATE");  // diagnostics: 1 = no element phase, 4 = no plain-tile store path
-  T.ablate = ab ? atoi(ab) : 0;
-  T.lean = c->q1_gauss_standard && !getenv("PYNAMA_NO_LEAN") ? 1 : 0;
-  PYN_TRY(pyn_mesh_all_affine(c, mesh_aff));
-  if (L.std_ok < 0) {      // once per graph: may the index arithmetic replace P / zord / rowptr?
+  T.q.aff = k.no_affine ? nullptr : c->d_aff;
+  T.ablate = k.lattice_ablate;   // diagnostics: 1 = no element phase, 4 = no plain-tile store path
+  T.lean = c->q1_gauss_standard && !k.no_lean ? 1 : 0;
+}
+
+// the two device checks behind the lattice kernels: every element a parallelepiped (once per mesh), and may the index arithmetic
+// replace P / zord / rowptr (once per graph)
+int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k) {
+  Lattice& L = c->lat;
+  int mesh_aff = 0;
+  PYN_TRY(pyn_mesh_all_affine(c, &mesh_aff));
+  if (L.std_ok < 0) {
     L.std_ok = 0;
-    if (L.std_shape && !getenv("PYNAMA_NO_STD_LATTICE")) {
+    if (L.std_shape && !k.no_std_lattice) {
       DevTmp flag;
       PYN_HIP(flag.alloc(sizeof(int)));
       const int one = 1;
       PYN_HIP(hipMemcpyAsync(flag.p, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
-      LatArgs Tc = T;
+      LatArgs Tc;
+      lat_fill(c, k, Tc);
       Tc.std_lat = 1;
       lattice_rowptr_check_kernel<<<(int)((c->n_owned + 255) / 256), 256, 0, c->stream>>>(Tc, c->d_rowptr, c->n_owned, flag.as<int>());
       int h = 0;
@@ -1580,8 +1573,27 @@ static int lat_fill_args(pyn_ctx* c, LatArgs& T, double* A, double* Arhs, int* m
       L.std_ok = h;
     }
   }
-  T.std_lat = L.std_ok == 1;
   return PYN_OK;
+}
+
+// the matrix-free products: checks + arguments, under the switches of the moment (only those the checks and the fill read: this
+// runs once per product of a Krylov loop)
+static int lat_fill_args(pyn_ctx* c, LatArgs& T, int* mesh_aff) {
+  const AsmKnobs k = lat_fill_knobs();
+  PYN_TRY(pyn_lattice_checks(c, k));
+  lat_fill(c, k, T);
+  *mesh_aff = c->mesh_affine == 1;
+  return PYN_OK;
+}
+
+// what the KLE kernels (assembly and matrix-free) need beyond the lattice arguments: the two coefficients, the reduced rule
+static void kle_fill(const pyn_ctx* c, KleLatArgs& T, double alpha_d, double alpha_w) {
+  T.alpha_d = alpha_d;
+  T.alpha_w = alpha_w;
+  T.wr = c->quad[1].w;
+  T.hrsr = c->quad[1].Hrs;
+  T.Hr = c->quad[1].H;
+  T.hcoor = c->quad[1].HrsCoo;
 }
 
 template <int TX, int TY, int TZ, bool GEN>
@@ -1591,25 +1603,12 @@ static int launch_kle_lattice(pyn_ctx* c, KleLatArgs& T, double* K, double* Krhs
   T.L.nty = (T.L.ny + TY - 1) / TY;
   const int n_tiles = T.L.ntx * T.L.nty * ((T.L.n_own + TZ - 1) / TZ);
   const size_t lds = (size_t)LT::NR * 243 * sizeof(double) + LT::META_INTS * sizeof(int);
-  static bool attr_done = false;
-  if (!attr_done) {
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_kle_lattice_kernel<TX, TY, TZ, false, GEN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_kle_lattice_kernel<TX, TY, TZ, true, GEN>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_done = true;
-  }
+  PYN_TRY(pyn_kernel_lds(c, assemble_q1_hex_kle_lattice_kernel<TX, TY, TZ, false, GEN>, lds));
+  PYN_TRY(pyn_kernel_lds(c, assemble_q1_hex_kle_lattice_kernel<TX, TY, TZ, true, GEN>, lds));
   if (K) {
     if (GEN) {   // the element Laplacians, once per element
       const int64_t ne = (int64_t)(T.L.nx - 1) * (T.L.ny - 1) * (T.L.npl - 1);
-      const size_t need = (size_t)28 * ne * sizeof(double);
-      if (need > c->kle_lel_bytes) {
-        if (c->d_kle_lel) PYN_HIP(hipFree(c->d_kle_lel));
-        c->d_kle_lel = nullptr;
-        c->kle_lel_bytes = 0;
-        PYN_HIP(hipMalloc((void**)&c->d_kle_lel, need));
-        c->kle_lel_bytes = need;
-      }
+      PYN_TRY(pyn_grow(&c->d_kle_lel, &c->kle_lel_bytes, (size_t)28 * ne * sizeof(double)));
       kle_elem_laplace_kernel<<<(int)((ne + 255) / 256), 256, 0, c->stream>>>(T.L, c->d_kle_lel, ne);
       T.Lel = c->d_kle_lel;
       T.ne = ne;
@@ -1627,73 +1626,50 @@ static int launch_kle_lattice(pyn_ctx* c, KleLatArgs& T, double* K, double* Krhs
   return PYN_OK;
 }
 
-// KLE on lattices of parallelepipeds (the reference's box meshes): plan-free kernels
-int pyn_assemble_kle_lattice(pyn_ctx* c, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled) {
-  if (!c->lat.valid || c->quad[0].ngp != 8 || c->quad[1].ngp != 1 || getenv("PYNAMA_NO_KLE_LATTICE")) return PYN_OK;
+// KLE on lattices (the reference's box meshes): plan-free kernels.  Parallelepipeds: closed forms, tile = the plan's shape; general
+// geometry (AsmPlan::kle_general): the same four-wave kernel with the closed form of the 2x2x2 rule (standard tables only)
+int pyn_assemble_kle_lattice(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P) {
   KleLatArgs T;
-  int mesh_aff = 0;
-  PYN_TRY(lat_fill_args(c, T.L, nullptr, nullptr, &mesh_aff));
-  const bool affine = mesh_aff && c->aff_standard && c->aff_rw_standard && !getenv("PYNAMA_NO_AFFINE");
-  // general geometry: the same plan-free four-wave kernel with the closed form of the 2x2x2 rule (standard tables only);
-  // anything else falls through to the patch-plan kernels with the table-driven quadrature
-  const bool general = !affine && c->q1_gauss_standard && c->q1_red_standard && !getenv("PYNAMA_NO_KLE_GENERAL");
-  if (!affine && !general) return PYN_OK;
-  T.alpha_d = alpha_d;
-  T.alpha_w = alpha_w;
-  T.wr = c->quad[1].w;
-  T.hrsr = c->quad[1].Hrs;
-  T.Hr = c->quad[1].H;
-  T.hcoor = c->quad[1].HrsCoo;
-  const char* tl = getenv("PYNAMA_KLE_LATTICE_TILE");
-  if (general) {
-    PYN_TRY((launch_kle_lattice<3, 3, 3, true>(c, T, K, Krhs, Rw)));
-    *handled = true;
-    return PYN_OK;
+  lat_fill(c, k, T.L);
+  kle_fill(c, T, rq.alpha_d, rq.alpha_w);
+  T.L.rhs_clean = rq.rhs_clean ? 1 : 0;
+  T.L.rcrow = rq.rcrow;
+  if (P.kle_general) return launch_kle_lattice<3, 3, 3, true>(c, T, rq.K, rq.Krhs, rq.Rw);
+  switch (P.shape) {
+    case 1: return launch_kle_lattice<6, 2, 2, false>(c, T, rq.K, rq.Krhs, rq.Rw);
+    case 2: return launch_kle_lattice<3, 3, 2, false>(c, T, rq.K, rq.Krhs, rq.Rw);
+    case 3: return launch_kle_lattice<4, 3, 3, false>(c, T, rq.K, rq.Krhs, rq.Rw);
+    case 4: return launch_kle_lattice<5, 2, 2, false>(c, T, rq.K, rq.Krhs, rq.Rw);   // 39 KB: four workgroups per CU, -3.5 % (flat 6x3x1 / 7x2x1 / 3x3x1 tiles: +0 .. +37 %)
+    default: return launch_kle_lattice<3, 3, 3, false>(c, T, rq.K, rq.Krhs, rq.Rw);
   }
-  switch (tl ? atoi(tl) : 0) {
-    case 1: PYN_TRY((launch_kle_lattice<6, 2, 2, false>(c, T, K, Krhs, Rw))); break;
-    case 2: PYN_TRY((launch_kle_lattice<3, 3, 2, false>(c, T, K, Krhs, Rw))); break;
-    case 3: PYN_TRY((launch_kle_lattice<4, 3, 3, false>(c, T, K, Krhs, Rw))); break;
-    case 4: PYN_TRY((launch_kle_lattice<5, 2, 2, false>(c, T, K, Krhs, Rw))); break;   // 39 KB: four workgroups per CU, -3.5 % (flat 6x3x1 / 7x2x1 / 3x3x1 tiles: +0 .. +37 %)
-    default: PYN_TRY((launch_kle_lattice<3, 3, 3, false>(c, T, K, Krhs, Rw))); break;
-  }
-  *handled = true;
-  return PYN_OK;
 }
 
-int pyn_assemble_lattice(pyn_ctx* c, double* A, double* Arhs, bool* handled) {
-  Lattice& L = c->lat;
-  if (!L.valid || c->quad[0].ngp != 8) return PYN_OK;
+// The scalar Laplacian on a lattice.  Measured at 10M DOFs: parallelepipeds are store-bound -> small tiles, 5 workgroups
+// per CU; the quadrature path is FP64-bound -> the z-marching kernel (AK_MARCH), else 7x7x7 tiles (least redundant integration that
+// fits the LDS twice).  A compact Arhs is left to the completion pass.
+int pyn_assemble_lattice(pyn_ctx* c, AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P) {
   LatArgs T;
-  int mesh_aff = 0;
-  PYN_TRY(lat_fill_args(c, T, A, Arhs, &mesh_aff));
-  T.dinv = c->asm_dinv;            // the store phases see whole rows: 1 / diagonal leaves with them (no diag_kernel pass)
-  c->asm_dinv_written = T.dinv != nullptr;
-  const bool affine = mesh_aff == 1 && T.q.aff != nullptr && c->aff_standard;
-  // measured at 10M DOFs: parallelepipeds are store-bound -> small tiles, 5 workgroups per CU;
-  // the quadrature path is FP64-bound -> 7x7x7 tiles (least redundant integration that fits the LDS twice)
-  const char* tl = getenv("PYNAMA_LATTICE_TILE");
-  if (!affine && c->q1_gauss_standard && T.std_lat && !tl && !getenv("PYNAMA_NO_MARCH")) {   // general geometry: FP64-bound -> z-marching kernel
-    const char* mt = getenv("PYNAMA_MARCH_TILE");
-    PYN_TRY(pyn_assemble_lattice_march(c, &T, mt ? atoi(mt) : 0));
-    *handled = true;
-    return PYN_OK;
+  lat_fill(c, k, T);
+  T.A = rq.K;
+  T.Arhs = P.krhs_pending ? nullptr : rq.Krhs;
+  T.rhs_clean = rq.rhs_clean ? 1 : 0;
+  T.rcrow = rq.rcrow;
+  T.dinv = P.dinv ? rq.dinv : nullptr;   // the store phases see whole rows: 1 / diagonal leaves with them (no diag_kernel pass)
+  rq.dinv_written = T.dinv != nullptr;
+  if (P.kind == AK_MARCH) return pyn_assemble_lattice_march(c, k, &T, P.shape);
+  const bool affine = P.k_closed;
+  switch (P.shape) {
+    case 1: return launch_lattice<7, 7, 7>(c, T, affine);
+    case 2: return launch_lattice<6, 6, 6>(c, T, affine);
+    case 3: return launch_lattice<8, 6, 6>(c, T, affine);
+    case 4: return launch_lattice<7, 6, 6>(c, T, affine);
+    case 5: return launch_lattice<6, 6, 4>(c, T, affine);
+    case 6: return launch_lattice<6, 5, 5>(c, T, affine);
+    case 7: return launch_lattice<7, 4, 4>(c, T, affine);
+    case 8: return launch_lattice<14, 3, 3>(c, T, affine);
+    case 9: return launch_lattice<7, 5, 5>(c, T, affine);
+    default: return launch_lattice<7, 5, 4>(c, T, affine);
   }
-  const int sel = tl ? atoi(tl) : (affine ? 0 : 1);
-  switch (sel) {
-    case 1: PYN_TRY((launch_lattice<7, 7, 7>(c, T, affine))); break;
-    case 2: PYN_TRY((launch_lattice<6, 6, 6>(c, T, affine))); break;
-    case 3: PYN_TRY((launch_lattice<8, 6, 6>(c, T, affine))); break;
-    case 4: PYN_TRY((launch_lattice<7, 6, 6>(c, T, affine))); break;
-    case 5: PYN_TRY((launch_lattice<6, 6, 4>(c, T, affine))); break;
-    case 6: PYN_TRY((launch_lattice<6, 5, 5>(c, T, affine))); break;
-    case 7: PYN_TRY((launch_lattice<7, 4, 4>(c, T, affine))); break;
-    case 8: PYN_TRY((launch_lattice<14, 3, 3>(c, T, affine))); break;
-    case 9: PYN_TRY((launch_lattice<7, 5, 5>(c, T, affine))); break;
-    default: PYN_TRY((launch_lattice<7, 5, 4>(c, T, affine))); break;
-  }
-  *handled = true;
-  return PYN_OK;
 }
 
 
@@ -1781,7 +1757,7 @@ static int matfree_laplace_launch(pyn_ctx* c, const double* x, double* y, bool d
   PYN_CHECK(c->mf_set[PYN_MATFREE_LAPLACE], "matrix-free Laplacian: pyn_matfree_set first");
   LatArgs T;
   int mesh_aff = 0;
-  PYN_TRY(lat_fill_args(c, T, nullptr, nullptr, &mesh_aff));
+  PYN_TRY(lat_fill_args(c, T, &mesh_aff));
   T.bcmask = c->mf_mask[PYN_MATFREE_LAPLACE];
   const bool affine = mesh_aff == 1 && T.q.aff != nullptr && c->aff_standard;
   const char* tl = getenv("PYNAMA_MATFREE_TILE");
@@ -1841,14 +1817,9 @@ static int matfree_kle_launch(pyn_ctx* c, const double* x, double* y, bool dot, 
   PYN_CHECK(c->mf_set[PYN_MATFREE_KLE], "matrix-free KLE operator: pyn_matfree_set first");
   KleLatArgs K;
   int mesh_aff = 0;
-  PYN_TRY(lat_fill_args(c, K.L, nullptr, nullptr, &mesh_aff));
+  PYN_TRY(lat_fill_args(c, K.L, &mesh_aff));
   K.L.bcmask = c->mf_mask[PYN_MATFREE_KLE];
-  K.alpha_d = c->mf_alpha_d;
-  K.alpha_w = c->mf_alpha_w;
-  K.wr = c->quad[1].w;
-  K.hrsr = c->quad[1].Hrs;
-  K.Hr = c->quad[1].H;
-  K.hcoor = c->quad[1].HrsCoo;
+  kle_fill(c, K, c->mf_alpha_d, c->mf_alpha_w);
   const bool affine = mesh_aff == 1 && K.L.q.aff != nullptr && c->aff_standard;
   const char* tl = getenv("PYNAMA_MATFREE_TILE");
   switch (tl ? atoi(tl) : 0) {

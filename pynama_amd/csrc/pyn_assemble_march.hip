@@ -319,32 +319,26 @@ __global__ void __launch_bounds__((TX + 1) * (TY + 1), WPS) assemble_q1_hex_marc
 }
 
 template <int TX, int TY, int WPS, int ROLLED = 0>
-int launch_march(pyn_ctx* c, LatArgs& T, int wg_per_cu) {
+int launch_march(pyn_ctx* c, const AsmKnobs& k, LatArgs& T, int wg_per_cu) {
   using MT = MarchTile<TX, TY>;
   T.ntx = (T.nx + TX - 1) / TX;
   T.nty = (T.ny + TY - 1) / TY;
   const int ncol = T.ntx * T.nty;
   // z-chunks: about 28 planes each, then as many chunks as fit into the same number of rounds of resident workgroups
   const int resident = 256 * wg_per_cu;
-  const char* zl = getenv("PYNAMA_MARCH_ZLEN");
   int nzc = std::max(1, (T.n_own + 27) / 28);
-  if (zl) nzc = std::max(1, (T.n_own + atoi(zl) - 1) / std::max(1, atoi(zl)));
+  if (k.march_zlen >= 0) nzc = std::max(1, (T.n_own + k.march_zlen - 1) / std::max(1, k.march_zlen));
   else {
     const int rounds = (ncol * nzc + resident - 1) / resident;
     nzc = std::min(T.n_own, std::max(nzc, rounds * resident / ncol));
   }
   const int zlen = (T.n_own + nzc - 1) / nzc;
   nzc = (T.n_own + zlen - 1) / zlen;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_march_kernel<TX, TY, WPS, ROLLED>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)MT::BYTES));
-    attr_done = true;
-  }
+  PYN_TRY(pyn_kernel_lds(c, assemble_q1_hex_march_kernel<TX, TY, WPS, ROLLED>, MT::BYTES));
   const double ws = 1.0 / 512.0;   // unit weights of the 2x2x2 rule (checked: q1_gauss_standard)
   DevTmp stamps;
   const int nblk = ncol * nzc;
-  if (getenv("PYNAMA_MARCH_STAMPS")) {
+  if (k.march_stamps) {
     PYN_HIP(stamps.alloc((size_t)nblk * 32 * 8 * sizeof(unsigned long long)));
     PYN_HIP(hipMemsetAsync(stamps.p, 0, (size_t)nblk * 32 * 8 * sizeof(unsigned long long), c->stream));
     T.dbg = stamps.as<unsigned long long>();
@@ -388,24 +382,24 @@ bool pyn_q1_gauss_tables_standard(const double* w, const double* H, const double
   return true;
 }
 
-// general-geometry scalar Laplacian on a lattice: z-marching kernel.  `tile`: 0 = default shape
-int pyn_assemble_lattice_march(pyn_ctx* c, void* lat_args, int tile) {
+// general-geometry scalar Laplacian on a lattice: z-marching kernel.  `shape`: the plan's, 0 = default shape
+int pyn_assemble_lattice_march(pyn_ctx* c, const AsmKnobs& k, void* lat_args, int shape) {
   LatArgs& T = *static_cast<LatArgs*>(lat_args);
-  switch (tile) {
-    case 1: return launch_march<15, 11, 2>(c, T, 2);
-    case 2: return launch_march<15, 7, 2>(c, T, 3);
-    case 3: return launch_march<31, 7, 1>(c, T, 1);
-    case 5: return launch_march<15, 15, 1>(c, T, 1);
-    case 6: return launch_march<7, 7, 3, true>(c, T, 7);
-    case 7: return launch_march<7, 7, 2>(c, T, 7);     // Gauss points unrolled: 256 VGPRs, 9 % slower than the rolled loop
-    case 8: return launch_march<15, 7, 3, true>(c, T, 3);
-    case 9: return launch_march<15, 7, 2, true>(c, T, 3);
-    case 10: return launch_march<15, 15, 1, true>(c, T, 1);
-    case 11: return launch_march<15, 11, 2, true>(c, T, 2);
-    case 12: return launch_march<7, 7, 2, true>(c, T, 7);   // the default shape with the pointwise (rolled) element routine
-    case 13: return launch_march<15, 7, 2, 2>(c, T, 3);
-    case 14: return launch_march<15, 15, 1, 2>(c, T, 1);
+  switch (shape) {
+    case 1: return launch_march<15, 11, 2>(c, k, T, 2);
+    case 2: return launch_march<15, 7, 2>(c, k, T, 3);
+    case 3: return launch_march<31, 7, 1>(c, k, T, 1);
+    case 5: return launch_march<15, 15, 1>(c, k, T, 1);
+    case 6: return launch_march<7, 7, 3, true>(c, k, T, 7);
+    case 7: return launch_march<7, 7, 2>(c, k, T, 7);     // Gauss points unrolled: 256 VGPRs, 9 % slower than the rolled loop
+    case 8: return launch_march<15, 7, 3, true>(c, k, T, 3);
+    case 9: return launch_march<15, 7, 2, true>(c, k, T, 3);
+    case 10: return launch_march<15, 15, 1, true>(c, k, T, 1);
+    case 11: return launch_march<15, 11, 2, true>(c, k, T, 2);
+    case 12: return launch_march<7, 7, 2, true>(c, k, T, 7);   // the default shape with the pointwise (rolled) element routine
+    case 13: return launch_march<15, 7, 2, 2>(c, k, T, 3);
+    case 14: return launch_march<15, 15, 1, 2>(c, k, T, 1);
     // one wave per workgroup, 7 workgroups per CU, rolled loop over the Gauss points (224 VGPRs): fastest measured
-    default: return launch_march<7, 7, 2, 2>(c, T, 7);
+    default: return launch_march<7, 7, 2, 2>(c, k, T, 7);
   }
 }

@@ -1045,9 +1045,8 @@ extern "C" int pyn_patch_plan_info(pyn_ctx* c, int kind, int64_t* info) {
   return PYN_OK;
 }
 
-static bool g_default_plan = false;  // pyn_patch_plan_set_kind called by ensure_default_plan
-
-extern "C" int pyn_patch_plan_set_kind(pyn_ctx* c, int kind, int n_patch, const int32_t* patch_ptr, const int32_t* patch_rows) {
+// user: set through the C ABI (the lattice families then stand back), not the automatic plan of pyn_patch_plan_default
+static int patch_plan_install(pyn_ctx* c, int kind, int n_patch, const int32_t* patch_ptr, const int32_t* patch_rows, bool user) {
   PYN_CHECK(c, "ctx is NULL");
   PYN_CHECK(kind == 0 || kind == 1, "plan kind must be 0 (scalar) or 1 (KLE)");
   PatchPlan& P = c->plan[kind];
@@ -1128,7 +1127,7 @@ extern "C" int pyn_patch_plan_set_kind(pyn_ctx* c, int kind, int n_patch, const 
   int maxlen = 0;
   for (int64_t i = 0; i < c->n_owned; ++i) maxlen = std::max(maxlen, rp[i + 1] - rp[i]);
   P.npatch = n_patch;
-  P.user = !g_default_plan;
+  P.user = user;
   P.npe = npe;
   P.maxrows = max_rows;
   P.maxlen = maxlen;
@@ -1136,29 +1135,22 @@ extern "C" int pyn_patch_plan_set_kind(pyn_ctx* c, int kind, int n_patch, const 
   if (kind == 0) {
     size_t lds = (size_t)max_rows * maxlen * sizeof(double) + (size_t)max_rows * 3 * sizeof(int);
     PYN_CHECK(lds <= 160 * 1024, "patch accumulators need %zu B of LDS", lds);
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_tiled_kernel<0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_tiled_kernel<1>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_tiled_kernel<2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_p1_tet_tiled_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_tiled_affine_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (const void* fn : {(const void*)assemble_q1_hex_tiled_kernel<0>, (const void*)assemble_q1_hex_tiled_kernel<1>,
+                           (const void*)assemble_q1_hex_tiled_kernel<2>, (const void*)assemble_p1_tet_tiled_kernel,
+                           (const void*)assemble_q1_hex_tiled_affine_kernel})
+      PYN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // the size follows the plan: always
   } else {
     size_t lds = kle_lds_bytes(max_rows, maxlen);
     PYN_CHECK(lds <= 160 * 1024, "KLE patch accumulators need %zu B of LDS", lds);
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_kle_tiled_kernel<0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_kle_tiled_kernel<1>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_kle_affine_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(assemble_q1_hex_kle_affine_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (const void* fn : {(const void*)assemble_q1_hex_kle_tiled_kernel<0>, (const void*)assemble_q1_hex_kle_tiled_kernel<1>,
+                           (const void*)assemble_q1_hex_kle_affine_kernel<false>, (const void*)assemble_q1_hex_kle_affine_kernel<true>})
+      PYN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // the size follows the plan: always
   }
   return PYN_OK;
+}
+
+extern "C" int pyn_patch_plan_set_kind(pyn_ctx* c, int kind, int n_patch, const int32_t* patch_ptr, const int32_t* patch_rows) {
+  return patch_plan_install(c, kind, n_patch, patch_ptr, patch_rows, true);
 }
 
 namespace {
@@ -1207,71 +1199,9 @@ int pyn_mesh_all_affine(pyn_ctx* c, int* out) {
   return PYN_OK;
 }
 
-static int assemble_kle_tiled(pyn_ctx* c, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled) {
-  PatchPlan& P = c->plan[1];
-  if (!P.npatch || c->dim != 3 || c->nn != 8 || c->quad[0].ngp != 8 || c->quad[1].ngp != 1) return PYN_OK;
-  KleArgs T;
-  T.conn = c->d_conn;
-  T.xyz = c->d_xyz;
-  T.rowptr = c->d_rowptr;
-  T.colidx = c->d_colidx;
-  T.bcmask = c->d_bcmask;
-  T.p_rowptr = P.rowptr;
-  T.p_rows = P.rows;
-  T.p_eptr = P.eptr;
-  T.p_elem = P.elem;
-  T.rowslot4 = (const uint4*)P.rowslot4;
-  T.kmap4 = (const uint4*)P.kmap4;
-  T.npe = P.npe;
-  T.maxlen = P.maxlen;
-  T.maxrows = P.maxrows;
-  T.w = c->quad[0].w;
-  T.H = c->quad[0].H;
-  T.hrs = c->quad[0].Hrs;
-  T.hcoo = c->quad[0].HrsCoo;
-  T.wr = c->quad[1].w;
-  T.Hr = c->quad[1].H;
-  T.hrsr = c->quad[1].Hrs;
-  T.hcoor = c->quad[1].HrsCoo;
-  T.aff = getenv("PYNAMA_NO_AFFINE") ? nullptr : c->d_aff;
-  T.aff_rw = (T.aff && c->aff_rw_standard) ? 1 : 0;
-  T.lean = c->q1_gauss_standard && !getenv("PYNAMA_NO_LEAN") ? 1 : 0;
-  {
-    const char* ab = getenv("PYNAMA_KLE_ABLATE");
-    T.ablate = ab ? atoi(ab) : 0;
-  }
-  T.alpha_d = alpha_d;
-  T.alpha_w = alpha_w;
-  const size_t lds = kle_lds_bytes(P.maxrows, P.maxlen);
-  if (K) {
-    T.K = K;
-    T.Krhs = Krhs;
-    int all_aff = 0;
-    if (T.aff && c->aff_standard) PYN_TRY(pyn_mesh_all_affine(c, &all_aff));
-    if (all_aff)
-      assemble_q1_hex_kle_affine_kernel<false><<<P.npatch, KLE_AFF_THREADS, lds, c->stream>>>(T);
-    else
-      assemble_q1_hex_kle_tiled_kernel<0><<<P.npatch, KLE_THREADS, lds, c->stream>>>(T);
-  }
-  if (Rw) {
-    T.K = Rw;
-    T.Krhs = nullptr;
-    int all_aff = 0;
-    if (T.aff_rw) PYN_TRY(pyn_mesh_all_affine(c, &all_aff));
-    if (all_aff)
-      assemble_q1_hex_kle_affine_kernel<true><<<P.npatch, KLE_AFF_THREADS, lds, c->stream>>>(T);
-    else
-      assemble_q1_hex_kle_tiled_kernel<1><<<P.npatch, KLE_THREADS, lds, c->stream>>>(T);
-  }
-  PYN_HIP(hipGetLastError());
-  *handled = true;
-  return PYN_OK;
-}
-
 // Meshes without a caller-supplied plan get patches of consecutive rows: optimal for no numbering in
 // particular, but any partition is valid and even 8x redundant integration beats the HBM-atomic scatter.
-
-static int ensure_default_plan(pyn_ctx* c, int kind) {
+int pyn_patch_plan_default(pyn_ctx* c, int kind) {
   const bool tets = kind == 0 && c->nn == 4 && c->quad[0].const_grad;
   if (c->plan[kind].npatch || c->plan_unfit[kind] || c->dim != 3 || !(c->nn == 8 || tets) || getenv("PYNAMA_NO_AUTO_PLAN")) return PYN_OK;
   const int64_t n = c->n_owned;
@@ -1299,58 +1229,23 @@ static int ensure_default_plan(pyn_ctx* c, int kind) {
     for (int p = 0; p <= np; ++p) ptr[p] = (int32_t)std::min<int64_t>((int64_t)p * chunk, n);
     for (int64_t i = 0; i < n; ++i) rows[i] = (int32_t)i;
   }
-  g_default_plan = true;
-  int rc = pyn_patch_plan_set_kind(c, kind, (int)ptr.size() - 1, ptr.data(), rows.data());
-  g_default_plan = false;
+  int rc = patch_plan_install(c, kind, (int)ptr.size() - 1, ptr.data(), rows.data(), false);
   if (rc != PYN_OK && tets) {   // e.g. rows longer than the 32 entries the store phase handles: atomics kernel instead
-    (void)pyn_patch_plan_set_kind(c, kind, 0, nullptr, nullptr);
+    (void)patch_plan_install(c, kind, 0, nullptr, nullptr, false);
     c->plan_unfit[kind] = true;
     rc = PYN_OK;
   }
   return rc;
 }
 
-int pyn_assemble_q1_tiled(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, double* Rd, bool* handled) {
-  *handled = false;
-  if (c->ho3.valid && !Rd && ((form == PYN_FORM_LAPLACE && K && !Rw) || (form == PYN_FORM_KLE && (K || (Rw && !Krhs))))) {
-    // second-order (ngl = 3) structured meshes: row-run kernels without atomics (pyn_assemble_ho3.hip)
-    PYN_TRY(pyn_assemble_ho3_lattice(c, form, alpha_d, alpha_w, K, Krhs, Rw, handled));
-    if (*handled) return PYN_OK;
-    PYN_CHECK(!getenv("PYNAMA_HO3_REQUIRE"), "PYNAMA_HO3_REQUIRE: the ngl = 3 lattice kernels declined this assembly (non-affine cell or tables missing)");
-  }
-  // Kernel families that cannot address a COMPACT imposed-column target (c->asm_rcrow) assemble K (and Rw) alone; run_assembly then
-  // fills the compact Krhs from the elements that hold an imposed node.  Native: the ngl = 3 row-run kernels above, the KLE lattice kernels.
-  double* const KrhsN = c->asm_rcrow ? nullptr : Krhs;
-  const bool pend = Krhs && c->asm_rcrow;
-  if (form == PYN_FORM_LAPLACE && K && !Rw && !Rd && c->lat.valid && !c->plan[0].user) {
-    PYN_TRY(pyn_assemble_lattice(c, K, KrhsN, handled));
-    if (*handled) {
-      c->asm_krhs_pending = pend;
-      return PYN_OK;
-    }
-  }
-  if (form == PYN_FORM_KLE && (K || (Rw && !Krhs)) && !Rd && !c->plan[1].user) {   // (Rw alone is a legal request of the ABI)
-    PYN_TRY(pyn_assemble_kle_lattice(c, alpha_d, alpha_w, K, Krhs, Rw, handled));
-    if (*handled) return PYN_OK;
-  }
-  if (form == PYN_FORM_KLE && K && !Rd) PYN_TRY(ensure_default_plan(c, 1));
-  if (form == PYN_FORM_LAPLACE && K && !Rw && !Rd) PYN_TRY(ensure_default_plan(c, 0));
-  if (form == PYN_FORM_KLE && K && !Rd) {
-    PYN_TRY(assemble_kle_tiled(c, alpha_d, alpha_w, K, KrhsN, Rw, handled));
-    if (*handled) c->asm_krhs_pending = pend;
-    return PYN_OK;
-  }
-  PatchPlan& P = c->plan[0];
-  if (!P.npatch || form != PYN_FORM_LAPLACE || !K || Rw || Rd) return PYN_OK;
-  const bool tets = c->dim == 3 && c->nn == 4 && c->quad[0].const_grad && !getenv("PYNAMA_NO_P1_TILED");
-  if (!tets && (c->dim != 3 || c->nn != 8 || c->quad[0].ngp != 8)) return PYN_OK;
-  TileArgs T;
+// what TileArgs and KleArgs share: mesh, graph, plan, full-rule tables, the affine shortcut and the lean closed form
+template <typename Args>
+static void patch_fill(const pyn_ctx* c, const AsmKnobs& k, const PatchPlan& P, Args& T) {
   T.conn = c->d_conn;
   T.xyz = c->d_xyz;
   T.rowptr = c->d_rowptr;
   T.colidx = c->d_colidx;
   T.bcmask = c->d_bcmask;
-  T.colbc = nullptr;
   T.p_rowptr = P.rowptr;
   T.p_rows = P.rows;
   T.p_eptr = P.eptr;
@@ -1358,34 +1253,67 @@ int pyn_assemble_q1_tiled(pyn_ctx* c, int form, double alpha_d, double alpha_w, 
   T.rowslot4 = (const uint4*)P.rowslot4;
   T.kmap4 = (const uint4*)P.kmap4;
   T.npe = P.npe;
-  T.n_patch = P.npatch;
   T.maxlen = P.maxlen;
   T.maxrows = P.maxrows;
   T.w = c->quad[0].w;
   T.hrs = c->quad[0].Hrs;
   T.hcoo = c->quad[0].HrsCoo;
-  T.aff = getenv("PYNAMA_NO_AFFINE") ? nullptr : c->d_aff;
-  T.lean = c->q1_gauss_standard && !getenv("PYNAMA_NO_LEAN") ? 1 : 0;
-  T.A = K;
-  T.Arhs = KrhsN;
-  c->asm_krhs_pending = pend;
-  size_t lds = (size_t)P.maxrows * P.maxlen * sizeof(double) + (size_t)P.maxrows * 3 * sizeof(int);
-  const char* ab = getenv("PYNAMA_TILED_ABLATE");  // diagnostics only: 1 = no LDS adds, 2 = no quadrature
-  const int abl = ab ? atoi(ab) : 0;
-  int all_aff = 0;
-  if (!tets && T.aff && c->aff_standard && !abl && !getenv("PYNAMA_NO_LEAN_PLAN")) PYN_TRY(pyn_mesh_all_affine(c, &all_aff));
-  if (tets)
-    assemble_p1_tet_tiled_kernel<<<P.npatch, TILE_THREADS, lds, c->stream>>>(T, c->quad[0].wsum);
-  else if (all_aff)
-    assemble_q1_hex_tiled_affine_kernel<<<P.npatch, TILE_THREADS, lds, c->stream>>>(T);
-  else if (abl == 1)
-    assemble_q1_hex_tiled_kernel<1><<<P.npatch, TILE_THREADS, lds, c->stream>>>(T);
-  else if (abl == 2)
-    assemble_q1_hex_tiled_kernel<2><<<P.npatch, TILE_THREADS, lds, c->stream>>>(T);
-  else
-    assemble_q1_hex_tiled_kernel<0><<<P.npatch, TILE_THREADS, lds, c->stream>>>(T);
-  PYN_HIP(hipGetLastError());
-  *handled = true;
-  return PYN_OK;
+  T.aff = k.no_affine ? nullptr : c->d_aff;
+  T.lean = c->q1_gauss_standard && !k.no_lean ? 1 : 0;
 }
 
+// The patch-plan kernels: KLE on Q1 hexahedra (K, Rw), the scalar Laplacian on Q1 hexahedra and linear tetrahedra; parallelepiped
+// meshes take the affine forms (P.k_closed / P.rw_closed).  A compact Krhs is left to the completion pass.
+int pyn_assemble_patch(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P) {
+  double* const Krhs = P.krhs_pending ? nullptr : rq.Krhs;
+  if (rq.form == PYN_FORM_KLE) {
+    const PatchPlan& pl = c->plan[1];
+    KleArgs T = KleArgs();
+    patch_fill(c, k, pl, T);
+    T.H = c->quad[0].H;
+    T.wr = c->quad[1].w;
+    T.Hr = c->quad[1].H;
+    T.hrsr = c->quad[1].Hrs;
+    T.hcoor = c->quad[1].HrsCoo;
+    T.aff_rw = (T.aff && c->aff_rw_standard) ? 1 : 0;
+    T.ablate = k.kle_ablate;
+    T.alpha_d = rq.alpha_d;
+    T.alpha_w = rq.alpha_w;
+    const size_t lds = kle_lds_bytes(pl.maxrows, pl.maxlen);
+    T.K = rq.K;
+    T.Krhs = Krhs;
+    if (P.k_closed)
+      assemble_q1_hex_kle_affine_kernel<false><<<pl.npatch, KLE_AFF_THREADS, lds, c->stream>>>(T);
+    else
+      assemble_q1_hex_kle_tiled_kernel<0><<<pl.npatch, KLE_THREADS, lds, c->stream>>>(T);
+    if (rq.Rw) {
+      T.K = rq.Rw;
+      T.Krhs = nullptr;
+      if (P.rw_closed)
+        assemble_q1_hex_kle_affine_kernel<true><<<pl.npatch, KLE_AFF_THREADS, lds, c->stream>>>(T);
+      else
+        assemble_q1_hex_kle_tiled_kernel<1><<<pl.npatch, KLE_THREADS, lds, c->stream>>>(T);
+    }
+    PYN_HIP(hipGetLastError());
+    return PYN_OK;
+  }
+  const PatchPlan& pl = c->plan[0];
+  TileArgs T = TileArgs();
+  patch_fill(c, k, pl, T);
+  T.n_patch = pl.npatch;
+  T.A = rq.K;
+  T.Arhs = Krhs;
+  const size_t lds = (size_t)pl.maxrows * pl.maxlen * sizeof(double) + (size_t)pl.maxrows * 3 * sizeof(int);
+  if (c->nn == 4)
+    assemble_p1_tet_tiled_kernel<<<pl.npatch, TILE_THREADS, lds, c->stream>>>(T, c->quad[0].wsum);
+  else if (P.k_closed)
+    assemble_q1_hex_tiled_affine_kernel<<<pl.npatch, TILE_THREADS, lds, c->stream>>>(T);
+  else if (k.tiled_ablate == 1)   // diagnostics only: 1 = no LDS adds, 2 = no quadrature
+    assemble_q1_hex_tiled_kernel<1><<<pl.npatch, TILE_THREADS, lds, c->stream>>>(T);
+  else if (k.tiled_ablate == 2)
+    assemble_q1_hex_tiled_kernel<2><<<pl.npatch, TILE_THREADS, lds, c->stream>>>(T);
+  else
+    assemble_q1_hex_tiled_kernel<0><<<pl.npatch, TILE_THREADS, lds, c->stream>>>(T);
+  PYN_HIP(hipGetLastError());
+  return PYN_OK;
+}

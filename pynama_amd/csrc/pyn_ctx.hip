@@ -195,12 +195,23 @@ extern "C" int pyn_sync(pyn_ctx* c) {
   return PYN_OK;
 }
 
-int pyn_ensure_work(pyn_ctx* c, size_t bytes) {
-  if (bytes <= c->work_bytes) return PYN_OK;
-  if (c->d_work) PYN_HIP(hipFree(c->d_work));
-  c->d_work = nullptr;
-  PYN_HIP(hipMalloc((void**)&c->d_work, bytes));
-  c->work_bytes = bytes;
+int pyn_ensure_work(pyn_ctx* c, size_t bytes) { return pyn_grow(&c->d_work, &c->work_bytes, bytes); }
+
+// Kernel attributes belong to a device, so they are remembered per context (released with it): a process-wide "done" flag would
+// leave a second context on another device at the 64 KB default.  For kernels that always ask for the SAME size only: contexts of one
+// device share the attribute, so a kernel whose size follows the mesh (generic, patch plan) sets it at every launch / plan instead.
+int pyn_kernel_lds(pyn_ctx* c, const void* fn, size_t bytes) {
+  size_t& have = c->kern_lds[fn];
+  if (have >= bytes) return PYN_OK;
+  PYN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  have = bytes;
+  return PYN_OK;
+}
+
+int pyn_kernel_occupancy(pyn_ctx* c, const void* fn, int threads, size_t lds, int* per_cu) {
+  int& n = c->kern_occ[{fn, lds}];
+  if (!n) PYN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, lds));
+  *per_cu = n;
   return PYN_OK;
 }
 

@@ -7,7 +7,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <functional>
+#include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/pynama_hip.h"
@@ -341,13 +343,10 @@ struct pyn_ctx {
   double* d_work = nullptr;
   size_t work_bytes = 0;
   std::vector<hipEvent_t> prof_ev;  // event pool for per-kernel timing
-  // 1/diagonal target of the scalar assembly in flight (the K matrix's DMat::dinv) and whether a kernel filled it
-  double* asm_dinv = nullptr;
-  bool asm_dinv_written = false;
-  bool asm_rhs_clean = false;   // the Krhs / Arhs target of the assembly in flight holds zeros wherever this Dirichlet set leaves zeros
-  const int32_t* asm_rcrow = nullptr;      // ... is a COMPACT matrix: first block of every owned node row in it (-1: not stored), else null
-  const int32_t* asm_rcrow_fs = nullptr;   // the same for Krhsfs of the no-slip split
-  bool asm_krhs_pending = false;           // the kernel family that took K left the compact Krhs to the generic kernel (run_assembly)
+  int64_t asm_last[8] = {0};     // pyn_assemble_last: what the most recent numeric assembly launched (pyn_assemble.hip)
+  // per-context kernel attributes (pyn_kernel_lds / pyn_kernel_occupancy): a second context on another device sets its own
+  std::map<const void*, size_t> kern_lds;                      // dynamic-LDS limit this context has raised the kernel to
+  std::map<std::pair<const void*, size_t>, int> kern_occ;      // workgroups per CU of (kernel, dynamic LDS)
   // elements with an imposed node (the only ones that feed an imposed-column matrix), per Dirichlet set
   int32_t* d_esel = nullptr;
   int64_t n_esel = 0, esel_stamp = -1;
@@ -382,6 +381,15 @@ inline int pyn_lattice_kind(const pyn_ctx* c) {
 
 // ---- cross-TU helpers ---------------------------------------------------------------------
 int pyn_ensure_work(pyn_ctx* c, size_t bytes);
+inline int pyn_grow(double** p, size_t* have, size_t need) {   // a scratch buffer of at least `need` bytes (contents not kept)
+  if (need <= *have) return PYN_OK;
+  if (*p) PYN_HIP(hipFree(*p));
+  *p = nullptr;
+  *have = 0;
+  PYN_HIP(hipMalloc((void**)p, need));
+  *have = need;
+  return PYN_OK;
+}
 int pyn_halo_exchange(pyn_ctx* c, double* x, int bs);  // fills ghost part of x (stream ordered)
 int pyn_halo_exchange_on(pyn_ctx* c, double* x, int bs, hipStream_t st);
 int pyn_check_mat(pyn_ctx* c, int id, const char* what);
@@ -425,11 +433,8 @@ int pyn_mesh_all_affine(pyn_ctx* c, int* out);                        // pyn_ass
 inline bool pyn_has_comm(const pyn_ctx* c) { return c->comm != nullptr || c->shm != nullptr; }
 int pyn_allreduce_dev(pyn_ctx* c, double* dbuf, int n, int op, hipStream_t st);   // op 0 sum, 1 max; in place, device buffer
 int pyn_lattice_symbolic(pyn_ctx* c, bool* done);
-int pyn_assemble_lattice(pyn_ctx* c, double* A, double* Arhs, bool* handled);   // pyn_assemble_lattice.hip
-int pyn_assemble_kle_lattice(pyn_ctx* c, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
 bool pyn_q1_mixed_tables_standard(const double* w, const double* H, const double* Hrs);
 bool pyn_q1_gauss_tables_standard(const double* w, const double* H, const double* Hrs, const double* HrsCoo);   // pyn_assemble_march.hip
-int pyn_assemble_lattice_march(pyn_ctx* c, void* lat_args, int tile);   // general geometry, z-marching (pyn_assemble_march.hip)
 // second-order (ngl = 3) lattices (pyn_assemble_ho3.hip)
 void pyn_ho3_view(pyn_ctx* c);
 void pyn_ho3_release(pyn_ctx* c);
@@ -439,7 +444,6 @@ int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]);  
 // box lattices of order ngl >= 4 (pyn_matfree_ho.hip)
 void pyn_ho_view(pyn_ctx* c);
 void pyn_ho_release(pyn_ctx* c);
-int pyn_assemble_ho3_lattice(pyn_ctx* c, int form, double alpha_d, double alpha_w, double* K, double* Krhs, double* Rw, bool* handled);
 void pyn_ibm_release(pyn_ctx* c);   // pyn_ibm.hip: the marker set belongs to the mesh
 // dense LU shared by the direct solve, the coarsest multigrid level and the immersed-boundary force solve (pyn_direct.hip): piv holds 2 n + 1 ints
 int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n);
@@ -484,4 +488,101 @@ struct LinOp {
 // V-cycle z = M^-1 r whose level-0 products are prod0 (the assembled product or the matrix-free shell)
 int pyn_mg_ensure(pyn_ctx* c, DMat& A);
 int pyn_mg_vcycle(pyn_ctx* c, DMat& A, const double* r, double* z, const LinOp& prod0);
-int pyn_assemble_ho3_operator(pyn_ctx* c, int rule, int br, int bc, int nterms, const int32_t* terms, const double* coef, double* M, bool* handled);
+
+// ---- numeric assembly: request -> knobs, facts -> plan -> launch (pyn_assemble.hip) -------------------------------------------
+// Every entry point describes what it was asked for (AsmRequest), reads the environment once (asm_knobs), gathers what the choice
+// depends on (asm_facts), resolves the kernel family in one pure host function (asm_choose, exported as pyn_assemble_choose) and
+// launches from the plan through one switch (asm_run), which records what ran for pyn_assemble_last.
+enum AssemblyKind { AK_NONE = 0, AK_GENERIC = 1, AK_P1 = 2, AK_PATCH = 3, AK_LATTICE = 4, AK_MARCH = 5, AK_KLE_LATTICE = 6, AK_ROWRUN = 7 };
+constexpr int PYN_HO3_MAX_TERMS = 32;   // operator terms the row-run kernels carry in their arguments
+
+// The PYNAMA_* switches that steer the numeric assembly, read per assembly call (tests set them between calls).  F: flag, set or
+// not; I: integer with the value that stands for "not set".  The switches that act when a mesh or a graph is installed are read
+// there (DESIGN.md lists both groups).
+// PYN_LAT_FILL_KNOBS: the ones behind the lattice checks and argument fill, all that a matrix-free Q1 product reads (lat_fill_knobs).
+#define PYN_LAT_FILL_KNOBS(F, I)                                                                                                 \
+  F(no_affine, "PYNAMA_NO_AFFINE") F(no_lean, "PYNAMA_NO_LEAN") F(no_std_lattice, "PYNAMA_NO_STD_LATTICE")                       \
+  I(lattice_ablate, "PYNAMA_LATTICE_ABLATE", 0)
+#define PYN_ASM_KNOBS(F, I)                                                                                                      \
+  PYN_LAT_FILL_KNOBS(F, I) F(no_lean_plan, "PYNAMA_NO_LEAN_PLAN") F(no_p1, "PYNAMA_NO_P1")                                       \
+  F(no_p1_tiled, "PYNAMA_NO_P1_TILED") F(no_ho, "PYNAMA_NO_HO") F(no_ho_mfma, "PYNAMA_NO_HO_MFMA")                               \
+  F(no_dinv, "PYNAMA_NO_ASM_DINV") F(rhs_full_write, "PYNAMA_RHS_FULL_WRITE")                                                    \
+  F(no_kle_lattice, "PYNAMA_NO_KLE_LATTICE") F(no_kle_general, "PYNAMA_NO_KLE_GENERAL") F(no_march, "PYNAMA_NO_MARCH")           \
+  F(no_ho3_lattice, "PYNAMA_NO_HO3_LATTICE") F(no_ho3_operator, "PYNAMA_NO_HO3_OPERATOR") F(ho3_require, "PYNAMA_HO3_REQUIRE")   \
+  F(ho3_no_diag, "PYNAMA_HO3_NO_DIAG") F(ho3_no_pstd, "PYNAMA_HO3_NO_PSTD") F(march_stamps, "PYNAMA_MARCH_STAMPS")               \
+  I(lattice_tile, "PYNAMA_LATTICE_TILE", -1) I(march_tile, "PYNAMA_MARCH_TILE", -1)                                             \
+  I(kle_lattice_tile, "PYNAMA_KLE_LATTICE_TILE", -1) I(march_zlen, "PYNAMA_MARCH_ZLEN", -1) I(ho3_run, "PYNAMA_HO3_RUN", 0)     \
+  I(ho3_wgs_per_cu, "PYNAMA_HO3_WGS_PER_CU", -1) I(ho3_grid, "PYNAMA_HO3_GRID", -1) I(kle_ablate, "PYNAMA_KLE_ABLATE", 0)       \
+  I(tiled_ablate, "PYNAMA_TILED_ABLATE", 0) I(ho3_ablate, "PYNAMA_HO3_ABLATE", 0)
+struct AsmKnobs {
+#define PYN_F(f, e) bool f = false;
+#define PYN_I(f, e, d) int f = d;
+  PYN_ASM_KNOBS(PYN_F, PYN_I)
+#undef PYN_F
+#undef PYN_I
+};
+AsmKnobs asm_knobs();        // the one reader of the switches above ...
+AsmKnobs lat_fill_knobs();   // ... and of the four a matrix-free Q1 product reads, per product (the rest at their defaults)
+
+// What the choice depends on beyond the request (asm_facts fills it; the ones that cost device work only for the family that reads
+// them: mesh_affine, lat_std_ok, ho3_affine stay -1 "not checked" otherwise)
+#define PYN_ASM_FACTS(X)                                                                                                         \
+  X(dim) X(nn) X(nc) X(ngl) X(ngp0) X(ngp1) X(ngp2) X(const_grad) X(q1_gauss_standard) X(q1_red_standard) X(aff_standard)        \
+  X(aff_rw_standard) X(mesh_affine) X(lat_valid) X(lat_std_ok) X(ho3_valid) X(ho3_affine) X(ho3_tabs_nn) X(ho3_tabs_ok0)         \
+  X(ho3_tabs_ok1) X(ho3_tabs_ok2) X(plan0_present) X(plan0_user) X(plan0_unfit) X(plan1_present) X(plan1_user) X(plan1_unfit)
+struct AsmFacts {
+#define PYN_X(f) int f = 0;
+  PYN_ASM_FACTS(PYN_X)
+#undef PYN_X
+  // this assembly has run the row-run geometry pre-pass (asm_facts launches it once) / tried the automatic patch plan, which left none
+  bool geom_done = false, plan_declined = false;
+};
+
+// What an entry point was asked for, handed by reference to the launchers, + what they report back
+struct AsmRequest {
+  int form = 0, variant = 1;
+  double alpha_d = 0.0, alpha_w = 0.0;
+  double *K = nullptr, *Krhs = nullptr, *Rw = nullptr, *Rd = nullptr;   // value targets (scalar forms: K = A, Krhs = Arhs; operators: K = M)
+  const int32_t* rcrow = nullptr;   // the Krhs target is COMPACT: first block of every owned node row in it (-1: not stored), else null
+  int64_t krhs_blocks = 0;          // blocks it stores
+  bool rhs_clean = false;           // the Krhs target holds zeros wherever this Dirichlet set leaves zeros
+  double* dinv = nullptr;           // 1 / diagonal target (the K matrix's DMat::dinv), null: not wanted
+  int op_rule = 0, op_br = 0, op_bc = 0, op_nterms = 0;   // PYN_FORM_OPERATOR
+  const int32_t* op_terms = nullptr;                      // host copies [nterms][3], [nterms]
+  const double* op_coef = nullptr;
+  // results
+  bool dinv_written = false;        // a kernel filled dinv
+  bool krhs_completed = false;      // the compact Krhs was left to the completion pass (generic kernel over the imposed elements)
+  int generic = 0;                  // sub-variant of the last generic launch
+};
+
+struct AsmPlan {
+  AssemblyKind kind = AK_GENERIC;
+  int shape = 0;        // tile / shape id as the PYNAMA_*_TILE tables number it (ids they do not number: 0, the default arm); AK_ROWRUN: rows per run
+  bool k_closed = false, rw_closed = false;   // the K / Rw target takes the affine closed forms (false: quadrature, or no such target)
+  bool kle_general = false;   // AK_KLE_LATTICE: the general-geometry kernel (closed form of the 2x2x2 rule), not the parallelepipeds'
+  int generic = 0;      // AK_GENERIC: 1 64 threads, 2 256 threads with the points in LDS, 3 ... in global scratch, 4 staged high order, 5 MFMA
+  bool krhs_pending = false;   // the family cannot address the compact Krhs: the completion pass fills it
+  bool dinv = false;    // 1 / diagonal leaves with the store phase
+  // rowrun_candidate: the request is one the row-run view is tried for (PYNAMA_HO3_REQUIRE); want_plan: the patch kernels' turn on a
+  // graph without a plan -- the actor builds the automatic one and asks again
+  bool rowrun_candidate = false, want_plan = false;
+};
+AsmPlan asm_choose(const AsmRequest& rq, const AsmFacts& f, const AsmKnobs& k);
+int asm_facts(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, AsmFacts* f);
+// the launchers behind the plan, each next to its kernels; called only when chosen
+int pyn_assemble_ho3_lattice(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P);    // AK_ROWRUN, operators included
+int pyn_assemble_lattice(pyn_ctx* c, AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P);              // AK_LATTICE, AK_MARCH
+int pyn_assemble_lattice_march(pyn_ctx* c, const AsmKnobs& k, void* lat_args, int shape);               // pyn_assemble_march.hip
+int pyn_assemble_kle_lattice(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P);    // AK_KLE_LATTICE
+int pyn_assemble_patch(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P);          // AK_PATCH
+int pyn_patch_plan_default(pyn_ctx* c, int kind);   // the automatic plan of a graph without one; leaves none where it does not apply or fit
+int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k);   // c->mesh_affine, c->lat.std_ok (once per mesh / graph)
+int pyn_ho3_prepare(pyn_ctx* c);                         // geometry pre-pass of a row-run assembly (+ c->ho3.affine / diag, once per mesh)
+int pyn_ho3_run_length(int dim, int ngl, bool op, int knob);   // rows per run of the row-run kernels
+// per-context kernel attributes (pyn_ctx.hip): raise fn's dynamic-LDS limit unless this context already set at least `bytes` (kernels
+// of one fixed size only); workgroups per CU of (fn, lds), asked once
+int pyn_kernel_lds(pyn_ctx* c, const void* fn, size_t bytes);
+int pyn_kernel_occupancy(pyn_ctx* c, const void* fn, int threads, size_t lds, int* per_cu);
+template <typename F>
+inline int pyn_kernel_lds(pyn_ctx* c, F* fn, size_t bytes) { return pyn_kernel_lds(c, reinterpret_cast<const void*>(fn), bytes); }

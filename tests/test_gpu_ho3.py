@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
-from tests.util import mat_to_scipy, rel_err, sp_rel_err
+from tests.util import assert_assembled, mat_to_scipy, rel_err, sp_rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -97,12 +97,14 @@ def test_kle_vs_oracle_and_generic(lib, nelem, upper):
     ctx = make_ctx(lib, mesh, boundary_mask(mesh), dim)
     K, Krhs, Rw = ctx.mat_create(dim, dim), ctx.mat_create(dim, dim), ctx.mat_create(dim, dw)
     ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, -1, variant=1)
+    assert_assembled(ctx, lib.AK_ROWRUN, shape=32 if dim == 2 else 4, k_closed=1, rw_closed=1, krhs_completed=0)
     ref = fo.assemble_kle_freeslip(mesh, fo.Tables(3, dim))
     got = {"K": mat_to_scipy(ctx, K, dim, dim), "Krhs": mat_to_scipy(ctx, Krhs, dim, dim), "Rw": mat_to_scipy(ctx, Rw, dim, dw)}
     for k in ("K", "Krhs", "Rw"):
         assert sp_rel_err(got[k], ref[k]) < FP_TOL, k
     K0, Kr0, Rw0 = ctx.mat_create(dim, dim), ctx.mat_create(dim, dim), ctx.mat_create(dim, dw)
     ctx.assemble_kle(1e3, 1e2, K0, Kr0, Rw0, -1, variant=0)
+    assert_assembled(ctx, lib.AK_GENERIC, generic=2)
     for a, b, br, bc in ((K, K0, dim, dim), (Krhs, Kr0, dim, dim), (Rw, Rw0, dim, dw)):
         assert rel_err(ctx.mat_values(a, br, bc), ctx.mat_values(b, br, bc)) < FP_TOL       # entry by entry, storage order
     ctx.close()
@@ -121,6 +123,7 @@ def test_run_lengths(lib, nelem, run):
         ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, -1)
     finally:
         del os.environ["PYNAMA_HO3_RUN"]
+    assert_assembled(ctx, lib.AK_ROWRUN, shape=run)
     ref = fo.assemble_kle_freeslip(mesh, fo.Tables(3, dim))
     assert sp_rel_err(mat_to_scipy(ctx, K, dim, dim), ref["K"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Krhs, dim, dim), ref["Krhs"]) < FP_TOL
@@ -149,6 +152,7 @@ def test_workgroups_walk_many_runs(lib, nelem, ngl, grid):
         ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, -1)
     finally:
         del os.environ["PYNAMA_HO3_GRID"], os.environ["PYNAMA_HO3_REQUIRE"]
+    assert_assembled(ctx, lib.AK_ROWRUN, krhs_completed=0, count=2)      # the compact Krhs is addressed by the kernel itself
     ref = oracle_kle(mesh, mask, ngl=ngl)
     assert sp_rel_err(mat_to_scipy(ctx, K, dim, dim), ref["K"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Krhs, dim, dim), ref["Krhs"]) < FP_TOL
@@ -174,6 +178,7 @@ def test_dirichlet_routing(lib, nelem, kind):
     ctx = make_ctx(lib, mesh, mask, dim)
     K, Krhs, Rw = ctx.mat_create(dim, dim), ctx.mat_create(dim, dim), ctx.mat_create(dim, dw)
     ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, -1)
+    assert_assembled(ctx, lib.AK_ROWRUN)
     ref = oracle_kle(mesh, mask if mask is not None else np.zeros((mesh.n_node, dim), np.uint8))
     assert sp_rel_err(mat_to_scipy(ctx, K, dim, dim), ref["K"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Krhs, dim, dim), ref["Krhs"]) < FP_TOL
@@ -199,6 +204,10 @@ def test_sheared_mesh_and_nonaffine_fallback(lib, dim):
         ctx = make_ctx(lib, mesh, boundary_mask(mesh), dim)
         K, Krhs, Rw = ctx.mat_create(dim, dim), ctx.mat_create(dim, dim), ctx.mat_create(dim, dw)
         ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, -1)
+        if bend:
+            assert_assembled(ctx, lib.AK_GENERIC, generic=2, k_closed=0, rw_closed=0)
+        else:
+            assert_assembled(ctx, lib.AK_ROWRUN, k_closed=1, rw_closed=1)
         ref = fo.assemble_kle_freeslip(mesh, fo.Tables(3, dim))
         assert sp_rel_err(mat_to_scipy(ctx, K, dim, dim), ref["K"]) < FP_TOL, bend
         assert sp_rel_err(mat_to_scipy(ctx, Krhs, dim, dim), ref["Krhs"]) < FP_TOL, bend
@@ -510,12 +519,14 @@ def test_operators_on_lattices(lib, nelem, ngl):
         br, bc, terms, coef = ops[name]
         m, m0 = ctx.mat_create(br, bc), ctx.mat_create(br, bc)
         ctx.assemble_operator(lib.Q_NODAL, terms, coef, m)
+        assert_assembled(ctx, lib.AK_ROWRUN, shape={(2, 2): 32, (3, 2): 8, (2, 3): 16, (3, 3): 2}[dim, ngl], k_closed=1)
         t_fast = ctx.timers()["assemble_ms"]
         os.environ["PYNAMA_NO_HO3_OPERATOR"] = "1"
         try:
             ctx.assemble_operator(lib.Q_NODAL, terms, coef, m0)
         finally:
             del os.environ["PYNAMA_NO_HO3_OPERATOR"]
+        assert_assembled(ctx, lib.AK_GENERIC, generic=1 if ngl == 2 else 2)
         assert rel_err(ctx.mat_values(m, br, bc), ctx.mat_values(m0, br, bc)) < FP_TOL, (name, t_fast)
         vs = ctx.vec_create(br)
         ctx.vec_set(vs, np.repeat(1.0 / w, br))

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
-from tests.util import mat_to_scipy, rel_err, sp_rel_err
+from tests.util import assert_assembled, mat_to_scipy, rel_err, sp_rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -150,12 +150,15 @@ def test_assemble_tiled_tiles_and_no_bc(lib, tile):
     ctx.patch_plan_set(*tile_plan(mesh, tile))
     A, Arhs = ctx.mat_create(1, 1), ctx.mat_create(1, 1)
     ctx.assemble_scalar(lib.FORM_LAPLACE, A, Arhs, variant=1)
+    assert_assembled(ctx, lib.AK_PATCH, k_closed=0, krhs_completed=0, dinv=0)     # the user plan keeps the lattice family out
     assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref["A"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Arhs, 1, 1), ref["Arhs"]) < FP_TOL
     ctx.assemble_scalar(lib.FORM_LAPLACE, A, -1, variant=1)
+    assert_assembled(ctx, lib.AK_PATCH)
     assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref["A"]) < FP_TOL
     ctx.bc_set(1, None)
     ctx.assemble_scalar(lib.FORM_LAPLACE, A, -1, variant=1)
+    assert_assembled(ctx, lib.AK_PATCH, count=3)
     assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref0["A"]) < FP_TOL
     ctx.close()
 
@@ -175,6 +178,7 @@ def test_assemble_tiled_scattered_patches(lib):
     ctx.patch_plan_set(ptr, rows)
     A, Arhs = ctx.mat_create(1, 1), ctx.mat_create(1, 1)
     ctx.assemble_scalar(lib.FORM_LAPLACE, A, Arhs, variant=1)
+    assert_assembled(ctx, lib.AK_PATCH, k_closed=0)
     assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref["A"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Arhs, 1, 1), ref["Arhs"]) < FP_TOL
     ctx.close()
@@ -206,6 +210,8 @@ def test_assemble_kle_tiled_variants(lib, kind):
     ctx.patch_plan_set(ptr, rows, kind=1)
     K, Krhs, Rw = ctx.mat_create(3, 3), ctx.mat_create(3, 3), ctx.mat_create(3, 3)
     ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, -1, variant=1)
+    closed = 1 if kind == "uniform" else 0
+    assert_assembled(ctx, lib.AK_PATCH, k_closed=closed, rw_closed=closed, krhs_completed=0)
     # oracle with the same per-DOF mask
     tb = fo.Tables(2, 3)
     Ke, Rwe, _ = fo.elem_kle_matrices(tb, mesh.corners())
@@ -230,8 +236,10 @@ def test_assemble_kle_tiled_variants(lib, kind):
     # generic kernel agrees too (same per-DOF routing), and K alone (no Krhs / Rw) works
     K2 = ctx.mat_create(3, 3)
     ctx.assemble_kle(1e3, 1e2, K2, -1, -1, -1, variant=1)
+    assert_assembled(ctx, lib.AK_PATCH, k_closed=closed, rw_closed=0)
     assert sp_rel_err(mat_to_scipy(ctx, K2, 3, 3), Kref) < FP_TOL
     ctx.assemble_kle(1e3, 1e2, K2, -1, -1, -1, variant=0)
+    assert_assembled(ctx, lib.AK_GENERIC, generic=1)
     assert sp_rel_err(mat_to_scipy(ctx, K2, 3, 3), Kref) < FP_TOL
     ctx.close()
 
@@ -507,6 +515,7 @@ def test_assemble_tiled_affine_shortcut(lib, kind):
     ctx.patch_plan_set(*tile_plan(mesh))
     A, Arhs = ctx.mat_create(1, 1), ctx.mat_create(1, 1)
     ctx.assemble_scalar(lib.FORM_LAPLACE, A, Arhs, variant=1)
+    assert_assembled(ctx, lib.AK_PATCH, k_closed=0 if kind == "mixed" else 1, krhs_completed=0, dinv=0)
     assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref["A"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Arhs, 1, 1), ref["Arhs"]) < FP_TOL
     ctx.close()
@@ -582,6 +591,7 @@ def test_assemble_kle_noslip_vs_oracle(lib, nelem, ns, dr):
               ("Kfs", dim, dim), ("Krhsfs", dim, dim), ("Rwfs", dim, dw), ("Rdfs", dim, 1)]
     ids = [ctx.mat_create(br, bc) for _, br, bc in shapes]
     ctx.assemble_kle_noslip(1e3, 1e2, ids)
+    assert_assembled(ctx, lib.AK_GENERIC, generic=1, krhs_completed=0, dinv=0)
     for (name, br, bc), mid in zip(shapes, ids):
         assert sp_rel_err(mat_to_scipy(ctx, mid, br, bc), ref[name]) < FP_TOL, name
     # K + Kfs is the operator with only the doubly imposed DOFs eliminated (base_problem.py:318)
@@ -719,13 +729,18 @@ def test_assemble_lattice_kernel(lib, tile, nelem, jitter):
         rp_o, ci_o = fo.node_graph(mesh)
         assert np.array_equal(rp, rp_o) and np.array_equal(ci, ci_o)
         A, Arhs = ctx.mat_create(1, 1), ctx.mat_create(1, 1)
+        general = jitter > 0 and min(nelem) >= 2          # (the jitter moves interior nodes: [2, 1, 3] has none and stays a box)
+        tiles = dict(shape=tile, k_closed=0 if general else 1, dinv=1, krhs_completed=0)   # a tile request keeps the tile kernel
         ctx.assemble_scalar(lib.FORM_LAPLACE, A, Arhs)
+        assert_assembled(ctx, lib.AK_LATTICE, **tiles)
         assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref["A"]) < FP_TOL
         assert sp_rel_err(mat_to_scipy(ctx, Arhs, 1, 1), ref["Arhs"]) < FP_TOL
         ctx.assemble_scalar(lib.FORM_LAPLACE, A, -1)
+        assert_assembled(ctx, lib.AK_LATTICE, **tiles)
         assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref["A"]) < FP_TOL
         ctx.bc_set(1, None)
         ctx.assemble_scalar(lib.FORM_LAPLACE, A, -1)
+        assert_assembled(ctx, lib.AK_LATTICE, **tiles)
         assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref0["A"]) < FP_TOL
         # an interior Dirichlet node set (not the lattice boundary): the mask is data, not topology
         rng = np.random.default_rng(5)
@@ -734,12 +749,19 @@ def test_assemble_lattice_kernel(lib, tile, nelem, jitter):
         mask[some] = 1
         ctx.bc_set(1, mask)
         ctx.assemble_scalar(lib.FORM_LAPLACE, A, Arhs)
+        assert_assembled(ctx, lib.AK_LATTICE, **tiles)
         ref2 = fo.assemble_scalar(mesh, fo.Tables(2, 3), "laplace", dirichlet=some)
+        assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref2["A"]) < FP_TOL
+        assert sp_rel_err(mat_to_scipy(ctx, Arhs, 1, 1), ref2["Arhs"]) < FP_TOL
+        # without a tile request: parallelepipeds take the default tile, general geometry the z-marching kernel
+        del os.environ["PYNAMA_LATTICE_TILE"]
+        ctx.assemble_scalar(lib.FORM_LAPLACE, A, Arhs)
+        assert_assembled(ctx, lib.AK_MARCH if general else lib.AK_LATTICE, shape=0, k_closed=0 if general else 1, dinv=1)
         assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref2["A"]) < FP_TOL
         assert sp_rel_err(mat_to_scipy(ctx, Arhs, 1, 1), ref2["Arhs"]) < FP_TOL
         ctx.close()
     finally:
-        del os.environ["PYNAMA_LATTICE_TILE"]
+        os.environ.pop("PYNAMA_LATTICE_TILE", None)
 
 
 @pytest.mark.parametrize("kind", ["sheared", "mixed", "stretched"])
@@ -908,8 +930,10 @@ def test_assemble_kle_lattice_kernel(lib, tile, kind):
         assert ctx.mesh_topology()[0] == "lattice"
         K, Krhs, Rw = ctx.mat_create(3, 3), ctx.mat_create(3, 3), ctx.mat_create(3, 3)
         ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, -1)
+        assert_assembled(ctx, lib.AK_KLE_LATTICE, shape=tile, k_closed=1, rw_closed=1, krhs_completed=0)   # parallelepipeds, every kind
         K2 = ctx.mat_create(3, 3)
         ctx.assemble_kle(1e3, 1e2, K2, -1, -1, -1)
+        assert_assembled(ctx, lib.AK_KLE_LATTICE, shape=tile, k_closed=1, rw_closed=0)
         tb = fo.Tables(2, 3)
         Ke, Rwe, _ = fo.elem_kle_matrices(tb, mesh.corners())
         vdof = fo.dof_indices(mesh.conn, 3)
@@ -931,11 +955,13 @@ def test_assemble_kle_lattice_kernel(lib, tile, kind):
         assert sp_rel_err(mat_to_scipy(ctx, Rw, 3, 3), Rwref) < FP_TOL
         Rw2 = ctx.mat_create(3, 3)
         ctx.assemble_kle(1e3, 1e2, -1, -1, Rw2, -1)          # Rw alone
+        assert_assembled(ctx, lib.AK_KLE_LATTICE, shape=tile, k_closed=0, rw_closed=1)
         assert sp_rel_err(mat_to_scipy(ctx, Rw2, 3, 3), Rwref) < FP_TOL
         # and the patch-plan kernels (explicit plan) give the same matrices
         ctx.patch_plan_set(*tile_plan(mesh, (3, 3, 3)), kind=1)
         K3, Rw3 = ctx.mat_create(3, 3), ctx.mat_create(3, 3)
         ctx.assemble_kle(1e3, 1e2, K3, -1, Rw3, -1)
+        assert_assembled(ctx, lib.AK_PATCH, shape=0, k_closed=1, rw_closed=1)
         assert sp_rel_err(mat_to_scipy(ctx, K3, 3, 3), Kref) < FP_TOL
         assert sp_rel_err(mat_to_scipy(ctx, Rw3, 3, 3), Rwref) < FP_TOL
         ctx.close()
@@ -965,6 +991,8 @@ def test_kle_lattice_kernel_on_rank_slabs(lib, size, nz, jitter):
         ctx.csr_symbolic()
         K, Kr, Rw = ctx.mat_create(3, 3), ctx.mat_create(3, 3), ctx.mat_create(3, 3)
         ctx.assemble_kle(1e3, 1e2, K, Kr, Rw, -1)
+        closed = 0 if jitter else 1          # general geometry: the one-shape kernel with the closed form of the 2x2x2 rule
+        assert_assembled(ctx, lib.AK_KLE_LATTICE, shape=0, k_closed=closed, rw_closed=closed)
         cols = dom._local2global(np.arange(dom.nLocal))
         rows3 = (np.arange(dom.rStart, dom.rEnd)[:, None] * 3 + np.arange(3)).ravel()
         cols3 = (cols[:, None] * 3 + np.arange(3)).ravel()
@@ -1291,11 +1319,13 @@ def test_assembly_emits_jacobi_diagonal(lib, jitter, tile):
             ctx = make_ctx(lib, mesh, 2, bc_ndof=1, bc_nodes=some)
             A = ctx.mat_create(1, 1)
             ctx.assemble_scalar(lib.FORM_LAPLACE, A, -1)
+            assert_assembled(ctx, lib.AK_LATTICE if tile or not jitter else lib.AK_MARCH, dinv=0 if no_dinv else 1)
             vb, vx = ctx.vec_create(1), ctx.vec_create(1)
             ctx.vec_set(vb, b)
             ctx.solve(A, vb, vx, fixed_iters=25, norm_type=lib.NORM_UNPRECONDITIONED)
             x1 = ctx.vec_get(vx, 1).copy()
             ctx.assemble_scalar(lib.FORM_LAPLACE, A, -1)      # second version of the same matrix
+            assert_assembled(ctx, lib.AK_LATTICE if tile or not jitter else lib.AK_MARCH, dinv=0 if no_dinv else 1, count=2)
             ctx.solve(A, vb, vx, fixed_iters=25, norm_type=lib.NORM_UNPRECONDITIONED)
             x2 = ctx.vec_get(vx, 1)      # (LDS atomics: the summation order of an entry, hence its last bit, varies between launches)
             assert np.abs(x1 - x2).max() <= 1e-12 * np.abs(x1).max()
@@ -1325,6 +1355,7 @@ def test_march_kernel_shapes_vs_oracle(lib, tile):
         ctx = make_ctx(lib, mesh, 2, bc_ndof=1, bc_nodes=some)
         A, Arhs = ctx.mat_create(1, 1), ctx.mat_create(1, 1)
         ctx.assemble_scalar(lib.FORM_LAPLACE, A, Arhs)
+        assert_assembled(ctx, lib.AK_MARCH, shape=int(tile), k_closed=0, dinv=1, krhs_completed=0)
         assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref["A"]) < FP_TOL
         assert sp_rel_err(mat_to_scipy(ctx, Arhs, 1, 1), ref["Arhs"]) < FP_TOL
         ctx.close()
@@ -1421,3 +1452,72 @@ def test_csr_product_equals_sell_image_product(lib, nelem):
             os.environ.pop("PYNAMA_SELL_IMAGE", None)
     assert np.abs(out["csr"][1] - out["image"][1]).max() <= 1e-9 * np.abs(out["image"][1]).max()
     assert abs(out["csr"][2] - out["image"][2]) <= 1
+
+
+# ---- the record of what ran equals the chooser's answer for the facts of the context -----------------------------------------
+def _permuted(mesh, seed=4):
+    perm = np.random.default_rng(seed).permutation(mesh.n_node)
+    mesh.conn = perm[mesh.conn].astype(np.int32)
+    mesh.xyz = mesh.xyz[np.argsort(perm)]
+    mesh.boundary = np.sort(perm[mesh.boundary])
+    return mesh
+
+
+@pytest.mark.parametrize("name", ["q1_3d", "q1_3d_jitter", "q1_3d_general", "q1_2d", "ngl3_2d", "ngl3_3d", "ngl4_2d", "tets",
+                                  "q1_3d_permuted"])
+def test_assemble_last_matches_choose(lib, name):
+    """assemble the scalar Laplacian and K / Krhs / Rw once on a tiny mesh of every family, feed the facts of the context -- read back
+    through the ABI where it reports them, known from how the mesh was made otherwise -- to the host chooser, and compare its answer
+    with the record of what ran"""
+    from pynama_amd.elements.simplex import Simplex
+    from pynama_amd.elements.spectral import Spectral
+    nelem, ngl, jitter = {"q1_3d": ([2, 1, 3], 2, 0.0), "q1_3d_jitter": ([2, 1, 3], 2, 0.2), "q1_3d_general": ([2, 2, 3], 2, 0.2),
+                          "q1_2d": ([3, 2], 2, 0.0),
+                          "ngl3_2d": ([3, 2], 3, 0.0), "ngl3_3d": ([2, 2, 2], 3, 0.0), "ngl4_2d": ([2, 2], 4, 0.0),
+                          "tets": ([1, 1, 1], 2, 0.0), "q1_3d_permuted": ([2, 1, 3], 2, 0.0)}[name]
+    dim = len(nelem)
+    if name == "tets":
+        mesh = fo.simplex_box_mesh(nelem, [0.0] * dim, [1.0] * dim)
+        assert mesh.n_elem == 6
+        tables = Simplex(dim).deviceTables()
+    else:
+        mesh = fo.box_mesh(nelem, [0.0] * dim, [1.0, 0.8, 1.1][:dim], ngl, jitter=jitter)
+        if name == "q1_3d_permuted":
+            mesh = _permuted(mesh)
+        tables = Spectral(ngl, dim).deviceTables()
+    ctx = lib.Context(0)
+    ctx.mesh_set(dim, mesh.conn, mesh.xyz)
+    for t in tables:
+        ctx.tables_set(*t)
+    ctx.csr_symbolic()
+    topo = ctx.mesh_topology()[0]
+    assert topo == {"q1_3d": "lattice", "q1_3d_jitter": "lattice", "q1_3d_general": "lattice", "q1_2d": "lattice-q1-2d", "ngl3_2d": "lattice-ngl3",
+                    "ngl3_3d": "lattice-ngl3"}.get(name, "general")
+    nn = mesh.conn.shape[1]
+    hex8 = dim == 3 and nn == 8
+    affine = 0 if jitter and min(nelem) >= 2 else 1      # the jitter moves interior nodes: [2, 1, 3] has none and stays a box
+    facts = dict(dim=dim, nn=nn, nc=dim + 1 if name == "tets" else 2 ** dim, ngl=ngl, const_grad=name == "tets",
+                 q1_gauss_standard=hex8, q1_red_standard=hex8, aff_standard=hex8, aff_rw_standard=hex8,
+                 mesh_affine=affine if hex8 else -1, lat_valid=topo == "lattice", lat_std_ok=1 if topo == "lattice" else -1,
+                 ho3_valid=topo != "general", ho3_affine=affine if topo.startswith("lattice-") else -1, ho3_tabs_nn=nn,
+                 ho3_tabs_ok0=topo != "general", ho3_tabs_ok1=topo != "general", ho3_tabs_ok2=topo != "general")
+    for t in tables:
+        facts["ngp%d" % t[0]] = np.size(t[1])
+    dw = 1 if dim == 2 else 3
+    mask = np.zeros((mesh.n_node, dim), np.uint8)
+    mask[mesh.boundary] = 1
+    mats = [ctx.mat_create(1, 1), ctx.mat_create(1, 1), ctx.mat_create(dim, dim), ctx.mat_create(dim, dim), ctx.mat_create(dim, dw)]
+    for form in (lib.FORM_LAPLACE, lib.FORM_KLE):
+        if form == lib.FORM_KLE:
+            ctx.bc_set(dim, mask)
+            ctx.assemble_kle(1e3, 1e2, *mats[2:], -1)
+        else:
+            ctx.bc_set(1, np.ascontiguousarray(mask[:, :1]))
+            ctx.assemble_scalar(form, *mats[:2])
+        for kd in (0, 1):      # after the assembly: it builds the automatic plan of a graph without one
+            facts["plan%d_present" % kd] = ctx.patch_plan_info(kd)[0] > 0
+        want = lib.assemble_choose(dict(form=form, K=1, Krhs=1, Rw=form == lib.FORM_KLE), facts)
+        last = ctx.assemble_last()
+        assert {k: last[k] for k in want if k in last} == {k: v for k, v in want.items() if k in last}, (name, form, want, last)
+    assert last["count"] == 2
+    ctx.close()

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import fem_oracle as fo
-from tests.util import mat_to_scipy, rel_err, sp_rel_err
+from tests.util import assert_assembled, mat_to_scipy, rel_err, sp_rel_err
 
 pytestmark = pytest.mark.gpu
 FP_TOL = 2e-13
@@ -58,6 +58,13 @@ def test_kle_compact_krhs(lib, nelem, ngl, jitter, variant, plan):
         ctx.patch_plan_set(*tile_plan(mesh, (4, 3, 3)), kind=1)
     K, Krhs, Kfull = ctx.mat_create(dim, dim), ctx.mat_create_rhs(dim, dim), ctx.mat_create(dim, dim)
     ctx.assemble_kle(1e3, 1e2, K, Krhs, -1, -1, variant=variant)
+    if variant == 0 or ngl > 3 or (dim == 2 and jitter):
+        kind = lib.AK_GENERIC            # addresses the compact matrix itself, like the row-run and the KLE lattice kernels
+    elif ngl == 3:
+        kind = lib.AK_ROWRUN
+    else:
+        kind = lib.AK_PATCH if plan else lib.AK_KLE_LATTICE
+    assert_assembled(ctx, kind, krhs_completed=1 if plan else 0)
     ref = fo.assemble_kle_freeslip(mesh, fo.Tables(ngl, dim))
     assert sp_rel_err(mat_to_scipy(ctx, K, dim, dim), ref["K"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Krhs, dim, dim), ref["Krhs"]) < FP_TOL      # pyn_mat_get_values returns the graph's layout
@@ -74,7 +81,9 @@ def test_kle_compact_krhs(lib, nelem, ngl, jitter, variant, plan):
     assert rel_err(ctx.vec_get(vy, dim), ref["Krhs"] @ v) < 1e-13
     # a second assembly into the same compact matrix, and the same values as a matrix with the graph's full pattern
     ctx.assemble_kle(1e3, 1e2, K, Krhs, -1, -1, variant=variant)
+    assert_assembled(ctx, kind, krhs_completed=1 if plan else 0)
     ctx.assemble_kle(1e3, 1e2, K, Kfull, -1, -1, variant=variant)
+    assert_assembled(ctx, kind, krhs_completed=0)
     assert rel_err(ctx.mat_values(Krhs, dim, dim), ctx.mat_values(Kfull, dim, dim)) < FP_TOL
     with pytest.raises(lib.PynamaHipError):
         ctx.solve(Krhs, vx, vy)
@@ -126,6 +135,10 @@ def test_scalar_compact_arhs(lib, nelem, jitter, variant):
     ctx = make_ctx(lib, mesh, 2, mask, 1)
     A, Ar = ctx.mat_create(1, 1), ctx.mat_create_rhs(1, 1)
     ctx.assemble_scalar(lib.FORM_LAPLACE, A, Ar, variant=variant)
+    if variant == 0 or dim == 2:         # (2-D: the jittered quadrilaterals are no parallelograms, the row-run kernels stand back)
+        assert_assembled(ctx, lib.AK_GENERIC, krhs_completed=0)
+    else:
+        assert_assembled(ctx, lib.AK_MARCH if jitter else lib.AK_LATTICE, krhs_completed=1)
     ref = fo.assemble_scalar(mesh, fo.Tables(2, dim), "laplace", dirichlet=mesh.boundary)
     assert sp_rel_err(mat_to_scipy(ctx, A, 1, 1), ref["A"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Ar, 1, 1), ref["Arhs"]) < FP_TOL
@@ -145,6 +158,7 @@ def test_noslip_split_with_compact_krhs_and_krhsfs(lib):
     ids = [ctx.mat_create(3, 3), ctx.mat_create_rhs(3, 3), ctx.mat_create(3, 3), ctx.mat_create(3, 1),
            ctx.mat_create(3, 3), ctx.mat_create_rhs(3, 3), ctx.mat_create(3, 3), ctx.mat_create(3, 1)]
     ctx.assemble_kle_noslip(1e3, 1e2, ids)
+    assert_assembled(ctx, lib.AK_GENERIC, krhs_completed=0)      # the split's kernel addresses both compact matrices itself
     ref = fo.assemble_kle_noslip(mesh, fo.Tables(2, 3), cls)
     for k, (name, bc) in enumerate((("K", 3), ("Krhs", 3), ("Rw", 3), ("Rd", 1), ("Kfs", 3), ("Krhsfs", 3), ("Rwfs", 3), ("Rdfs", 1))):
         assert sp_rel_err(mat_to_scipy(ctx, ids[k], 3, bc), ref[name]) < FP_TOL, name
@@ -205,6 +219,7 @@ def test_rank_slabs_with_compact_krhs(lib, ngl, nelem):
         ctx.csr_symbolic()
         K, Krhs = ctx.mat_create(3, 3), ctx.mat_create_rhs(3, 3)
         ctx.assemble_kle(1e3, 1e2, K, Krhs, -1, -1)
+        assert_assembled(ctx, lib.AK_KLE_LATTICE if ngl == 2 else lib.AK_ROWRUN, krhs_completed=0)   # natively addressed on a slab too
         l2g = dom._local2global(np.arange(dom.nLocal))
         rows = (np.arange(dom.rStart, dom.rEnd)[:, None] * 3 + np.arange(3)).ravel()
         cv = (l2g[:, None] * 3 + np.arange(3)).ravel()

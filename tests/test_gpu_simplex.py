@@ -9,7 +9,7 @@ import yaml
 
 import pynama_amd
 from oracle import fem_oracle as fo
-from tests.util import mat_to_scipy, rel_err, sp_rel_err
+from tests.util import assert_assembled, mat_to_scipy, rel_err, sp_rel_err
 
 pytestmark = pytest.mark.gpu
 FP_TOL = 2e-13      # relative, FP64 with atomics (summation order differs from numpy)
@@ -65,6 +65,7 @@ def test_simplex_assembly_and_krylov_vs_oracle(lib, dim, nelem):
     assert np.array_equal(rp, rp_o) and np.array_equal(ci, ci_o)
     A, Ar = ctx.mat_create(1, 1), ctx.mat_create(1, 1)
     ctx.assemble_scalar(lib.FORM_LAPLACE, A, Ar)
+    assert_assembled(ctx, lib.AK_PATCH if dim == 3 else lib.AK_P1, k_closed=0, krhs_completed=0)   # tets: the automatic patch plan
     ref = fo.assemble_scalar(mesh, tb, "laplace", dirichlet=mesh.boundary)
     S = mat_to_scipy(ctx, A, 1, 1)
     assert sp_rel_err(S, ref["A"]) < FP_TOL and sp_rel_err(mat_to_scipy(ctx, Ar, 1, 1), ref["Arhs"]) < FP_TOL
@@ -79,6 +80,7 @@ def test_simplex_assembly_and_krylov_vs_oracle(lib, dim, nelem):
         finally:
             for e in env:
                 del os.environ[e]
+        assert_assembled(ctx, lib.AK_P1 if len(env) == 1 else lib.AK_GENERIC, generic=0 if len(env) == 1 else 1)
         assert sp_rel_err(mat_to_scipy(ctx, A2, 1, 1), ref["A"]) < FP_TOL
         assert sp_rel_err(mat_to_scipy(ctx, Ar2, 1, 1), ref["Arhs"]) < FP_TOL
     rng = np.random.default_rng(1)

@@ -54,3 +54,13 @@ def sp_rel_err(A, B):
     d = abs(A - B)
     s = abs(B).max()
     return (d.max() if d.nnz else 0.0) / (s if s > 0 else 1.0)
+
+
+def assert_assembled(ctx, kind, **slots):
+    """the context's most recent numeric assembly ran kernel family `kind` (pynama_amd._lib.AK_*), with these slots of
+    Context.assemble_last(): a detector or a heuristic that moves cannot silently move a test onto another family"""
+    from pynama_amd._lib import ASSEMBLY_KINDS
+    last = ctx.assemble_last()
+    assert last["kind"] == kind, f"assembled by {ASSEMBLY_KINDS[last['kind']]}, expected {ASSEMBLY_KINDS[kind]}: {last}"
+    for key, val in slots.items():
+        assert last[key] == val, f"{key} = {last[key]}, expected {val}: {last}"
