@@ -242,6 +242,52 @@ int pyn_vec_maxpy(pyn_ctx* ctx, int y, int x, int m, const int* ids, const doubl
 int pyn_ts_step_finish(pyn_ctx* ctx, int x, int m, const int* ids, const double* hb, const double* hd, double atol, double rtol,
                        double* wnorm);
 
+/* ---- analytic fields and constant values on node sets (pyn_fields.hip) ------------------------
+ * What the reference does per node on the host -- DMPlexDom.applyFunctionVecToVec / applyValuesToVec (src/domain/dmplex.py:
+ * 262-296) with the closed-form fields of src/cases/custom_func.py (:173-310) -- as one stream-ordered launch: no host loop over
+ * nodes, no host-to-device copy, no synchronise. */
+/* A set of OWNED local nodes kept on the device: nodes[n] strictly increasing, each in [0, n_owned) (checked here, once; n = 0 is
+ * a valid empty set, nodes may then be NULL) -- the `nodes` argument of dmplex.py's apply*ToVec helpers (dmplex.py:262-296), which
+ * the reference rebuilds per call.  Sets belong to the mesh: pyn_mesh_set / pyn_mesh_box release them all, like the immersed-
+ * boundary markers; a released id is never handed out again. */
+int pyn_nodeset_create(pyn_ctx* ctx, int64_t n, const int32_t* nodes, int* set_id);
+int pyn_nodeset_destroy(pyn_ctx* ctx, int set_id);
+/* The closed-form fields of src/cases/custom_func.py: Taylor-Green 2-D (:173-193), Taylor-Green 3-D on the unit box (:196-272), the
+ * sinusoidal field of the operator study (:276-310).  Every factor that does not depend on the coordinates is computed by the
+ * caller and travels in params; the kernel computes the phases k x_d, one sincos per axis it needs, and multiplies left to right
+ * as the Python expressions do (no exp; one rounding per operation: contraction into fused multiply-adds is off for these kernels).  With k = 2 pi, e the decay exp(...) of the field at (nu, t):
+ *   field                    dim bs  params                                  value
+ *   TG2D_VEL                  2  2   k, e                                    cos x sin y e ; -sin x cos y e
+ *   TG2D_VORT                 2  1   k, c = -2 pi (1/Lx + 1/Ly), e           c cos x cos y e
+ *   TG3D_VEL                  3  3   k, e                                    cos x sin y sin z e ; sin x cos y sin z e ; -2 sin x sin y cos z e
+ *   TG3D_VORT                 3  3   k, q = 2 pi e                           -3 q sin x cos y cos z ; 3 q cos x sin y cos z ; 0
+ *   TG3D_CONV                 3  3   k, a = 6 (2 pi e)^2                     -a sin y cos y sin z cos z ; a sin x cos x sin z cos z ; 0
+ *   TG3D_DIFF                 3  3   k, a = 9 nu e (2 pi)^3                  a sin x cos y cos z ; -a cos x sin y cos z ; 0
+ *   SEN2D_VEL                 2  2   k                                       sin(k y) ; sin(2k x)
+ *   SEN2D_VORT                2  1   k                                       2k cos(2k x) - k cos(k y)
+ *   SEN2D_CONV                2  1   k, c = (2 pi)^2 - (4 pi)^2              c sin(k y) sin(2k x)
+ *   SEN2D_DIFF                2  1   k, nu, a = (2 pi)^3, b = (4 pi)^3       nu (a cos(k y) - b cos(2k x))
+ * (x, y, z in the Taylor-Green rows are the phases k x_d; 2k is exact, so 4 pi needs no slot of its own.) */
+enum {
+  PYN_FIELD_TG2D_VEL = 0, PYN_FIELD_TG2D_VORT = 1,
+  PYN_FIELD_TG3D_VEL = 2, PYN_FIELD_TG3D_VORT = 3, PYN_FIELD_TG3D_CONV = 4, PYN_FIELD_TG3D_DIFF = 5,
+  PYN_FIELD_SEN2D_VEL = 6, PYN_FIELD_SEN2D_VORT = 7, PYN_FIELD_SEN2D_CONV = 8, PYN_FIELD_SEN2D_DIFF = 9,
+  PYN_FIELD_COUNT = 10
+};
+#define PYN_FIELD_MAX_PARAMS 4
+/* dimension, block size and parameter count of a field (host only: no context; any pointer may be NULL) */
+int pyn_field_info(int field, int* dim, int* bs, int* nparams);
+/* vec[node*bs + k] = field_k(xyz[node]) for every node of the set (set_id -1: every owned node); other entries, ghosts included,
+ * are untouched -- DMPlexDom.applyFunctionVecToVec (dmplex.py:262-275) for a custom_func.py field.  Stream-ordered: no copy, no
+ * synchronise; params travel by value in the kernel arguments.  Refused with a message, before any launch: an unknown field, a
+ * field whose dimension is not the mesh's, a vector whose block size is not the field's, nparams that is not the field's, a set id
+ * that is dead or was never handed out by this context. */
+int pyn_field_eval(pyn_ctx* ctx, int field, const double* params, int nparams, int set_id, int vec_id);
+/* vec[node*bs + k] = values[k] for the nodes of the set (-1: every owned node) and the components with dofs[k] != 0 (dofs NULL:
+ * all); values[nvalues], nvalues == bs, by value in the kernel arguments -- DMPlexDom.applyValuesToVec (dmplex.py:287-296) and the
+ * per-wall Vec.setValues of src/cases/cavity.py:56-75.  Stream-ordered like pyn_field_eval. */
+int pyn_vec_set_nodes(pyn_ctx* ctx, int vec_id, int set_id, const double* values, int nvalues, const uint8_t* dofs);
+
 /* ---- numeric phase (HOT LOOP 1) -----------------------------------------------------------
  * One device pass over all local elements: quadrature (spectral.py:89-157) + scatter-add with
  * Dirichlet elimination (base_problem.py:499-552) + unit diagonal on imposed DOFs

@@ -26,6 +26,10 @@ MG_MAX_LEVELS = 16
 TS_MAX_STAGES = 8
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
 T_SYMBOLIC, T_ASSEMBLE, T_SPMV, T_SOLVE = 0, 1, 2, 3
+# PYN_FIELD_*: the closed-form fields of cases/custom_func.py that pyn_field_eval evaluates on the device
+(FIELD_TG2D_VEL, FIELD_TG2D_VORT, FIELD_TG3D_VEL, FIELD_TG3D_VORT, FIELD_TG3D_CONV, FIELD_TG3D_DIFF,
+ FIELD_SEN2D_VEL, FIELD_SEN2D_VORT, FIELD_SEN2D_CONV, FIELD_SEN2D_DIFF) = range(10)
+FIELD_COUNT, FIELD_MAX_PARAMS = 10, 4
 
 
 class PynamaHipError(RuntimeError):
@@ -112,6 +116,11 @@ SIGNATURES = {
     "pyn_vec_norm": [_P, _I, _I, C.POINTER(_D)],
     "pyn_vec_maxpy": [_P, _I, _I, _I, _pi32, _pf64],
     "pyn_ts_step_finish": [_P, _I, _I, _pi32, _pf64, _P, _D, _D, C.POINTER(_D)],
+    "pyn_nodeset_create": [_P, _L, _P, C.POINTER(_I)],
+    "pyn_nodeset_destroy": [_P, _I],
+    "pyn_field_info": [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)],
+    "pyn_field_eval": [_P, _I, _pf64, _I, _I, _I],
+    "pyn_vec_set_nodes": [_P, _I, _I, _pf64, _I, _P],
     "pyn_assemble_kle": [_P, _D, _D, _I, _I, _I, _I, _I],
     "pyn_assemble_kle_noslip": [_P, _D, _D, C.POINTER(_I)],
     "pyn_assemble_scalar": [_P, _I, _I, _I, _I],
@@ -217,6 +226,13 @@ def ho_local_lattice(ngl, dim):
     loc = np.zeros((int(ngl) ** int(dim), int(dim)), np.int32)
     _check(load_library().pyn_ho_local_lattice(int(ngl), int(dim), loc))
     return loc
+
+
+def field_info(field):
+    """(dim, block size, number of parameters) of a PYN_FIELD_* id as the library holds them (no device needed)"""
+    d, b, n = _I(0), _I(0), _I(0)
+    _check(load_library().pyn_field_info(int(field), C.byref(d), C.byref(b), C.byref(n)))
+    return d.value, b.value, n.value
 
 
 def product_choose(br, bc, npat, maxw, nnzb, n_owned, rhs_compact=False, solver=False, image=False, sell_image=False,
@@ -582,6 +598,39 @@ class Context:
         assert hd.size == ids.size
         _check(self.lib.pyn_ts_step_finish(self.h, x, ids.size, ids, hb, hd.ctypes.data, float(atol), float(rtol), C.byref(out)))
         return out.value
+
+    # -- node sets, analytic fields and constant values on them
+    def nodeset_create(self, nodes) -> int:
+        """device copy of a set of OWNED local nodes (strictly increasing, each in [0, n_owned); may be empty); the id dies with the
+        mesh"""
+        nodes = np.asarray(nodes).ravel()
+        if nodes.size and (nodes.min() < -2 ** 31 or nodes.max() >= 2 ** 31):
+            raise PynamaHipError("nodeset_create: a node id does not fit 32 bits")
+        nodes = _i32(nodes)
+        i = _I(-1)
+        _check(self.lib.pyn_nodeset_create(self.h, nodes.size, nodes.ctypes.data_as(_P) if nodes.size else None, C.byref(i)))
+        return i.value
+
+    def nodeset_destroy(self, set_id):
+        if self.h:
+            _check(self.lib.pyn_nodeset_destroy(self.h, int(set_id)))
+
+    def field_eval(self, field, params, set_id, vid):
+        """vec[node*bs + k] = field_k(xyz[node]) over the node set (-1: every owned node), stream-ordered; params: the field's
+        coordinate-independent factors, computed by the caller (include/pynama_hip.h lists them per field)"""
+        params = _f64(np.atleast_1d(params)).ravel()
+        _check(self.lib.pyn_field_eval(self.h, int(field), params if params.size else np.zeros(1), params.size, int(set_id), int(vid)))
+
+    def vec_set_nodes(self, vid, set_id, values, dofs=None):
+        """vec[node*bs + k] = values[k] over the node set (-1: every owned node) for the components with dofs[k] != 0 (None: all)"""
+        values = _f64(np.atleast_1d(values)).ravel()
+        d = None
+        if dofs is not None:
+            d = np.ascontiguousarray(dofs, dtype=np.uint8).ravel()
+            if d.size != values.size:
+                raise PynamaHipError(f"vec_set_nodes: {d.size} component flags for {values.size} values")
+        _check(self.lib.pyn_vec_set_nodes(self.h, int(vid), int(set_id), values if values.size else np.zeros(1), values.size,
+                                          d.ctypes.data_as(_P) if d is not None else None))
 
     def vec_norm(self, x, norm_type=2) -> float:
         d = _D(0)

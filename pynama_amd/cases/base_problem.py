@@ -149,6 +149,9 @@ class BaseProblem(object):
         self.setUpElement()
         self.createMesh()
         self.bcNodes = self.dom.getNodesFromLabel("External Boundary")
+        # the same nodes, and all of them, as node sets: sorted owned local ids + their device copy, built once and reused
+        self.bcNodeSet = self.dom.nodeSet(self.bcNodes)
+        self.allNodeSet = self.dom.nodeSet(self.dom.getAllNodes())
 
     def buildOperators(self):
         """SrT / DivSrT / Curl operators (base_problem.py:132-140) in three device passes."""

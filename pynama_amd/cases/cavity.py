@@ -10,6 +10,8 @@ class Cavity(NoSlipFreeSlip):
     def setUp(self):
         super().setUp()
         self.collectCornerNodes()
+        # one node set per wall, built once: applyBoundaryConditions / applyBoundaryConditionsFS rebuild no index array
+        self.wallNodeSets = {wall: self.dom.nodeSet(self.dom.getBorderNodes(wall)) for wall in self.nsWalls.getWallsNames()}
 
     def collectCornerNodes(self):
         cornerNodes = set()
@@ -42,7 +44,6 @@ class Cavity(NoSlipFreeSlip):
 
     def _setWallValues(self, vec, walls, static):
         for wallName in walls:
-            nodes = self.dom.getBorderNodes(wallName)
             if static:
                 velDofs = self.nsWalls.getStaticDofsByName(wallName)
                 vel = np.zeros(len(velDofs))
@@ -50,8 +51,9 @@ class Cavity(NoSlipFreeSlip):
                 vel, velDofs = self.nsWalls.getWallVelocity(wallName)
             if len(velDofs) == 0:
                 continue
-            dofs = [node * self.dim + dof for node in nodes for dof in velDofs]
-            vec.setValues(dofs, np.tile(np.asarray(vel, dtype=float), len(nodes)))
+            values, flags = np.zeros(self.dim), np.zeros(self.dim, dtype=np.uint8)
+            values[velDofs], flags[velDofs] = np.asarray(vel, dtype=float), 1
+            self.dom.ctx.vec_set_nodes(vec.id, self.wallNodeSets[wallName].id, values, flags)
 
     def applyBoundaryConditions(self, time=None):
         self.vel.set(0.0)

@@ -14,46 +14,48 @@ class CustomFuncCase(FreeSlip):
         self.buildKLEMats()
         self.buildOperators()
         self.nu = self.mu / self.rho
+        # the fields as objects: callable like the static methods below (the same functions), and evaluable on the device
+        from pynama_amd.cases import fields
         if self.case == 'taylor-green':
             if self.dim == 2:
-                self.velFunction = self.taylorGreenVel_2D
-                self.vortFunction = self.taylorGreenVort_2D
+                self.velFunction = fields.taylorGreenVel_2D
+                self.vortFunction = fields.taylorGreenVort_2D
             else:
-                self.velFunction = self.taylorGreenVel_3D
-                self.vortFunction = self.taylorGreenVort_3D
-                self.diffusiveFunction = self.taylorGreen3dDiffusive
-                self.convectiveFunction = self.taylorGreen3dConvective
+                self.velFunction = fields.taylorGreenVel_3D
+                self.vortFunction = fields.taylorGreenVort_3D
+                self.diffusiveFunction = fields.taylorGreen3dDiffusive
+                self.convectiveFunction = fields.taylorGreen3dConvective
         elif self.case == 'senoidal':
             if self.dim != 2:
                 raise Exception("not defined func")
-            self.velFunction = self.senoidalVel_2D
-            self.vortFunction = self.senoidalVort_2D
-            self.diffusiveFunction = self.senoidalDiffusive
-            self.convectiveFunction = self.senoidalConvective
+            self.velFunction = fields.senoidalVel_2D
+            self.vortFunction = fields.senoidalVort_2D
+            self.diffusiveFunction = fields.senoidalDiffusive
+            self.convectiveFunction = fields.senoidalConvective
         else:
             raise Exception("Case not found")
 
+    def _at(self, function, time):
+        """function(., nu, t=time) for the apply*ToVec helpers: a field object binds (they may then evaluate it on the device,
+        -pynama_device_fields), any other callable is wrapped as before"""
+        if hasattr(function, "bind"):
+            return function.bind(self.nu, time)
+        return lambda coords: function(coords, self.nu, t=time)
+
     def computeInitialCondition(self, startTime):
-        allNodes = self.dom.getAllNodes()
-        fvort = lambda coords: self.vortFunction(coords, self.nu, t=startTime)
-        self.vort = self.dom.applyFunctionVecToVec(allNodes, fvort, self.vort, self.dim_w)
+        self.vort = self.dom.applyFunctionVecToVec(self.allNodeSet, self._at(self.vortFunction, startTime), self.vort, self.dim_w)
 
     def generateExactVecs(self, time):
         exactVel = self.mat.K.createVecRight()
         exactVort = self.mat.Rw.createVecRight()
-        allNodes = self.dom.getAllNodes()
-        fvel = lambda coords: self.velFunction(coords, self.nu, t=time)
-        fvort = lambda coords: self.vortFunction(coords, self.nu, t=time)
-        exactVel = self.dom.applyFunctionVecToVec(allNodes, fvel, exactVel, self.dim)
-        exactVort = self.dom.applyFunctionVecToVec(allNodes, fvort, exactVort, self.dim_w)
+        exactVel = self.dom.applyFunctionVecToVec(self.allNodeSet, self._at(self.velFunction, time), exactVel, self.dim)
+        exactVort = self.dom.applyFunctionVecToVec(self.allNodeSet, self._at(self.vortFunction, time), exactVort, self.dim_w)
         return exactVel, exactVort
 
     def applyBoundaryConditions(self, time):
         self.vel.set(0.0)
-        fvel = lambda coords: self.velFunction(coords, self.nu, t=time)
-        fvort = lambda coords: self.vortFunction(coords, self.nu, t=time)
-        self.vel = self.dom.applyFunctionVecToVec(self.bcNodes, fvel, self.vel, self.dim)
-        self.vort = self.dom.applyFunctionVecToVec(self.bcNodes, fvort, self.vort, self.dim_w)
+        self.vel = self.dom.applyFunctionVecToVec(self.bcNodeSet, self._at(self.velFunction, time), self.vel, self.dim)
+        self.vort = self.dom.applyFunctionVecToVec(self.bcNodeSet, self._at(self.vortFunction, time), self.vort, self.dim_w)
 
     @staticmethod
     def taylorGreenVel_2D(coord, nu, t=None):
@@ -73,7 +75,7 @@ class CustomFuncCase(FreeSlip):
     def _fieldVec(self, like, function, time, dof, name):
         vec = like.duplicate()
         vec.setName(f"{self.caseName}-exact-{name}")
-        return self.dom.applyFunctionVecToVec(self.dom.getAllNodes(), lambda c: function(c, self.nu, t=time), vec, dof)
+        return self.dom.applyFunctionVecToVec(self.allNodeSet, self._at(function, time), vec, dof)
 
     def generateExactOperVecs(self, time):
         vel0, vort0 = self.mat.K.createVecRight(), self.mat.Rw.createVecRight()

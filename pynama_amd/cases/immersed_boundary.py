@@ -45,7 +45,7 @@ class ImmersedBoundaryStatic(FreeSlip):
 
     def applyBoundaryConditions(self, time):
         self.vel.set(0.0)
-        self.vel = self.dom.applyValuesToVec(self.bcNodes, self.cteValue, self.vel)
+        self.vel = self.dom.applyValuesToVec(self.bcNodeSet, self.cteValue, self.vel)
 
     # -- the body on the device
     def buildIBMMatrix(self, time=0.0):

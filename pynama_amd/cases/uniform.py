@@ -22,11 +22,11 @@ class UniformFlow(FreeSlip):
         self.vort.set(0.0)
 
     def applyBoundaryConditions(self, time):
-        self.vel = self._uniform(self.vel, self.bcNodes)
+        self.vel = self._uniform(self.vel, self.bcNodeSet)
 
     def generateExactVecs(self, time=None):
         vel, vort = self.mat.K.createVecRight(), self.mat.Rw.createVecRight()
         for vec, what in ((vel, "vel"), (vort, "vort")):
             vec.setName(f"{self.caseName}-exact-{what}")
         vort.set(0.0)
-        return self._uniform(vel, self.dom.getAllNodes()), vort
+        return self._uniform(vel, self.allNodeSet), vort

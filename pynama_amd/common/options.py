@@ -49,6 +49,11 @@ class Options:
         Options._db.pop(key.lstrip('-'), None)
 
 
+def flag_set(o, key):
+    """a PETSc-style boolean option: present and not 0 / false / no"""
+    return o.hasName(key) and str(o.getString(key, '1')).lower() not in ('0', 'false', 'no')
+
+
 def _is_number(s):
     try:
         float(s)

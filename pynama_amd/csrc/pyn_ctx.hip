@@ -161,6 +161,7 @@ extern "C" int pyn_ctx_destroy(pyn_ctx* c) {
   pyn_ho3_release(c);
   pyn_ho_release(c);
   pyn_ibm_release(c);
+  pyn_nodesets_release(c);
   (void)hipFree(c->d_ho3_tabs);
   (void)hipFree(c->d_ho3_t1d);
   (void)hipFree(c->d_bcmask);
@@ -622,6 +623,7 @@ static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
     c->mf_set[k] = false;
   }
   pyn_ibm_release(c);             // ... and so does the immersed-boundary marker set
+  pyn_nodesets_release(c);        // ... and every node set
   PYN_TRY(pyn_box_detect(c, at));   // structured topology: found once, admitted per kernel family
   PYN_TRY(pyn_lattice_view(c));
   pyn_ho3_view(c);

@@ -232,6 +232,13 @@ struct DVec {
   bool live = false;
 };
 
+// a set of owned local nodes on the device (pyn_fields.hip): strictly increasing, range-checked when it was created
+struct DNodeSet {
+  int32_t* d = nullptr;  // [n]; null when n == 0
+  int64_t n = 0;
+  bool live = false;
+};
+
 constexpr int64_t PYN_RHS_UNKNOWN = -2, PYN_RHS_ANY = -1;   // DMat::rhs_clean
 constexpr int PYN_MAX_PARTIALS = 2048;  // grid cap of every reducing kernel
 
@@ -332,6 +339,7 @@ struct pyn_ctx {
 
   std::vector<DMat> mats;
   std::vector<DVec> vecs;
+  std::vector<DNodeSet> nodesets;   // ids are never reused: a released set stays dead (pyn_fields.hip)
 
   // reduction / solver scratch
   double* d_part = nullptr;    // [8][PYN_MAX_PARTIALS]
@@ -445,6 +453,7 @@ int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]);  
 void pyn_ho_view(pyn_ctx* c);
 void pyn_ho_release(pyn_ctx* c);
 void pyn_ibm_release(pyn_ctx* c);   // pyn_ibm.hip: the marker set belongs to the mesh
+void pyn_nodesets_release(pyn_ctx* c);   // pyn_fields.hip: ... and so do the node sets
 // dense LU shared by the direct solve, the coarsest multigrid level and the immersed-boundary force solve (pyn_direct.hip): piv holds 2 n + 1 ints
 int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n);
 int pyn_dense_lu_solve(pyn_ctx* c, const double* D, const int* piv, int64_t n, const double* b, double* x, double* z);

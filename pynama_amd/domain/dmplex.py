@@ -23,6 +23,7 @@ import numpy as np
 
 from pynama_amd import _lib
 from pynama_amd.common.comm import get_world
+from pynama_amd.common.options import Options, flag_set
 from pynama_amd.elements.spectral import _local_lattice
 
 
@@ -62,6 +63,34 @@ class IndicesManager:
     def mapNodesToIndices(self, nodes, dof):
         """global DOF = node * dof + component, node-major (indices.py:90-92)"""
         return (np.asarray(list(nodes), dtype=np.int64)[:, None] * dof + np.arange(dof)).ravel().tolist()
+
+
+class NodeSet:
+    """The owned part of a set of global nodes, kept for reuse: `globalNodes` / `localNodes` sorted (what DMPlexDom._owned_local
+    computes per call from a Python set) and, on first use, the device copy `id` the library's node-set entries take
+    (pyn_nodeset_create; -1 stands for "every owned node" and needs none).  Belongs to the domain's current device context."""
+
+    def __init__(self, dom, globalNodes, localNodes, everything=False):
+        self.dom, self.globalNodes, self.localNodes, self.everything = dom, globalNodes, localNodes, everything
+        self._ctx = self._id = None
+
+    def __len__(self):
+        return int(self.localNodes.size)
+
+    @property
+    def id(self):
+        if self.everything:
+            return -1
+        ctx = self.dom.ctx
+        if self._ctx is not ctx:          # first use, or the domain was indexed again: the old context took its sets with it
+            self._id, self._ctx = ctx.nodeset_create(self.localNodes), ctx
+        return self._id
+
+    def release(self):
+        """drop the device copy (it is made again on the next use)"""
+        if self._id is not None and self._ctx is self.dom._ctx and self._ctx.h:
+            self._ctx.nodeset_destroy(self._id)
+        self._ctx = self._id = None
 
 
 class SlabPartition:
@@ -829,7 +858,21 @@ class DMPlexDom(object):
         from pynama_amd.vectors import Vec
         return Vec(self.ctx, bs or self.dim)
 
+    def nodeSet(self, nodes):
+        """NodeSet of the owned nodes among `nodes` (global ids: a set, a list, a range); every owned node -> the set -1"""
+        if isinstance(nodes, NodeSet):
+            return nodes
+        gn, ln = self._owned_local(nodes)
+        order = np.argsort(ln, kind="stable")
+        gn, ln = gn[order], ln[order]
+        if ln.size > 1 and np.any(np.diff(ln) == 0):
+            keep = np.concatenate([[True], np.diff(ln) != 0])
+            gn, ln = gn[keep], ln[keep]
+        return NodeSet(self, gn, ln, everything=bool(ln.size == self.nOwned))
+
     def _owned_local(self, nodes):
+        if isinstance(nodes, NodeSet):
+            return nodes.globalNodes, nodes.localNodes
         if isinstance(nodes, range):
             nodes = np.arange(nodes.start, nodes.stop, nodes.step, dtype=np.int64)
         else:
@@ -838,6 +881,23 @@ class DMPlexDom(object):
         return nodes[keep], nodes[keep] - self.rStart
 
     def applyFunctionVecToVec(self, nodes, f_vec, vec, dof):
+        """vec[node, :] = f_vec(coordinates of node) over the owned nodes among `nodes` (global ids, or a NodeSet).  A bound
+        analytic field (cases/fields.py) is evaluated on the device when -pynama_device_fields is set: one stream-ordered launch
+        over the device coordinates, no per-node call, no copy.  Any other callable, and every callable without the option, is
+        mapped over the nodes on the host."""
+        dev = getattr(f_vec, "deviceField", None) if flag_set(Options(), 'pynama_device_fields') else None
+        if dev is not None and self.ctx.n_node > 0:
+            if dev.bs != dof:
+                raise ValueError(f"the field has {dev.bs} components, {dof} were asked for")
+            if isinstance(nodes, NodeSet):
+                self.ctx.field_eval(dev.id, dev.params, nodes.id, vec.id)
+            else:      # a one-off set: built, uploaded and released here (a sort, a copy and two synchronises; keep a NodeSet to avoid them)
+                once = self.nodeSet(nodes)
+                try:
+                    self.ctx.field_eval(dev.id, dev.params, once.id, vec.id)
+                finally:
+                    once.release()
+            return vec
         gn, ln = self._owned_local(nodes)
         coords = self._coords_of_local(ln)
         values = np.array(list(map(f_vec, coords)), dtype=np.float64).reshape(len(ln), dof)
@@ -852,10 +912,15 @@ class DMPlexDom(object):
         return vec
 
     def applyValuesToVec(self, nodes, values, vec):
+        """vec[node * dof + k] = values[k], dof = len(values), over the owned nodes among `nodes`; one value fills the whole vector
+        (the reference's quirk).  A NodeSet takes the device path (pyn_vec_set_nodes) when dof is the vector's block size; any other
+        `nodes`, and a dof below the block size, keep the host indexing."""
         dof = len(values)
         assert dof <= self.dim
         if dof == 1:
             vec.set(values[0])
+        elif isinstance(nodes, NodeSet) and dof == vec.bs:     # the device copy of the set: one launch, the values in its arguments
+            self.ctx.vec_set_nodes(vec.id, nodes.id, values)
         else:
             gn, ln = self._owned_local(nodes)
             inds = (ln[:, None] * dof + np.arange(dof)[None, :]).ravel()

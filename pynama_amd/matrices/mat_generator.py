@@ -13,13 +13,8 @@ import numpy as np
 
 from pynama_amd import _lib
 from pynama_amd.common.comm import get_world
-from pynama_amd.common.options import Options
+from pynama_amd.common.options import Options, flag_set as _flag_set
 from pynama_amd.vectors import Vec
-
-
-def _flag_set(o, key):
-    """a PETSc-style boolean option: present and not 0 / false / no"""
-    return o.hasName(key) and str(o.getString(key, '1')).lower() not in ('0', 'false', 'no')
 
 
 class DeviceMat:
