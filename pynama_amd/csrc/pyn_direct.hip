@@ -62,7 +62,9 @@ __global__ void __launch_bounds__(256) lu_pivot_kernel(const double* __restrict_
   }
   if (threadIdx.x == 0) {
     piv[k] = si[0];
-    if (!(sv[0] > 0.0)) *flag = k + 1;   // singular (or NaN) column
+    // singular (or NaN) column; the first one is reported: the division by the zero pivot fills the panel with NaN, and every
+    // later column is flagged as well
+    if (!(sv[0] > 0.0) && *flag == 0) *flag = k + 1;
   }
 }
 
