@@ -391,13 +391,24 @@ int pyn_assemble_choose_layout(char* buf, int len);
  *                                                          a cell that is not affine, PYN_MATFREE_LAPLACE, an order above the limit,
  *                                                          a connectivity that is not the lexicographic box lattice (imported /
  *                                                          renumbered meshes), tables that are not the Lobatto(ngl) / Gauss(ngl-1) rules
+ *   ANY quadrilateral / hexahedral mesh of order ngl >= 4   PYN_MATFREE_KLE_GENERAL only: bent (bilinear / trilinear) cells, any node
+ *                                                          numbering, cell order, cell orientation and vertex valence (imported Gmsh
+ *                                                          meshes), ngl <= 12 in 2-D and <= 8 in 3-D, ONE rank (lane per node with the
+ *                                                          Jacobian formed at every point from the cell's corners, a gather pass over
+ *                                                          a node -> cell incidence list; pyn_matfree_ho_general.hip).  Refused with a
+ *                                                          message: an order outside 4..limit (ngl <= 3 meshes included), several ranks
+ *                                                          or ghost nodes, n_elem * nn >= 2^31, tables that are not those rules or
+ *                                                          whose geometry tables are not the multilinear corner basis, a cell with
+ *                                                          det J <= 0 at a point of either rule ("non-positive Jacobian")
  *   PYN_MATFREE_LAPLACE  the scalar Laplacian pyn_assemble_scalar(PYN_FORM_LAPLACE) builds (1 DOF per node)
  *   PYN_MATFREE_KLE      the K of pyn_assemble_kle (dim DOFs per node: 3 on Q1 hexahedra, 2 / 3 on second- and higher-order meshes);
  *                        alpha_d / alpha_w are that call's penalty weights (1e3 / 1e2 in the reference, spectral.py:152-153)
+ *   PYN_MATFREE_KLE_GENERAL  the same K; its own operator id with its own snapshot (mask, alpha_d, alpha_w): on a box lattice of
+ *                        affine cells both ids may be set on one context and stay independent
  * pyn_matfree_set defines the operator from the mesh, the element tables and a SNAPSHOT of the current Dirichlet mask
  * (imposed rows identity, imposed columns eliminated, base_problem.py:531-549): call it next to the assembly it mirrors;
  * later pyn_bc_set calls do not change it. */
-enum { PYN_MATFREE_OFF = 0, PYN_MATFREE_LAPLACE = 1, PYN_MATFREE_KLE = 2 };
+enum { PYN_MATFREE_OFF = 0, PYN_MATFREE_LAPLACE = 1, PYN_MATFREE_KLE = 2, PYN_MATFREE_KLE_GENERAL = 3 };
 int pyn_matfree_set(pyn_ctx* ctx, int op, double alpha_d, double alpha_w);
 int pyn_matfree_apply(pyn_ctx* ctx, int op, int x_vec, int y_vec);
 typedef struct pyn_solve_opts {

@@ -20,7 +20,7 @@ CSRC = os.path.join(_HERE, "csrc")
 Q_FULL, Q_RED, Q_NODAL = 0, 1, 2
 FORM_LAPLACE, FORM_MASS_NODAL, FORM_MASS_FULL, FORM_KLE, FORM_OPERATOR = 0, 1, 2, 3, 4
 KSP_CG, KSP_GMRES = 0, 1
-MATFREE_OFF, MATFREE_LAPLACE, MATFREE_KLE = 0, 1, 2
+MATFREE_OFF, MATFREE_LAPLACE, MATFREE_KLE, MATFREE_KLE_GENERAL = 0, 1, 2, 3
 PC_NONE, PC_JACOBI, PC_MG = 0, 1, 2
 MG_MAX_LEVELS = 16
 TS_MAX_STAGES = 8
@@ -703,7 +703,7 @@ class Context:
     def matfree_apply(self, x, y, op=1):
         """y = A x without an assembled matrix (op: MATFREE_LAPLACE scalar, structured Q1 hex meshes; MATFREE_KLE dim DOFs per
         node: structured Q1 hex meshes, second-order lattices of affine cells, box lattices of affine cells of order ngl 4..12
-        in 2-D / 4..8 in 3-D)"""
+        in 2-D / 4..8 in 3-D; MATFREE_KLE_GENERAL the same K on any quadrilateral / hexahedral mesh of those orders, one rank)"""
         _check(self.lib.pyn_matfree_apply(self.h, op, x, y))
 
     def matfree_set(self, op=1, alpha_d=0.0, alpha_w=0.0):

@@ -1819,7 +1819,7 @@ static int matfree_kle_launch(pyn_ctx* c, const double* x, double* y, bool dot, 
   int mesh_aff = 0;
   PYN_TRY(lat_fill_args(c, K.L, &mesh_aff));
   K.L.bcmask = c->mf_mask[PYN_MATFREE_KLE];
-  kle_fill(c, K, c->mf_alpha_d, c->mf_alpha_w);
+  kle_fill(c, K, c->mf_alpha_d[PYN_MATFREE_KLE], c->mf_alpha_w[PYN_MATFREE_KLE]);
   const bool affine = mesh_aff == 1 && K.L.q.aff != nullptr && c->aff_standard;
   const char* tl = getenv("PYNAMA_MATFREE_TILE");
   switch (tl ? atoi(tl) : 0) {

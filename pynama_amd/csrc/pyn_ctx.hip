@@ -151,7 +151,7 @@ extern "C" int pyn_ctx_destroy(pyn_ctx* c) {
   (void)hipFree(c->d_esel);
   pyn_sell_drop_structure(c);
   for (auto& v : c->vecs) (void)hipFree(v.d);
-  for (int k = 0; k < 3; ++k) (void)hipFree(c->mf_mask[k]);
+  for (int k = 0; k < PYN_MATFREE_SLOTS; ++k) (void)hipFree(c->mf_mask[k]);
   for (auto& q : c->quad) free_quad(q);
   (void)hipFree(c->d_conn);
   (void)hipFree(c->d_xyz);
@@ -617,7 +617,7 @@ static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
     }
   }
   c->mesh_affine = -1;
-  for (int k = 0; k < 3; ++k) {   // matrix-free operators belong to the mesh
+  for (int k = 0; k < PYN_MATFREE_SLOTS; ++k) {   // matrix-free operators belong to the mesh
     (void)hipFree(c->mf_mask[k]);
     c->mf_mask[k] = nullptr;
     c->mf_set[k] = false;

@@ -215,6 +215,7 @@ struct Ho3MfBasis {
   int diag = 0;                // every cell's J^-1 is diagonal (axis-aligned boxes)
 };
 
+constexpr int PYN_MATFREE_SLOTS = PYN_MATFREE_KLE_GENERAL + 1;   // operator ids of include/pynama_hip.h
 constexpr int PYN_HO_MAX_NGL_2D = 12, PYN_HO_MAX_NGL_3D = 8;   // orders the matrix-free kernels are instantiated for
 
 struct SellShape {
@@ -298,9 +299,9 @@ struct pyn_ctx {
   int bc_ndof = 0;
   // matrix-free operators (pyn_matfree_set), slot = PYN_MATFREE_*: the Dirichlet mask is SNAPSHOT at set time, so later
   // pyn_bc_set calls (operator assembly, other matrices) do not change the operator
-  bool mf_set[3] = {false, false, false};
-  uint8_t* mf_mask[3] = {nullptr, nullptr, nullptr};   // null = no imposed DOF
-  double mf_alpha_d = 0.0, mf_alpha_w = 0.0;
+  bool mf_set[PYN_MATFREE_SLOTS] = {};
+  uint8_t* mf_mask[PYN_MATFREE_SLOTS] = {};   // null = no imposed DOF
+  double mf_alpha_d[PYN_MATFREE_SLOTS] = {}, mf_alpha_w[PYN_MATFREE_SLOTS] = {};   // penalty weights of each KLE operator's snapshot
   Ho3MfBasis mf_ho3;     // the KLE operator on a second-order lattice (pyn_matfree_ho3.hip): its 1-D point bases, set with mf_set[KLE]
   int64_t bc_stamp = 0;  // bumped by every pyn_bc_set
   uint8_t* d_bcmask = nullptr;
@@ -319,6 +320,10 @@ struct pyn_ctx {
   bool ho_valid = false;        // 4 <= ngl <= pyn_ho_matfree_max_ngl(dim) (pyn_matfree_ho.hip); pyn_mesh_topology says kind 0 for these
   double* d_ho_tab = nullptr;   // its matrix-free KLE operator: the 1-D tables of the order (set by pyn_matfree_set) ...
   double* d_ho_ye = nullptr;    // ... and the per-cell results between the two passes [n_elem][dim][nn]
+  // PYN_MATFREE_KLE_GENERAL (pyn_matfree_ho_general.hip), any quadrilateral / hexahedral mesh of these orders; shares d_ho_tab / d_ho_ye
+  int32_t* d_hog_aoft = nullptr;      // [nn] local node at tensor position t (the inverse of mesh_local_lattice)
+  int32_t* d_hog_inc_ptr = nullptr;   // [n_node + 1] node -> (cell, t) incidence list in CSR form ...
+  int32_t* d_hog_inc = nullptr;       // ... [n_elem * nn] entries cell * nn + t, ascending within a row
   // reference matrices of the ngl = 3 element in tensor (lattice) order, from the uploaded tables (pyn_elem_tables_set):
   // Tf / Tr[r][s][a][b] = sum_g w Hrs_r[a] Hrs_s[b] (full / reduced rule), Uf / Ur[r][a][b] = sum_g w H[a] Hrs_r[b]
   double* d_ho3_tabs = nullptr;
@@ -458,8 +463,8 @@ void pyn_nodesets_release(pyn_ctx* c);   // pyn_fields.hip: ... and so do the no
 int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n);
 int pyn_dense_lu_solve(pyn_ctx* c, const double* D, const int* piv, int64_t n, const double* b, double* x, double* z);
 // A matrix-free backend: the mesh family whose kernels apply the shell operators (PYN_MATFREE_*).  One static record per family, next
-// to its kernels: second-order lattices (pyn_matfree_ho3.hip), box lattices of order ngl >= 4 (pyn_matfree_ho.hip), Q1 lattices
-// (pyn_assemble_lattice.hip).
+// to its kernels: second-order lattices (pyn_matfree_ho3.hip), meshes of order ngl >= 4 (pyn_matfree_ho.hip: box lattices of affine
+// cells, and PYN_MATFREE_KLE_GENERAL on any mesh through pyn_matfree_ho_general.hip), Q1 lattices (pyn_assemble_lattice.hip).
 struct MfBackend {
   bool (*owns)(const pyn_ctx* c);
   int (*set)(pyn_ctx* c, int op);        // the checks and tables of pyn_matfree_set

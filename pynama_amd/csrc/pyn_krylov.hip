@@ -532,12 +532,14 @@ int dev_dot(pyn_ctx* c, const double* x, const double* y, int64_t n, double* out
 }  // namespace
 
 // ---- LinOp: how A is applied, decided once -------------------------------------------------------------------------
+static int mf_backend_of(const pyn_ctx* c, int op, const MfBackend** mf);
+
 int LinOp::init(pyn_ctx* ctx, DMat& M, int matfree, Ensure e) {
   c = ctx;
   A = &M;
   op = matfree;
-  mf = matfree != PYN_MATFREE_OFF ? pyn_matfree_backend(ctx) : nullptr;
-  if (mf) return PYN_OK;
+  mf = nullptr;
+  if (matfree != PYN_MATFREE_OFF) return mf_backend_of(ctx, matfree, &mf);
   if (e != IF_READY) PYN_TRY(pyn_sell_ensure(ctx, M, e == SOLVER));
   plan = M.plan.kind != PK_NONE ? &M.plan : &PYN_RAW_PLAN;
   if (plan->kind != PK_RAW) S = pyn_sell_shape(ctx, M);
@@ -676,10 +678,20 @@ extern "C" int pyn_spmv(pyn_ctx* c, int mat_id, int xv, int yv) {
 }
 
 // -----------------------------------------------------------------------------------------------
+// the backend of `op` on this mesh; only the backend of the orders ngl >= 4 knows PYN_MATFREE_KLE_GENERAL
+static int mf_backend_of(const pyn_ctx* c, int op, const MfBackend** mf) {
+  PYN_CHECK(op >= PYN_MATFREE_LAPLACE && op <= PYN_MATFREE_KLE_GENERAL, "unknown matrix-free operator %d", op);
+  *mf = pyn_matfree_backend(c);
+  PYN_CHECK(op != PYN_MATFREE_KLE_GENERAL || *mf == pyn_mf_ho(),
+            "general matrix-free KLE operator (PYN_MATFREE_KLE_GENERAL): serves quadrilateral / hexahedral meshes of order ngl 4..%d "
+            "(2-D) / 4..%d (3-D); this mesh has ngl %d", PYN_HO_MAX_NGL_2D, PYN_HO_MAX_NGL_3D, c->ngl);
+  return PYN_OK;
+}
+
 extern "C" int pyn_matfree_set(pyn_ctx* c, int op, double alpha_d, double alpha_w) {
   PYN_CHECK(c, "NULL context");
-  PYN_CHECK(op == PYN_MATFREE_LAPLACE || op == PYN_MATFREE_KLE, "unknown matrix-free operator %d", op);
-  const MfBackend* mf = pyn_matfree_backend(c);
+  const MfBackend* mf = nullptr;
+  PYN_TRY(mf_backend_of(c, op, &mf));
   PYN_TRY(mf->set(c, op));
   const int bs = mf->bs(c, op);
   PYN_CHECK(!c->d_bcmask || c->bc_ndof == bs, "matrix-free operator %d: the current Dirichlet mask must have %d DOF(s) per node", op, bs);
@@ -693,21 +705,19 @@ extern "C" int pyn_matfree_set(pyn_ctx* c, int op, double alpha_d, double alpha_
     PYN_HIP(hipMemcpyAsync(c->mf_mask[op], c->d_bcmask, nb, hipMemcpyDeviceToDevice, c->stream));
     PYN_HIP(hipStreamSynchronize(c->stream));
   }
-  if (op == PYN_MATFREE_KLE) {
-    c->mf_alpha_d = alpha_d;
-    c->mf_alpha_w = alpha_w;
-  }
+  c->mf_alpha_d[op] = alpha_d;
+  c->mf_alpha_w[op] = alpha_w;
   c->mf_set[op] = true;
   return PYN_OK;
 }
 
 extern "C" int pyn_matfree_apply(pyn_ctx* c, int op, int xv, int yv) {
   PYN_CHECK(c, "NULL context");
-  PYN_CHECK(op == PYN_MATFREE_LAPLACE || op == PYN_MATFREE_KLE, "unknown matrix-free operator %d", op);
+  const MfBackend* mf = nullptr;
+  PYN_TRY(mf_backend_of(c, op, &mf));
   PYN_TRY(pyn_check_vec(c, xv, "pyn_matfree_apply x"));
   PYN_TRY(pyn_check_vec(c, yv, "pyn_matfree_apply y"));
   PYN_CHECK(xv != yv, "x and y must differ");
-  const MfBackend* mf = pyn_matfree_backend(c);
   const int bs = mf->bs(c, op);
   PYN_CHECK(c->vecs[xv].bs == bs && c->vecs[yv].bs == bs, "this matrix-free operator acts on vectors of block size %d", bs);
   PYN_HIP(hipSetDevice(c->device));
@@ -1372,7 +1382,7 @@ extern "C" int pyn_solve(pyn_ctx* c, int mat_id, int bv, int xv, const pyn_solve
   PYN_CHECK(opts->pc != PYN_PC_MG || opts->method == PYN_KSP_CG, "the multigrid preconditioner (PYN_PC_MG) runs with CG only, not GMRES");
   PYN_CHECK(opts->maxit > 0 || opts->fixed_iters > 0, "maxit must be positive");
   PYN_CHECK(!(c->nranks > 1 && c->detached), "detached communicator: the Krylov solve needs collectives");
-  PYN_CHECK(opts->matfree >= PYN_MATFREE_OFF && opts->matfree <= PYN_MATFREE_KLE, "unknown matrix-free operator %d", opts->matfree);
+  PYN_CHECK(opts->matfree >= PYN_MATFREE_OFF && opts->matfree <= PYN_MATFREE_KLE_GENERAL, "unknown matrix-free operator %d", opts->matfree);
   PYN_HIP(hipSetDevice(c->device));
   double* b = c->vecs[bv].d;
   double* x = c->vecs[xv].d;

@@ -21,118 +21,11 @@
 // one read of (ngl / (ngl - 1))^dim vectors.
 // Dirichlet: a SNAPSHOT of the per-DOF mask taken by pyn_matfree_set.  Rank slabs: x carries the ghost tail; planes (3-D) / x-lines
 // (2-D) are numbered through BoxLattice::P; every cell of the local mesh touches an owned plane, so all of them are computed.
-#include <algorithm>
-#include <cmath>
+#include "pyn_ho_tables.h"
 
-#include "pyn_internal.h"
+using namespace pyn_ho;
 
 namespace {
-
-constexpr double PI = 3.14159265358979323846;
-
-// P_n(x) and P_{n-1}(x)
-void legendre(int n, double x, double& pn, double& pm) {
-  double p0 = 1.0, p1 = x;
-  if (n == 0) {
-    pn = 1.0;
-    pm = 0.0;
-    return;
-  }
-  for (int j = 2; j <= n; ++j) {
-    const double p2 = ((2 * j - 1) * x * p1 - (j - 1) * p0) / j;
-    p0 = p1;
-    p1 = p2;
-  }
-  pn = p1;
-  pm = p0;
-}
-
-// Gauss-Lobatto-Legendre rule with n points, ascending (Newton on (1 - x^2) P'_{n-1}, src/elements/utilities.py:63-92)
-void lobatto_rule(int n, double* x, double* w) {
-  std::vector<double> t(n), wt(n);
-  for (int i = 0; i < n; ++i) {
-    double v = std::cos(PI * i / (n - 1)), prev = 2.0;
-    for (int it = 0; it < 100 && std::fabs(v - prev) > 1e-16; ++it) {
-      prev = v;
-      double pn, pm;
-      legendre(n - 1, v, pn, pm);
-      v = prev - (v * pn - pm) / (n * pn);
-    }
-    double pn, pm;
-    legendre(n - 1, v, pn, pm);
-    t[i] = v;
-    wt[i] = 2.0 / ((n - 1) * (double)n * pn * pn);
-  }
-  for (int i = 0; i < n; ++i) {   // t descends from 1 to -1
-    x[i] = 0.5 * (t[n - 1 - i] - t[i]);
-    w[i] = 0.5 * (wt[n - 1 - i] + wt[i]);
-  }
-}
-
-// Gauss-Legendre rule with n points, ascending (Newton on P_n)
-void gauss_rule(int n, double* x, double* w) {
-  std::vector<double> t(n), wt(n);
-  for (int i = 0; i < n; ++i) {
-    double v = std::cos(PI * (i + 0.75) / (n + 0.5)), prev = 2.0, dp = 0.0;
-    for (int it = 0; it < 100 && std::fabs(v - prev) > 1e-16; ++it) {
-      prev = v;
-      double pn, pm;
-      legendre(n, v, pn, pm);
-      dp = n * (v * pn - pm) / (v * v - 1.0);
-      v = prev - pn / dp;
-    }
-    double pn, pm;
-    legendre(n, v, pn, pm);
-    dp = n * (v * pn - pm) / (v * v - 1.0);
-    t[i] = v;
-    wt[i] = 2.0 / ((1.0 - v * v) * dp * dp);
-  }
-  for (int i = 0; i < n; ++i) {
-    x[i] = 0.5 * (t[n - 1 - i] - t[i]);
-    w[i] = 0.5 * (wt[n - 1 - i] + wt[i]);
-  }
-}
-
-// Lagrange cardinal functions of `nodes` and their first derivatives at `pts`: h, dh [npts][n] (src/elements/element.py:17-49)
-void lagrange_1d(int n, const double* nodes, int npts, const double* pts, double* h, double* dh) {
-  for (int a = 0; a < n; ++a) {
-    double den = 1.0;
-    for (int b = 0; b < n; ++b)
-      if (b != a) den *= nodes[a] - nodes[b];
-    for (int ip = 0; ip < npts; ++ip) {
-      const double x = pts[ip];
-      double num = 1.0, acc = 0.0;
-      for (int b = 0; b < n; ++b)
-        if (b != a) num *= x - nodes[b];
-      for (int skip = 0; skip < n; ++skip) {
-        if (skip == a) continue;
-        double pr = 1.0;
-        for (int b = 0; b < n; ++b)
-          if (b != a && b != skip) pr *= x - nodes[b];
-        acc += pr;
-      }
-      h[ip * n + a] = num / den;
-      dh[ip * n + a] = acc / den;
-    }
-  }
-}
-
-// the 1-D tables of one order, in the layout the kernels read: wl[n] Dl[n][n] wr[n-1] Br[n-1][n] Gr[n-1][n]
-struct HoTab1D {
-  std::vector<double> xl, wl, Dl, xr, wr, Br, Gr;
-  explicit HoTab1D(int n) : xl(n), wl(n), Dl((size_t)n * n), xr(n - 1), wr(n - 1), Br((size_t)(n - 1) * n), Gr((size_t)(n - 1) * n) {
-    std::vector<double> hl((size_t)n * n);
-    lobatto_rule(n, xl.data(), wl.data());
-    gauss_rule(n - 1, xr.data(), wr.data());
-    lagrange_1d(n, xl.data(), n, xl.data(), hl.data(), Dl.data());
-    lagrange_1d(n, xl.data(), n - 1, xr.data(), Br.data(), Gr.data());
-  }
-  std::vector<double> packed() const {
-    std::vector<double> t;
-    for (const auto* v : {&wl, &Dl, &wr, &Br, &Gr}) t.insert(t.end(), v->begin(), v->end());
-    return t;
-  }
-};
 
 struct HoMfArgs {
   const double* xyz;
@@ -144,20 +37,6 @@ struct HoMfArgs {
   int EX, EY, EL;          // cells along x, y (3-D; 1 in 2-D), the slow axis
   int n_cells;
   double alpha_d, alpha_w;
-};
-
-constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
-
-template <int DIM, int N>
-struct HoCfg {
-  static constexpr int NQ = N - 1, NN = ipow(N, DIM), NPT = ipow(NQ, DIM);
-  static constexpr int CPB = NN >= 256 ? 1 : 256 / NN;              // cells per workgroup
-  static constexpr int BLOCK = (CPB * NN + 63) / 64 * 64;
-  static constexpr int BUF = DIM * NN;                              // one stage buffer (doubles); x_e takes one more
-  static constexpr int CELL_LDS = 3 * BUF;
-  static constexpr int TAB = N + N * N + NQ + 2 * NQ * N;
-  static_assert((size_t)(CPB * CELL_LDS + TAB) * sizeof(double) <= 65536, "static LDS");
-  static_assert(BLOCK <= 1024, "workgroup size");
 };
 
 // pass 1: y_e = K_e x_e of every local cell.  Lane t of a cell = node t (x fastest) in the full rule and the last stage, item t of the
@@ -632,8 +511,8 @@ HoMfArgs ho_args(const pyn_ctx* c) {
   A.EY = L.EY;
   A.EL = L.EL;
   A.n_cells = (int)c->n_elem;
-  A.alpha_d = c->mf_alpha_d;
-  A.alpha_w = c->mf_alpha_w;
+  A.alpha_d = c->mf_alpha_d[PYN_MATFREE_KLE];
+  A.alpha_w = c->mf_alpha_w[PYN_MATFREE_KLE];
   return A;
 }
 
@@ -680,6 +559,7 @@ void pyn_ho_release(pyn_ctx* c) {
   (void)hipFree(c->d_ho_ye);
   c->d_ho_tab = c->d_ho_ye = nullptr;
   c->ho_valid = false;
+  pyn_hog_release(c);
 }
 
 // The ngl >= 4 view of c->box: the orders the kernels are instantiated for.  pyn_mesh_topology keeps reporting kind 0 for these meshes:
@@ -691,23 +571,60 @@ void pyn_ho_view(pyn_ctx* c) {
                 c->n_elem < INT32_MAX && !getenv("PYNAMA_NO_HO_LATTICE");
 }
 
+int pyn_ho_check_rules(pyn_ctx* c, const HoTab1D& T, const char* what) {
+  const int dim = c->dim, ngl = c->ngl, nn = c->nn, nq = ngl - 1;
+  int npt = 1;
+  for (int d = 0; d < dim; ++d) npt *= nq;
+  PYN_CHECK(c->quad[0].ngp == nn && c->quad[1].ngp == npt && c->quad[1].H && c->quad[1].w,
+            "%s (ngl %d): needs the tables of the Lobatto(%d) full rule and the Gauss(%d) reduced rule "
+            "(pyn_elem_tables_set)", what, ngl, ngl, nq);
+  // the uploaded reduced rule (reference order of points and nodes) against the tensor products of the 1-D tables
+  std::vector<double> w((size_t)npt), H((size_t)npt * nn);
+  PYN_HIP(hipMemcpy(w.data(), c->quad[1].w, w.size() * sizeof(double), hipMemcpyDeviceToHost));
+  PYN_HIP(hipMemcpy(H.data(), c->quad[1].H, H.size() * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<int> ln, lp;
+  ref_local_lattice(ngl, dim, ln);
+  ref_local_lattice(nq, dim, lp);
+  double worst = 0.0;
+  for (int g = 0; g < npt; ++g) {
+    double wt = 1.0;
+    for (int d = 0; d < dim; ++d) wt *= T.wr[lp[g * dim + d]];
+    worst = std::max(worst, std::fabs(w[g] - wt));
+    for (int a = 0; a < nn; ++a) {
+      double hv = 1.0;
+      for (int d = 0; d < dim; ++d) hv *= T.Br[(size_t)lp[g * dim + d] * ngl + ln[a * dim + d]];
+      worst = std::max(worst, std::fabs(H[(size_t)g * nn + a] - hv));
+    }
+  }
+  PYN_CHECK(worst <= 1e-11, "%s (ngl %d): the element tables are not those of the Gauss(%d) reduced rule on the "
+                            "Lobatto(%d) nodes (largest difference %.3e)", what, ngl, nq, ngl, worst);
+  return PYN_OK;
+}
+
+int pyn_ho_tab_upload(pyn_ctx* c, const HoTab1D& T) {
+  const std::vector<double> packed = T.packed();
+  (void)hipFree(c->d_ho_tab);
+  c->d_ho_tab = nullptr;
+  PYN_HIP(hipMalloc((void**)&c->d_ho_tab, packed.size() * sizeof(double)));
+  PYN_HIP(hipMemcpy(c->d_ho_tab, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (!c->d_ho_ye) PYN_HIP(hipMalloc((void**)&c->d_ho_ye, (size_t)c->n_elem * c->nn * c->dim * sizeof(double)));
+  return PYN_OK;
+}
+
 // pyn_matfree_set on a mesh of order ngl >= 4: the refusals, the 1-D tables of the order (checked against the uploaded reduced-rule
 // tables), the per-cell scratch
 static int ho_matfree_set(pyn_ctx* c, int op) {
   const int dim = c->dim, ngl = c->ngl, lim = pyn_ho_matfree_max_ngl(dim);
   PYN_CHECK(ngl >= 4, "matrix-free operator: not a mesh of order ngl >= 4");
+  if (op == PYN_MATFREE_KLE_GENERAL) return pyn_hog_set(c);
   PYN_CHECK(op == PYN_MATFREE_KLE, "matrix-free operator %d: meshes of order ngl >= 4 have the matrix-free KLE operator only "
                                    "(PYN_MATFREE_KLE)", op);
   PYN_CHECK(ngl <= lim, "matrix-free KLE operator: ngl %d is above the limit of %d-D meshes (ngl <= %d; 2-D: %d, 3-D: %d)", ngl, dim, lim,
             PYN_HO_MAX_NGL_2D, PYN_HO_MAX_NGL_3D);
   PYN_CHECK(c->ho_valid, "matrix-free KLE operator (ngl %d): the connectivity is not that of a structured box lattice numbered "
                         "lexicographically (imported / renumbered meshes have no matrix-free form)", ngl);
-  const int nn = c->nn, nq = ngl - 1;
-  int npt = 1;
-  for (int d = 0; d < dim; ++d) npt *= nq;
-  PYN_CHECK(c->quad[0].ngp == nn && c->quad[1].ngp == npt && c->quad[1].H && c->quad[1].w,
-            "matrix-free KLE operator (ngl %d): needs the tables of the Lobatto(%d) full rule and the Gauss(%d) reduced rule "
-            "(pyn_elem_tables_set)", ngl, ngl, nq);
+  PYN_CHECK(c->quad[0].ngp == c->nn, "matrix-free KLE operator (ngl %d): needs the tables of the Lobatto(%d) full rule and the Gauss(%d) "
+                                     "reduced rule (pyn_elem_tables_set)", ngl, ngl, ngl - 1);
   PYN_HIP(hipSetDevice(c->device));
   HoMfArgs A = ho_args(c);
   {
@@ -727,39 +644,14 @@ static int ho_matfree_set(pyn_ctx* c, int op) {
                   "that is not affine", ngl);
   }
   const HoTab1D T(ngl);
-  {   // the uploaded reduced rule (reference order of points and nodes) against the tensor products of the 1-D tables
-    std::vector<double> w((size_t)npt), H((size_t)npt * nn);
-    PYN_HIP(hipMemcpy(w.data(), c->quad[1].w, w.size() * sizeof(double), hipMemcpyDeviceToHost));
-    PYN_HIP(hipMemcpy(H.data(), c->quad[1].H, H.size() * sizeof(double), hipMemcpyDeviceToHost));
-    std::vector<int> ln, lp;
-    ref_local_lattice(ngl, dim, ln);
-    ref_local_lattice(nq, dim, lp);
-    double worst = 0.0;
-    for (int g = 0; g < npt; ++g) {
-      double wt = 1.0;
-      for (int d = 0; d < dim; ++d) wt *= T.wr[lp[g * dim + d]];
-      worst = std::max(worst, std::fabs(w[g] - wt));
-      for (int a = 0; a < nn; ++a) {
-        double hv = 1.0;
-        for (int d = 0; d < dim; ++d) hv *= T.Br[(size_t)lp[g * dim + d] * ngl + ln[a * dim + d]];
-        worst = std::max(worst, std::fabs(H[(size_t)g * nn + a] - hv));
-      }
-    }
-    PYN_CHECK(worst <= 1e-11, "matrix-free KLE operator (ngl %d): the element tables are not those of the Gauss(%d) reduced rule on the "
-                              "Lobatto(%d) nodes (largest difference %.3e)", ngl, nq, ngl, worst);
-  }
-  const std::vector<double> packed = T.packed();
-  (void)hipFree(c->d_ho_tab);
-  c->d_ho_tab = nullptr;
-  PYN_HIP(hipMalloc((void**)&c->d_ho_tab, packed.size() * sizeof(double)));
-  PYN_HIP(hipMemcpy(c->d_ho_tab, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (!c->d_ho_ye) PYN_HIP(hipMalloc((void**)&c->d_ho_ye, (size_t)c->n_elem * nn * dim * sizeof(double)));
-  return PYN_OK;
+  PYN_TRY(pyn_ho_check_rules(c, T, "matrix-free KLE operator"));
+  return pyn_ho_tab_upload(c, T);
 }
 
 // y = K x under the mask snapshot of pyn_matfree_set; x carries the ghost tail.  dot: fused p.Ap partials into c->d_part (one per
 // workgroup of the gather pass, *grid_out of them).
 static int ho_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
+  if (op == PYN_MATFREE_KLE_GENERAL) return pyn_hog_spmv(c, x, y, dot, grid_out);
   PYN_CHECK(c->ho_valid, "matrix-free operator: not a structured mesh of order ngl >= 4");
   PYN_CHECK(op == PYN_MATFREE_KLE && c->mf_set[PYN_MATFREE_KLE] && c->d_ho_tab && c->d_ho_ye, "matrix-free KLE operator: pyn_matfree_set first");
   const BoxLattice& L = c->box;
@@ -786,7 +678,7 @@ static int ho_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool 
 
 // every mesh of order ngl >= 4 is answered here: ho_matfree_set accepts it or says why not
 static bool ho_matfree_mesh(const pyn_ctx* c) { return c->ngl >= 4; }
-static int ho_matfree_bs(const pyn_ctx* c, int op) { return op == PYN_MATFREE_KLE ? c->dim : 1; }
+static int ho_matfree_bs(const pyn_ctx* c, int op) { return op == PYN_MATFREE_KLE || op == PYN_MATFREE_KLE_GENERAL ? c->dim : 1; }
 
 const MfBackend* pyn_mf_ho() {
   static const MfBackend b = {ho_matfree_mesh, ho_matfree_set, ho_matfree_bs, ho_matfree_spmv, nullptr};

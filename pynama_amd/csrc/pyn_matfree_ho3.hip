@@ -565,8 +565,8 @@ static int ho3_matfree_spmv(pyn_ctx* c, int op, const double* x, double* y, bool
   A.EY = L.EY;
   A.EL = (L.npl - 1) / 2;
   A.ntx = A.nty = A.zb = 0;
-  A.alpha_d = c->mf_alpha_d;
-  A.alpha_w = c->mf_alpha_w;
+  A.alpha_d = c->mf_alpha_d[PYN_MATFREE_KLE];
+  A.alpha_w = c->mf_alpha_w[PYN_MATFREE_KLE];
   A.b = c->mf_ho3;
   const bool dg = c->mf_ho3.diag != 0;
   if (L.dim == 3) {

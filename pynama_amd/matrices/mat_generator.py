@@ -199,7 +199,8 @@ class Mat:
         self.ctx.assemble_kle(alpha_d, alpha_w, self.K.id, self.Krhs.id, self.Rw.id,
                               self.Rd.id if with_rd else -1, variant)
         # K also exists in matrix-free form on structured Q1 hex meshes (KspSolver -pynama_mat_free), and, opt-in, on structured
-        # meshes of affine cells of second order (-pynama_mat_free_ngl3) and of orders ngl >= 4 (-pynama_mat_free_ho)
+        # meshes of affine cells of second order (-pynama_mat_free_ngl3) and of orders ngl >= 4 (-pynama_mat_free_ho), and on any
+        # quadrilateral / hexahedral mesh of orders ngl >= 4, bent and imported ones included (-pynama_mat_free_ho_general)
         self.K.matfree = None
         topo = self.ctx.mesh_topology()[0]
         if self.dim == 3 and elem.nnode == 8 and topo == "lattice":
@@ -211,12 +212,16 @@ class Mat:
                 self.K.matfree = _lib.MATFREE_KLE
             except _lib.PynamaHipError as e:                              # e.g. a cell that is not affine
                 logging.getLogger("Mat").info(f"-pynama_mat_free_ngl3: K stays assembled only ({e})")
-        elif topo == "general" and getattr(elem, 'ngl', 0) >= 4 and _flag_set(Options(), 'pynama_mat_free_ho'):
-            try:
-                self.ctx.matfree_set(_lib.MATFREE_KLE, alpha_d, alpha_w)
-                self.K.matfree = _lib.MATFREE_KLE
-            except _lib.PynamaHipError as e:                              # a cell that is not affine, an order above the limit, ...
-                logging.getLogger("Mat").info(f"-pynama_mat_free_ho: K stays assembled only ({e})")
+        elif topo == "general" and getattr(elem, 'ngl', 0) >= 4:
+            # the affine box-lattice shell first, exactly as before; the general one where that is refused or was not asked for
+            for flag, op in (('pynama_mat_free_ho', _lib.MATFREE_KLE), ('pynama_mat_free_ho_general', _lib.MATFREE_KLE_GENERAL)):
+                if self.K.matfree is not None or not _flag_set(Options(), flag):
+                    continue
+                try:
+                    self.ctx.matfree_set(op, alpha_d, alpha_w)
+                    self.K.matfree = op
+                except _lib.PynamaHipError as e:                          # a cell that is not affine, an order above the limit, ...
+                    logging.getLogger("Mat").info(f"-{flag}: K stays assembled only ({e})")
 
     def createNonZeroIndex(self, d_nnz, o_nnz, dim1, dim2):
         di_nnz = [x * dim1 for x in d_nnz for d in range(dim2)]

@@ -15,7 +15,10 @@ whenever the matrix carries one -- 4 x the iteration rate of the assembled produ
 product, with a warning, if the library finds that the two differ; ``-pynama_mat_free 0`` keeps the assembled product.
 On second-order (ngl 3) structured meshes of affine cells ``Mat.K`` carries the shell only with ``-pynama_mat_free_ngl3``
 (opt-in), and on box meshes of affine cells of order ngl 4..12 (2-D) / 4..8 (3-D) only with ``-pynama_mat_free_ho``; from there
-the same rules apply.
+the same rules apply.  ``-pynama_mat_free_ho_general`` (opt-in, one rank) gives ``Mat.K`` of any quadrilateral / hexahedral mesh of
+those orders a shell -- bent cells, imported (Gmsh) meshes, any numbering and vertex valence: the Jacobian is formed at every
+quadrature point from the cell's corners.  With both options the affine shell is taken where it applies (it is the faster one) and
+the general one elsewhere.  ``-pc_type mg`` stays refused on meshes that are no lattice, with or without a shell.
 
 The reference's hard-wired default is ``preonly`` + ``lu`` (:13-16).  Systems of up to ``-pynama_direct_max_rows`` rows
 (default 8192 = the library's limit; one rank) ARE solved directly: ``pyn_solve_direct`` factors the matrix densely with partial pivoting once
@@ -167,7 +170,8 @@ class KspSolver(object):
             if tag is None:
                 raise ValueError("-pynama_mat_free: this operator has no matrix-free form (structured Q1 hex meshes; "
                                  "second-order structured meshes of affine cells with -pynama_mat_free_ngl3; box meshes "
-                                 "of affine cells of order ngl 4..12 in 2-D / 4..8 in 3-D with -pynama_mat_free_ho)")
+                                 "of affine cells of order ngl 4..12 in 2-D / 4..8 in 3-D with -pynama_mat_free_ho; any "
+                                 "quadrilateral / hexahedral mesh of those orders on one rank with -pynama_mat_free_ho_general)")
             mf = tag
         elif self.mat_free is None and tag is not None and self.ksp_type in ('cg', 'preonly'):
             try:                                       # automatic: the shell, unless the library finds it differs from A
