@@ -59,6 +59,9 @@ const char* pyn_last_error(void);
 int pyn_version(void);
 const char* pyn_source_hash(void);   /* first 16 hex digits of the sha256 of the kernel sources this library was built from */
 int pyn_device_count(int* count);
+/* device and pinned-host allocations the library holds right now, in this process: their count and their bytes (either pointer may be
+ * NULL).  Needs no device and no context; equal readings before a context is created and after it is destroyed mean nothing leaked. */
+int pyn_alloc_live(int64_t* buffers, int64_t* bytes);
 
 /* ---- context -------------------------------------------------------------------------- */
 int pyn_ctx_create(int device, pyn_ctx** out);

@@ -65,6 +65,7 @@ _pu8 = np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")
 SIGNATURES = {
     "pyn_version": [],
     "pyn_device_count": [C.POINTER(_I)],
+    "pyn_alloc_live": [C.POINTER(_L), C.POINTER(_L)],
     "pyn_ctx_create": [_I, C.POINTER(_P)],
     "pyn_ctx_destroy": [_P],
     "pyn_sync": [_P],
@@ -194,6 +195,13 @@ def _check(rc):
 def source_hash() -> str:
     """identity of the kernel sources the loaded library was built from (profiles/*.json record it)"""
     return load_library().pyn_source_hash().decode()
+
+
+def alloc_live():
+    """(buffers, bytes) of device and pinned-host memory the library holds right now, over all contexts of the process"""
+    n, b = _L(0), _L(0)
+    _check(load_library().pyn_alloc_live(C.byref(n), C.byref(b)))
+    return n.value, b.value
 
 
 def device_count() -> int:

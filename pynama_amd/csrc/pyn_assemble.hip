@@ -1394,7 +1394,7 @@ extern "C" int pyn_assemble_scalar(pyn_ctx* c, int form, int Aid, int Arhs, int 
   // the Jacobi data of A: kernels that see whole rows (lattice store phases) write 1 / diagonal on the way out
   if (Aid >= 0 && form == PYN_FORM_LAPLACE && !k.no_dinv) {
     DMat& m = c->mats[Aid];
-    if (!m.dinv) PYN_HIP(hipMalloc((void**)&m.dinv, (size_t)c->n_owned * sizeof(double)));
+    if (!m.dinv) PYN_HIP(m.dinv.alloc((size_t)c->n_owned));
     rq.dinv = m.dinv;
   }
   PYN_TRY(asm_run(c, rq, k));
@@ -1466,7 +1466,7 @@ extern "C" int pyn_elem_local(pyn_ctx* c, int form, double alpha_d, double alpha
   size_t n1 = kle ? (size_t)dim * nn * dw * nn : 0;
   size_t n2 = kle ? (size_t)dim * nn * nn : 0;
   size_t ncor = (size_t)c->nc * dim;
-  PYN_TRY(pyn_grow(&c->d_eloc, &c->eloc_bytes, (n0 + n1 + n2 + ncor) * sizeof(double)));
+  PYN_HIP(c->d_eloc.grow(n0 + n1 + n2 + ncor));
   double* d_cor = c->d_eloc;
   double* d0 = d_cor + ncor;
   double* d1 = d0 + n0;
@@ -1489,12 +1489,9 @@ extern "C" int pyn_elem_local(pyn_ctx* c, int form, double alpha_d, double alpha
 }
 
 // ---- first-order operator blocks (SrT / DivSrT / Curl of Spectral.getElemKLEOperators, spectral.py:159-218)
-static int upload_terms(pyn_ctx* c, int nterms, const int32_t* terms, const double* coef, int32_t** dt, double** dc) {
-  PYN_HIP(hipMalloc((void**)dt, (size_t)nterms * 3 * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)dc, (size_t)nterms * sizeof(double)));
-  PYN_HIP(hipMemcpyAsync(*dt, terms, (size_t)nterms * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  PYN_HIP(hipMemcpyAsync(*dc, coef, (size_t)nterms * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  return PYN_OK;
+static int upload_terms(pyn_ctx* c, int nterms, const int32_t* terms, const double* coef, DevBuf<int32_t>& dt, DevBuf<double>& dc) {
+  PYN_TRY(dev_upload(dt, terms, (size_t)nterms * 3, c->stream));
+  return dev_upload(dc, coef, (size_t)nterms, c->stream);
 }
 
 static int check_operator(pyn_ctx* c, int rule, int br, int bc, int nterms, const int32_t* terms, const double* coef) {
@@ -1514,9 +1511,9 @@ extern "C" int pyn_assemble_operator(pyn_ctx* c, int rule, int nterms, const int
   PYN_CHECK(!M.rhs_compact, "pyn_assemble_operator: the target must have the graph's full pattern");
   PYN_TRY(check_operator(c, rule, M.br, M.bc, nterms, terms, coef));
   PYN_HIP(hipSetDevice(c->device));
-  int32_t* dt = nullptr;
-  double* dc = nullptr;
-  PYN_TRY(upload_terms(c, nterms, terms, coef, &dt, &dc));
+  DevBuf<int32_t> dt;   // (their release at the end of the call waits for the kernels that read them)
+  DevBuf<double> dc;
+  PYN_TRY(upload_terms(c, nterms, terms, coef, dt, dc));
   AsmRequest rq;
   rq.form = PYN_FORM_OPERATOR;
   rq.op_rule = rule;
@@ -1528,8 +1525,6 @@ extern "C" int pyn_assemble_operator(pyn_ctx* c, int rule, int nterms, const int
   rq.K = M.val;
   M.touch();
   PYN_TRY(asm_run(c, rq, asm_knobs(), dt, dc));   // structured meshes of parallelepipeds: the row-run kernels, else scatter-add
-  PYN_HIP(hipFree(dt));
-  PYN_HIP(hipFree(dc));
   return PYN_OK;
 }
 
@@ -1539,10 +1534,10 @@ extern "C" int pyn_elem_operator_local(pyn_ctx* c, int rule, int br, int bc, int
   PYN_TRY(check_operator(c, rule, br, bc, nterms, terms, coef));
   PYN_HIP(hipSetDevice(c->device));
   const size_t n0 = (size_t)br * c->nn * bc * c->nn, ncor = (size_t)c->nc * c->dim;
-  PYN_TRY(pyn_grow(&c->d_eloc, &c->eloc_bytes, (n0 + ncor) * sizeof(double)));
-  int32_t* dt = nullptr;
-  double* dc = nullptr;
-  PYN_TRY(upload_terms(c, nterms, terms, coef, &dt, &dc));
+  PYN_HIP(c->d_eloc.grow(n0 + ncor));
+  DevBuf<int32_t> dt;   // (their release at the end of the call waits for the kernels that read them)
+  DevBuf<double> dc;
+  PYN_TRY(upload_terms(c, nterms, terms, coef, dt, dc));
   PYN_HIP(hipMemcpyAsync(c->d_eloc, corners, ncor * sizeof(double), hipMemcpyHostToDevice, c->stream));
   AsmArgs A;
   PYN_TRY(fill_args(c, A, PYN_FORM_OPERATOR));
@@ -1557,7 +1552,5 @@ extern "C" int pyn_elem_operator_local(pyn_ctx* c, int rule, int br, int bc, int
   PYN_TRY(launch_generic<true>(c, asm_knobs(), A, 1));
   PYN_HIP(hipMemcpyAsync(out, A.out0, n0 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   PYN_HIP(hipStreamSynchronize(c->stream));
-  PYN_HIP(hipFree(dt));
-  PYN_HIP(hipFree(dc));
   return PYN_OK;
 }

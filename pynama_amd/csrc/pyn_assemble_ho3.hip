@@ -1008,7 +1008,7 @@ int launch_ho3_g(pyn_ctx* c, const AsmKnobs& k, Ho3Args T) {
   T.runflag = nullptr;
   if (T.nbits) {   // which runs see an imposed DOF: once per Dirichlet set and run length
     if (V.runflag_stamp != c->bc_stamp || V.runflag_R != R) {
-      if (!V.d_runflag) PYN_HIP(hipMalloc((void**)&V.d_runflag, (size_t)c->n_owned + 8));
+      if (!V.d_runflag) PYN_HIP(V.d_runflag.alloc((size_t)c->n_owned + 8));
       ho3_runflag_kernel<<<(int)((c->n_owned + 255) / 256), 256, 0, c->stream>>>(T, DIM, NGL - 1, R, c->n_owned, V.d_runflag);
       PYN_HIP(hipGetLastError());
       V.runflag_stamp = c->bc_stamp;
@@ -1101,13 +1101,13 @@ int pyn_ho3_prepare(pyn_ctx* c) {
   Ho3View& L = c->ho3;
   hipStream_t s = c->stream;
   const int gs = c->dim == 3 ? 10 : 6;
-  if (!L.d_geom) PYN_HIP(hipMalloc((void**)&L.d_geom, (size_t)c->n_elem * gs * sizeof(double)));
+  if (!L.d_geom) PYN_HIP(L.d_geom.alloc((size_t)c->n_elem * gs));
   const int ge = (int)((c->n_elem + 255) / 256);
   DevTmp flag;
   int* d_flag = nullptr;
   if (L.affine < 0) {   // once per mesh
     PYN_HIP(flag.alloc(2 * sizeof(int)));   // [0] some cell is not affine, [1] some J is not diagonal
-    PYN_HIP(hipMemsetAsync(flag.p, 0, 2 * sizeof(int), s));
+    PYN_HIP(hipMemsetAsync(flag.get(), 0, 2 * sizeof(int), s));
     d_flag = flag.as<int>();
   }
   // J^-1, detJ of every element (part of the numeric phase: runs inside the timed region of every assembly)
@@ -1143,18 +1143,10 @@ int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]) {
   return PYN_OK;
 }
 
-void pyn_ho3_release(pyn_ctx* c) {
-  Ho3View& L = c->ho3;
-  (void)hipFree(L.d_geom);
-  (void)hipFree(L.d_nbits);
-  (void)hipFree(L.d_runflag);
-  L = Ho3View();
-}
-
 // The ngl 2 / 3 view of c->box: structured meshes of tensor-product cells of order 1 or 2, whose corners sit where the device code has
 // them spelled out (CB2 / CB3)
 void pyn_ho3_view(pyn_ctx* c) {
-  pyn_ho3_release(c);
+  c->ho3 = Ho3View();
   const BoxLattice& B = c->box;
   if (!B.valid || B.ngl > 3 || B.plane() > INT32_MAX / 4 || B.n_own < 1 || getenv("PYNAMA_NO_HO3")) return;
   const LocalOrder lo(B.dim, B.ngl);
@@ -1177,10 +1169,9 @@ int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double
   const int ts = (2 * dd + 3 * dim + 1) & ~1;        // record per node pair (TabRec)
   const size_t total = (size_t)ts * n2;
   if (c->ho3_tabs_nn != nn) {
-    (void)hipFree(c->d_ho3_tabs);
-    c->d_ho3_tabs = nullptr;
     c->ho3_tabs_ok[0] = c->ho3_tabs_ok[1] = c->ho3_tabs_ok[2] = false;
-    PYN_HIP(hipMalloc((void**)&c->d_ho3_tabs, total * sizeof(double)));
+    c->ho3_tabs_nn = 0;   // a failed allocation leaves no records: the next call allocates again
+    PYN_HIP(c->d_ho3_tabs.alloc(total));
     PYN_HIP(hipMemsetAsync(c->d_ho3_tabs, 0, total * sizeof(double), c->stream));
     c->ho3_tabs_host.assign(total, 0.0);
     c->ho3_tabs_nn = nn;
@@ -1273,7 +1264,7 @@ int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double
         }
       }
     if (worst <= 1e-13 * scale) {
-      if (!c->d_ho3_t1d) PYN_HIP(hipMalloc((void**)&c->d_ho3_t1d, 8 * 9 * sizeof(double)));
+      if (!c->d_ho3_t1d) PYN_HIP(c->d_ho3_t1d.alloc(8 * 9));
       PYN_HIP(hipMemcpyAsync(c->d_ho3_t1d, t1, (size_t)8 * n1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
       c->ho3_tens_ok = true;
     }
@@ -1290,31 +1281,29 @@ int pyn_ho3_symbolic(pyn_ctx* c, bool* done) {
   Ho3Args T;
   fill_lattice_args(c, asm_knobs(), T);   // (PYNAMA_HO3_NO_PSTD reaches the symbolic kernels too)
   const int64_t n = c->n_owned;
-  DevTmp tlen, tmp;
-  PYN_HIP(tlen.alloc((n + 1) * sizeof(int32_t)));
-  (void)hipFree(c->d_rowptr);
-  (void)hipFree(c->d_colidx);
-  c->d_rowptr = nullptr;
-  c->d_colidx = nullptr;
-  c->nnzb = 0;
-  PYN_HIP(hipMalloc((void**)&c->d_rowptr, (n + 1) * sizeof(int32_t)));
-  const int grid = (int)((n + 1 + 255) / 256);
-  ho3_rowlen_kernel<<<grid, 256, 0, s>>>(T, L.dim, L.ngl, n, tlen.as<int32_t>());
-  // the total must fit the int32 CSR before the scan wraps: the interior count bounds it
+  // the total must fit the int32 CSR before the scan wraps: the interior count bounds it.  Checked before anything is replaced.
   const double per_elem = L.ngl == 3 ? (L.dim == 3 ? 512.0 : 64.0) : (L.dim == 3 ? 27.0 : 9.0);
   const double est = (double)c->n_elem * per_elem;
   PYN_CHECK(est < 2.0e9, "pattern has about %.3g entries (int32 CSR limit)", est);
+  DevTmp tlen, tmp;
+  DevBuf<int32_t> rowptr, colidx;   // the new graph: committed together at the end
+  PYN_HIP(tlen.alloc((n + 1) * sizeof(int32_t)));
+  PYN_HIP(rowptr.alloc(n + 1));
+  const int grid = (int)((n + 1 + 255) / 256);
+  ho3_rowlen_kernel<<<grid, 256, 0, s>>>(T, L.dim, L.ngl, n, tlen.as<int32_t>());
   size_t tb = 0;
-  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, tlen.as<int32_t>(), c->d_rowptr, (int)(n + 1), s));
+  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, tlen.as<int32_t>(), rowptr.get(), (int)(n + 1), s));
   PYN_HIP(tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, tlen.as<int32_t>(), c->d_rowptr, (int)(n + 1), s));
+  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.get(), tb, tlen.as<int32_t>(), rowptr.get(), (int)(n + 1), s));
   int32_t nnz = 0;
-  PYN_HIP(hipMemcpyAsync(&nnz, c->d_rowptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipMemcpyAsync(&nnz, rowptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipStreamSynchronize(s));
   PYN_CHECK(nnz > 0, "empty pattern");
-  PYN_HIP(hipMalloc((void**)&c->d_colidx, (size_t)nnz * sizeof(int32_t)));
-  ho3_columns_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(T, L.dim, L.ngl, n, c->d_rowptr, c->d_colidx);
+  PYN_HIP(colidx.alloc((size_t)nnz));
+  ho3_columns_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(T, L.dim, L.ngl, n, rowptr, colidx);
   PYN_HIP(hipGetLastError());
+  c->d_rowptr = std::move(rowptr);   // (freeing the old graph waits for the device: no kernel still reads it)
+  c->d_colidx = std::move(colidx);
   c->nnzb = nnz;
   *done = true;
   return PYN_OK;
@@ -1343,7 +1332,7 @@ int pyn_assemble_ho3_lattice(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k
   }
   if (c->d_bcmask) {
     if (L.nbits_stamp != c->bc_stamp) {
-      if (!L.d_nbits) PYN_HIP(hipMalloc((void**)&L.d_nbits, (size_t)c->n_node));
+      if (!L.d_nbits) PYN_HIP(L.d_nbits.alloc((size_t)c->n_node));
       ho3_pack_bits_kernel<<<(int)((c->n_node + 255) / 256), 256, 0, c->stream>>>(c->d_bcmask, c->n_node, c->bc_ndof, L.d_nbits);
       L.nbits_stamp = c->bc_stamp;
     }

@@ -1486,7 +1486,6 @@ __global__ void lattice_symbolic_kernel(LatArgs T, int64_t n_rows, int32_t* __re
 // c->box at dim 3, ngl 2 (the detector's plane limit is this view's), + the z-neighbour planes of every plane in id order (zord)
 int pyn_lattice_view(pyn_ctx* c) {
   Lattice& L = c->lat;
-  (void)hipFree(L.d_zord);
   L = Lattice();
   const BoxLattice& B = c->box;
   if (!B.valid || B.dim != 3 || B.ngl != 2 || getenv("PYNAMA_NO_LATTICE")) return PYN_OK;
@@ -1502,8 +1501,10 @@ int pyn_lattice_view(pyn_ctx* c) {
     for (int i = 0; i < n; ++i) code |= (dz[i] + 1) << (2 + 2 * i);
     zord[j] = code;
   }
-  PYN_HIP(hipMalloc((void**)&L.d_zord, npl * sizeof(int32_t)));
-  PYN_HIP(hipMemcpy(L.d_zord, zord.data(), npl * sizeof(int32_t), hipMemcpyHostToDevice));
+  DevBuf<int32_t> d_zord;
+  PYN_HIP(d_zord.alloc(npl));
+  PYN_HIP(hipMemcpy(d_zord, zord.data(), npl * sizeof(int32_t), hipMemcpyHostToDevice));
+  L.d_zord = std::move(d_zord);
   L.std_shape = B.slab_order();   // the arithmetic shape lat_plane / lat_zcode assume (one rank, or a rank's z-slab)
   L.valid = true;
   return PYN_OK;
@@ -1562,13 +1563,13 @@ int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k) {
       DevTmp flag;
       PYN_HIP(flag.alloc(sizeof(int)));
       const int one = 1;
-      PYN_HIP(hipMemcpyAsync(flag.p, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
+      PYN_HIP(hipMemcpyAsync(flag.get(), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
       LatArgs Tc;
       lat_fill(c, k, Tc);
       Tc.std_lat = 1;
       lattice_rowptr_check_kernel<<<(int)((c->n_owned + 255) / 256), 256, 0, c->stream>>>(Tc, c->d_rowptr, c->n_owned, flag.as<int>());
       int h = 0;
-      PYN_HIP(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
       PYN_HIP(hipStreamSynchronize(c->stream));
       L.std_ok = h;
     }
@@ -1608,7 +1609,7 @@ static int launch_kle_lattice(pyn_ctx* c, KleLatArgs& T, double* K, double* Krhs
   if (K) {
     if (GEN) {   // the element Laplacians, once per element
       const int64_t ne = (int64_t)(T.L.nx - 1) * (T.L.ny - 1) * (T.L.npl - 1);
-      PYN_TRY(pyn_grow(&c->d_kle_lel, &c->kle_lel_bytes, (size_t)28 * ne * sizeof(double)));
+      PYN_HIP(c->d_kle_lel.grow((size_t)28 * ne));
       kle_elem_laplace_kernel<<<(int)((ne + 255) / 256), 256, 0, c->stream>>>(T.L, c->d_kle_lel, ne);
       T.Lel = c->d_kle_lel;
       T.ne = ne;
@@ -1886,14 +1887,13 @@ int pyn_lattice_symbolic(pyn_ctx* c, bool* done) {
   const int64_t sx = 3 * (int64_t)L.NX - 2, sy = 3 * (int64_t)L.NY - 2;
   const int64_t nnz = (3 * (int64_t)L.n_own - (L.p_own0 == 0 ? 1 : 0) - (L.p_own0 + L.n_own == L.npl ? 1 : 0)) * sy * sx;
   PYN_CHECK(nnz > 0 && nnz < (int64_t)INT32_MAX, "pattern has %lld entries (int32 CSR limit)", (long long)nnz);
-  (void)hipFree(c->d_rowptr);
-  (void)hipFree(c->d_colidx);
-  c->d_rowptr = nullptr;
-  c->d_colidx = nullptr;
-  PYN_HIP(hipMalloc((void**)&c->d_rowptr, (c->n_owned + 1) * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&c->d_colidx, nnz * sizeof(int32_t)));
-  lattice_symbolic_kernel<<<(int)((c->n_owned + 1 + 255) / 256), 256, 0, c->stream>>>(T, c->n_owned, c->d_rowptr, c->d_colidx);
+  DevBuf<int32_t> rowptr, colidx;   // the new graph: committed together at the end
+  PYN_HIP(rowptr.alloc(c->n_owned + 1));
+  PYN_HIP(colidx.alloc(nnz));
+  lattice_symbolic_kernel<<<(int)((c->n_owned + 1 + 255) / 256), 256, 0, c->stream>>>(T, c->n_owned, rowptr, colidx);
   PYN_HIP(hipGetLastError());
+  c->d_rowptr = std::move(rowptr);   // (freeing the old graph waits for the device: no kernel still reads it)
+  c->d_colidx = std::move(colidx);
   c->nnzb = nnz;
   *done = true;
   return PYN_OK;

@@ -340,7 +340,7 @@ int launch_march(pyn_ctx* c, const AsmKnobs& k, LatArgs& T, int wg_per_cu) {
   const int nblk = ncol * nzc;
   if (k.march_stamps) {
     PYN_HIP(stamps.alloc((size_t)nblk * 32 * 8 * sizeof(unsigned long long)));
-    PYN_HIP(hipMemsetAsync(stamps.p, 0, (size_t)nblk * 32 * 8 * sizeof(unsigned long long), c->stream));
+    PYN_HIP(hipMemsetAsync(stamps.get(), 0, (size_t)nblk * 32 * 8 * sizeof(unsigned long long), c->stream));
     T.dbg = stamps.as<unsigned long long>();
   }
   assemble_q1_hex_march_kernel<TX, TY, WPS, ROLLED><<<nblk, MT::NT, MT::BYTES, c->stream>>>(T, zlen, ws);

@@ -1049,18 +1049,11 @@ extern "C" int pyn_patch_plan_info(pyn_ctx* c, int kind, int64_t* info) {
 static int patch_plan_install(pyn_ctx* c, int kind, int n_patch, const int32_t* patch_ptr, const int32_t* patch_rows, bool user) {
   PYN_CHECK(c, "ctx is NULL");
   PYN_CHECK(kind == 0 || kind == 1, "plan kind must be 0 (scalar) or 1 (KLE)");
-  PatchPlan& P = c->plan[kind];
   const int max_rows_allowed = kind == 0 ? PATCH_MAX_ROWS : KLE_MAX_ROWS;
   PYN_HIP(hipSetDevice(c->device));
-  // drop an existing plan
-  (void)hipFree(P.rowptr);
-  (void)hipFree(P.rows);
-  (void)hipFree(P.eptr);
-  (void)hipFree(P.elem);
-  (void)hipFree(P.rowslot4);
-  (void)hipFree(P.kmap4);
-  P = PatchPlan();
+  c->plan[kind] = PatchPlan();   // drop an existing plan
   if (n_patch == 0) return PYN_OK;
+  PatchPlan P;                   // the new one: installed at the end, after the last step that can fail
   PYN_CHECK(patch_ptr && patch_rows, "NULL argument");
   PYN_CHECK(c->d_rowptr, "pyn_csr_symbolic first");
   PYN_CHECK(c->dim == 3 && (c->nn == 8 || (c->nn == 4 && kind == 0)), "patch plans are implemented for Q1 hexahedra (and, scalar forms, linear tetrahedra)");
@@ -1079,8 +1072,8 @@ static int patch_plan_install(pyn_ctx* c, int kind, int n_patch, const int32_t* 
     }
   }
   hipStream_t s = c->stream;
-  PYN_HIP(hipMalloc((void**)&P.rowptr, (n_patch + 1) * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&P.rows, c->n_owned * sizeof(int32_t)));
+  PYN_HIP(P.rowptr.alloc(n_patch + 1));
+  PYN_HIP(P.rows.alloc(c->n_owned));
   PYN_HIP(hipMemcpyAsync(P.rowptr, patch_ptr, (n_patch + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
   PYN_HIP(hipMemcpyAsync(P.rows, patch_rows, c->n_owned * sizeof(int32_t), hipMemcpyHostToDevice, s));
   DevTmp t_n2p, t_n2s, t_k0, t_k1, t_npe, t_tmp, t_cnt;  // scratch, released on every exit path
@@ -1099,7 +1092,7 @@ static int patch_plan_install(pyn_ctx* c, int kind, int n_patch, const int32_t* 
   size_t tb = 0;
   PYN_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, k0, k1, nk, 0, 64, s));
   PYN_HIP(t_tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceRadixSort::SortKeys(t_tmp.p, tb, k0, k1, nk, 0, 64, s));
+  PYN_HIP(hipcub::DeviceRadixSort::SortKeys(t_tmp.get(), tb, k0, k1, nk, 0, 64, s));
   plan_count_valid_kernel<<<1, 1, 0, s>>>(k1, nk, d_npe);
   int64_t npe = 0;
   PYN_HIP(hipMemcpyAsync(&npe, d_npe, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -1108,18 +1101,18 @@ static int patch_plan_install(pyn_ctx* c, int kind, int n_patch, const int32_t* 
   PYN_HIP(t_cnt.alloc((n_patch + 1) * sizeof(int32_t)));
   int32_t* ecount = t_cnt.as<int32_t>();
   PYN_HIP(hipMemsetAsync(ecount, 0, (n_patch + 1) * sizeof(int32_t), s));
-  PYN_HIP(hipMalloc((void**)&P.eptr, (n_patch + 1) * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&P.elem, npe * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&P.rowslot4, npe * sizeof(uint4)));
-  PYN_HIP(hipMalloc((void**)&P.kmap4, 4 * npe * sizeof(uint4)));
+  PYN_HIP(P.eptr.alloc(n_patch + 1));
+  PYN_HIP(P.elem.alloc(npe));
+  PYN_HIP(P.rowslot4.alloc(npe));
+  PYN_HIP(P.kmap4.alloc(4 * npe));
   grid = (int)std::min<int64_t>((npe + 255) / 256, 65536);
   plan_fill_kernel<<<grid, 256, 0, s>>>(k1, npe, c->d_conn, c->nn, c->n_owned, node2patch, node2slot, c->d_rowptr, c->d_colidx,
-                                        P.elem, ecount, (uint4*)P.rowslot4, (uint4*)P.kmap4);
+                                        P.elem, ecount, P.rowslot4, P.kmap4);
   tb = 0;
-  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ecount, P.eptr, n_patch + 1, s));
+  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ecount, P.eptr.get(), n_patch + 1, s));
   PYN_HIP(hipStreamSynchronize(s));
   PYN_HIP(t_tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(t_tmp.p, tb, ecount, P.eptr, n_patch + 1, s));
+  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(t_tmp.get(), tb, ecount, P.eptr.get(), n_patch + 1, s));
   // max row length of the graph (LDS row stride)
   std::vector<int32_t> rp((size_t)c->n_owned + 1);
   PYN_HIP(hipMemcpyAsync(rp.data(), c->d_rowptr, (c->n_owned + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -1146,6 +1139,7 @@ static int patch_plan_install(pyn_ctx* c, int kind, int n_patch, const int32_t* 
                            (const void*)assemble_q1_hex_kle_affine_kernel<false>, (const void*)assemble_q1_hex_kle_affine_kernel<true>})
       PYN_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // the size follows the plan: always
   }
+  c->plan[kind] = std::move(P);
   return PYN_OK;
 }
 
@@ -1185,12 +1179,12 @@ int pyn_mesh_all_affine(pyn_ctx* c, int* out) {
       DevTmp flag;
       PYN_HIP(flag.alloc(sizeof(int)));
       const int one = 1;
-      PYN_HIP(hipMemcpyAsync(flag.p, &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
+      PYN_HIP(hipMemcpyAsync(flag.get(), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
       TileArgs q = TileArgs();
       q.aff = c->d_aff;
       mesh_all_affine_kernel<<<(int)((c->n_elem + 255) / 256), 256, 0, c->stream>>>(c->d_conn, c->d_xyz, c->n_elem, q, flag.as<int>());
       int h = 0;
-      PYN_HIP(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
       PYN_HIP(hipStreamSynchronize(c->stream));
       c->mesh_affine = h;
     }
@@ -1250,8 +1244,8 @@ static void patch_fill(const pyn_ctx* c, const AsmKnobs& k, const PatchPlan& P, 
   T.p_rows = P.rows;
   T.p_eptr = P.eptr;
   T.p_elem = P.elem;
-  T.rowslot4 = (const uint4*)P.rowslot4;
-  T.kmap4 = (const uint4*)P.kmap4;
+  T.rowslot4 = P.rowslot4;
+  T.kmap4 = P.kmap4;
   T.npe = P.npe;
   T.maxlen = P.maxlen;
   T.maxrows = P.maxrows;

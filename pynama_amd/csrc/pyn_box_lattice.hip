@@ -79,16 +79,11 @@ __global__ void box_conn_verify_kernel(const int32_t* __restrict__ conn, const i
   if (conn[t] != id) atomicAdd(bad, 1);
 }
 
-void pyn_box_release(pyn_ctx* c) {
-  (void)hipFree(c->box.d_P);
-  c->box = BoxLattice();
-}
-
 // `at(i)`: entry i of the local connectivity as the host sees it (the uploaded array, or the closed form of pyn_mesh_box); the shape
 // guessed from O(element rows + layers) entries is checked against ALL of c->d_conn on the device.  Applies what every view asks for;
 // the views add their own limits.
 int pyn_box_detect(pyn_ctx* c, const ConnAt& at) {
-  pyn_box_release(c);
+  c->box = BoxLattice();
   const int dim = c->dim, nn = c->nn, ngl = c->ngl;
   if (ngl < 2 || c->n_elem < 1) return PYN_OK;
   const int m = ngl - 1;
@@ -136,24 +131,22 @@ int pyn_box_detect(pyn_ctx* c, const ConnAt& at) {
   if (p0 < 0 || p0 + n_own > npl) return PYN_OK;
   for (int j = 0; j < n_own; ++j)
     if (P[p0 + j] != (int64_t)j * PS) return PYN_OK;
-  DevTmp d_P, d_bad, d_loc;
+  DevBuf<int32_t> d_P, d_loc;
+  DevBuf<int> d_bad;
   int bad = 0;
   const std::vector<int32_t> loc32(loc.begin(), loc.end());
-  PYN_HIP(d_P.alloc(npl * sizeof(int32_t)));
-  PYN_HIP(d_bad.alloc(sizeof(int)));
-  PYN_HIP(d_loc.alloc(loc32.size() * sizeof(int32_t)));
-  PYN_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), c->stream));
-  PYN_HIP(hipMemcpyAsync(d_P.p, P.data(), npl * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  PYN_HIP(hipMemcpyAsync(d_loc.p, loc32.data(), loc32.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  box_conn_verify_kernel<<<(unsigned)((ne * nn + 255) / 256), 256, 0, c->stream>>>(c->d_conn, d_P.as<int32_t>(), d_loc.as<int32_t>(), dim, nn, m,
-                                                                                 ne, (int)EX, (int)EY, (int)NX, per_layer, d_bad.as<int>());
+  PYN_TRY(dev_upload(d_P, (const int32_t*)P.data(), (size_t)npl, c->stream));
+  PYN_TRY(dev_upload(d_loc, loc32.data(), loc32.size(), c->stream));
+  PYN_HIP(d_bad.alloc(1));
+  PYN_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
+  box_conn_verify_kernel<<<(unsigned)((ne * nn + 255) / 256), 256, 0, c->stream>>>(c->d_conn, d_P, d_loc, dim, nn, m, ne, (int)EX, (int)EY, (int)NX,
+                                                                                 per_layer, d_bad);
   PYN_HIP(hipGetLastError());
-  PYN_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  PYN_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   PYN_HIP(hipStreamSynchronize(c->stream));
   if (bad) return PYN_OK;
   BoxLattice& B = c->box;
-  B.d_P = d_P.as<int32_t>();
-  d_P.p = nullptr;   // kept: released by pyn_box_release
+  B.d_P = std::move(d_P);
   B.P = P;
   B.dim = dim;
   B.ngl = ngl;

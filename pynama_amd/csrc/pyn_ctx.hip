@@ -28,9 +28,8 @@ struct pyn_shm_comm {
   int64_t cap = 0;
   // asynchronous exchange: pinned staging per stream slot (0: main stream, 1: communication stream); a failure inside a stream
   // callback is parked here and reported by the next call that can return it
-  double* stage_out[2] = {nullptr, nullptr};
-  double* stage_in[2] = {nullptr, nullptr};
-  size_t stage_in_cap[2] = {0, 0};
+  PinBuf<unsigned char> stage_out[2];   // [cap] bytes
+  PinBuf<double> stage_in[2];           // [n_ghost * 6]
   std::atomic<int> failed{0};
   char fail_msg[256] = "";
   pyn_shm_hdr* hdr() const { return reinterpret_cast<pyn_shm_hdr*>(base); }
@@ -69,15 +68,9 @@ extern "C" int pyn_device_count(int* count) {
   return PYN_OK;
 }
 
-template <typename T>
-static int dev_upload(T** dst, const T* src, size_t n, hipStream_t s) {
-  if (*dst) {
-    PYN_HIP(hipFree(*dst));
-    *dst = nullptr;
-  }
-  if (n == 0) return PYN_OK;
-  PYN_HIP(hipMalloc((void**)dst, n * sizeof(T)));
-  if (src) PYN_HIP(hipMemcpyAsync(*dst, src, n * sizeof(T), hipMemcpyHostToDevice, s));
+extern "C" int pyn_alloc_live(int64_t* buffers, int64_t* bytes) {
+  if (buffers) *buffers = pyn_live_buffers.load();
+  if (bytes) *bytes = pyn_live_bytes.load();
   return PYN_OK;
 }
 
@@ -97,7 +90,7 @@ extern "C" int pyn_ctx_create(int device, pyn_ctx** out) {
     pyn_set_error("device %d is %s; this library is built for gfx950 (MI355X) only", device, prop.gcnArchName);
     return PYN_ENOGPU;
   }
-  pyn_ctx* c = new pyn_ctx();
+  std::unique_ptr<pyn_ctx> c(new pyn_ctx());   // a failure below destroys what was created so far
   c->device = device;
   PYN_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   PYN_HIP(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
@@ -105,87 +98,36 @@ extern "C" int pyn_ctx_create(int device, pyn_ctx** out) {
   PYN_HIP(hipEventCreate(&c->ev1));
   PYN_HIP(hipEventCreateWithFlags(&c->ev_vec, hipEventDisableTiming));
   PYN_HIP(hipEventCreateWithFlags(&c->ev_halo, hipEventDisableTiming));
-  PYN_HIP(hipMalloc((void**)&c->d_part, 8 * PYN_MAX_PARTIALS * sizeof(double)));
-  PYN_HIP(hipMalloc((void**)&c->d_scal, 64 * sizeof(double)));
-  PYN_HIP(hipMalloc((void**)&c->d_flag, 8 * sizeof(int)));
+  PYN_HIP(c->d_part.alloc(8 * PYN_MAX_PARTIALS));
+  PYN_HIP(c->d_scal.alloc(64));
+  PYN_HIP(c->d_flag.alloc(8));
   PYN_HIP(hipMemset(c->d_scal, 0, 64 * sizeof(double)));
   PYN_HIP(hipMemset(c->d_flag, 0, 8 * sizeof(int)));
-  PYN_HIP(hipHostMalloc((void**)&c->h_scal, 64 * sizeof(double), hipHostMallocDefault));
-  PYN_HIP(hipHostMalloc((void**)&c->h_flag, 8 * sizeof(int), hipHostMallocDefault));
-  *out = c;
+  PYN_HIP(c->h_scal.alloc(64));
+  PYN_HIP(c->h_flag.alloc(8));
+  *out = c.release();
   return PYN_OK;
 }
 
-static void free_quad(QuadTab& q) {
-  (void)hipFree(q.w);
-  (void)hipFree(q.H);
-  (void)hipFree(q.Hrs);
-  (void)hipFree(q.HrsCoo);
-  q = QuadTab();
+// What is not memory, in the order that lets the members free themselves afterwards: nothing is in flight once both streams drained.
+pyn_ctx::~pyn_ctx() {
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (comm_stream) (void)hipStreamSynchronize(comm_stream);
+  if (comm_halo && comm_halo != comm) ncclCommDestroy(comm_halo);
+  if (comm) ncclCommDestroy(comm);
+  if (shm) {
+    munmap(shm->base, shm->size);
+    delete shm;   // + its pinned staging
+  }
+  for (auto e : prof_ev) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {ev0, ev1, ev_vec, ev_halo})
+    if (e) (void)hipEventDestroy(e);
+  if (comm_stream) (void)hipStreamDestroy(comm_stream);
+  if (stream) (void)hipStreamDestroy(stream);
 }
 
 extern "C" int pyn_ctx_destroy(pyn_ctx* c) {
-  if (!c) return PYN_OK;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  if (c->comm_halo && c->comm_halo != c->comm) ncclCommDestroy(c->comm_halo);
-  if (c->comm) ncclCommDestroy(c->comm);
-  if (c->shm) {
-    (void)hipStreamSynchronize(c->comm_stream);
-    for (int k = 0; k < 2; ++k) {
-      (void)hipHostFree(c->shm->stage_out[k]);
-      (void)hipHostFree(c->shm->stage_in[k]);
-    }
-    munmap(c->shm->base, c->shm->size);
-    delete c->shm;
-    c->shm = nullptr;
-  }
-  for (auto& m : c->mats) {
-    (void)hipFree(m.val);
-    (void)hipFree(m.sell_val);
-    (void)hipFree(m.dinv);
-    m.release_lu();
-    m.release_mg();
-    pyn_rhs_release(m);
-  }
-  (void)hipFree(c->d_esel);
-  pyn_sell_drop_structure(c);
-  for (auto& v : c->vecs) (void)hipFree(v.d);
-  for (int k = 0; k < PYN_MATFREE_SLOTS; ++k) (void)hipFree(c->mf_mask[k]);
-  for (auto& q : c->quad) free_quad(q);
-  (void)hipFree(c->d_conn);
-  (void)hipFree(c->d_xyz);
-  (void)hipFree(c->d_aff);
-  (void)hipFree(c->lat.d_zord);
-  pyn_box_release(c);
-  pyn_ho3_release(c);
-  pyn_ho_release(c);
-  pyn_ibm_release(c);
-  pyn_nodesets_release(c);
-  (void)hipFree(c->d_ho3_tabs);
-  (void)hipFree(c->d_ho3_t1d);
-  (void)hipFree(c->d_bcmask);
-  (void)hipFree(c->d_rowptr);
-  (void)hipFree(c->d_colidx);
-  (void)pyn_patch_plan_set_kind(c, 0, 0, nullptr, nullptr);
-  (void)pyn_patch_plan_set_kind(c, 1, 0, nullptr, nullptr);
-  (void)hipFree(c->d_send_idx);
-  (void)hipFree(c->d_send_buf);
-  (void)hipFree(c->d_part);
-  (void)hipFree(c->d_scal);
-  (void)hipFree(c->d_flag);
-  (void)hipFree(c->d_work);
-  (void)hipFree(c->d_eloc);
-  (void)hipFree(c->d_kle_lel);
-  (void)hipHostFree(c->h_scal);
-  (void)hipHostFree(c->h_flag);
-  for (auto e : c->prof_ev) (void)hipEventDestroy(e);
-  (void)hipEventDestroy(c->ev0);
-  (void)hipEventDestroy(c->ev1);
-  (void)hipEventDestroy(c->ev_vec);
-  (void)hipEventDestroy(c->ev_halo);
-  (void)hipStreamDestroy(c->comm_stream);
-  (void)hipStreamDestroy(c->stream);
   delete c;
   return PYN_OK;
 }
@@ -196,7 +138,10 @@ extern "C" int pyn_sync(pyn_ctx* c) {
   return PYN_OK;
 }
 
-int pyn_ensure_work(pyn_ctx* c, size_t bytes) { return pyn_grow(&c->d_work, &c->work_bytes, bytes); }
+int pyn_ensure_work(pyn_ctx* c, size_t bytes) {
+  PYN_HIP(c->d_work.grow((bytes + sizeof(double) - 1) / sizeof(double)));
+  return PYN_OK;
+}
 
 // Kernel attributes belong to a device, so they are remembered per context (released with it): a process-wide "done" flag would
 // leave a second context on another device at the 64 KB default.  For kernels that always ask for the SAME size only: contexts of one
@@ -477,10 +422,8 @@ extern "C" int pyn_halo_set(pyn_ctx* c, int64_t n_owned, int64_t n_ghost, int n_
   c->n_send = c->send_ptr[n_neigh];
   for (int k = 0; k < n_neigh; ++k) PYN_CHECK(neigh[k] >= 0 && neigh[k] < c->nranks, "bad neighbour");
   for (int64_t i = 0; i < c->n_send; ++i) PYN_CHECK(send_idx[i] >= 0 && send_idx[i] < n_owned, "send_idx out of range");
-  PYN_TRY(dev_upload(&c->d_send_idx, send_idx, (size_t)c->n_send, c->stream));
-  if (c->d_send_buf) PYN_HIP(hipFree(c->d_send_buf));
-  c->d_send_buf = nullptr;
-  if (c->n_send) PYN_HIP(hipMalloc((void**)&c->d_send_buf, (size_t)c->n_send * 6 * sizeof(double)));
+  PYN_TRY(dev_upload(c->d_send_idx, send_idx, (size_t)c->n_send, c->stream));
+  PYN_HIP(c->d_send_buf.alloc((size_t)c->n_send * 6));
   PYN_HIP(hipStreamSynchronize(c->stream));
   c->halo_set = true;
   return PYN_OK;
@@ -515,14 +458,11 @@ int pyn_halo_exchange_on(pyn_ctx* c, double* x, int bs, hipStream_t st) {
     const size_t bytes = (size_t)c->n_send * bs * sizeof(double);
     PYN_CHECK((int64_t)bytes <= m->cap, "halo (%zu bytes) exceeds the shared-memory outbox", bytes);
     const int slot = st == c->comm_stream ? 1 : 0;
-    if (!m->stage_out[slot]) PYN_HIP(hipHostMalloc((void**)&m->stage_out[slot], (size_t)m->cap, hipHostMallocDefault));
+    if (!m->stage_out[slot]) PYN_HIP(m->stage_out[slot].alloc((size_t)m->cap));
     const size_t in_bytes = (size_t)c->n_ghost * bs * sizeof(double);
-    if (in_bytes > m->stage_in_cap[slot]) {
+    if (in_bytes > m->stage_in[slot].size() * sizeof(double)) {
       PYN_HIP(hipStreamSynchronize(st));   // an earlier exchange of this slot may still be copying from the old buffer
-      if (m->stage_in[slot]) PYN_HIP(hipHostFree(m->stage_in[slot]));
-      m->stage_in[slot] = nullptr;
-      PYN_HIP(hipHostMalloc((void**)&m->stage_in[slot], (size_t)c->n_ghost * 6 * sizeof(double), hipHostMallocDefault));
-      m->stage_in_cap[slot] = (size_t)c->n_ghost * 6 * sizeof(double);
+      PYN_HIP(m->stage_in[slot].alloc((size_t)c->n_ghost * 6));
     }
     if (bytes) PYN_HIP(hipMemcpyAsync(m->stage_out[slot], c->d_send_buf, bytes, hipMemcpyDeviceToHost, st));
     ShmExchange* e = new ShmExchange{m, slot, bs, bytes, c->neigh, c->send_ptr, c->recv_ptr};
@@ -599,41 +539,37 @@ __global__ void box_xyz_kernel(BoxArgs B, double* __restrict__ xyz) {
 
 // what pyn_mesh_set / pyn_mesh_box share once c->d_conn and c->d_xyz hold the local mesh
 static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
+  // first drop what belonged to the old mesh, so that a refusal below leaves nothing of it behind:
+  c->mesh_affine = -1;
+  for (int k = 0; k < PYN_MATFREE_SLOTS; ++k) {   // the matrix-free operators
+    c->mf_mask[k].reset();
+    c->mf_set[k] = false;
+  }
+  c->ibm.reset();                 // ... the immersed-boundary marker set
+  for (auto& s : c->nodesets) s = DNodeSet();   // ... every node set (ids are not reused: the slots stay, dead)
+  c->d_rowptr.reset();            // ... and the graph (the matrices go with the next pyn_csr_symbolic)
+  c->d_colidx.reset();
+  c->nnzb = 0;
   {
-    unsigned long long* d_bad = nullptr;
+    DevBuf<unsigned long long> d_bad;
     unsigned long long bad = ~0ull;
     const int64_t n = c->n_elem * c->nn;
-    PYN_HIP(hipMalloc((void**)&d_bad, sizeof(bad)));
+    PYN_HIP(d_bad.alloc(1));
     PYN_HIP(hipMemcpyAsync(d_bad, &bad, sizeof(bad), hipMemcpyHostToDevice, c->stream));
     conn_range_kernel<<<(unsigned)std::min<int64_t>((n + 255) / 256, 4096), 256, 0, c->stream>>>(c->d_conn, n, (int32_t)c->n_node, d_bad);
     PYN_HIP(hipGetLastError());
     PYN_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
     PYN_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(d_bad);
     if (bad != ~0ull) {
       const long long i = (long long)bad;
       c->n_elem = c->n_node = 0;
       PYN_CHECK(false, "conn[%lld]=%d out of range", i, (int)at(i));
     }
   }
-  c->mesh_affine = -1;
-  for (int k = 0; k < PYN_MATFREE_SLOTS; ++k) {   // matrix-free operators belong to the mesh
-    (void)hipFree(c->mf_mask[k]);
-    c->mf_mask[k] = nullptr;
-    c->mf_set[k] = false;
-  }
-  pyn_ibm_release(c);             // ... and so does the immersed-boundary marker set
-  pyn_nodesets_release(c);        // ... and every node set
   PYN_TRY(pyn_box_detect(c, at));   // structured topology: found once, admitted per kernel family
   PYN_TRY(pyn_lattice_view(c));
   pyn_ho3_view(c);
   pyn_ho_view(c);
-  // graph + matrices depend on the mesh
-  (void)hipFree(c->d_rowptr);
-  (void)hipFree(c->d_colidx);
-  c->d_rowptr = nullptr;
-  c->d_colidx = nullptr;
-  c->nnzb = 0;
   return PYN_OK;
 }
 
@@ -670,8 +606,8 @@ extern "C" int pyn_mesh_set(pyn_ctx* c, int dim, int nn, int64_t n_elem, int64_t
                             const double* xyz) {
   PYN_CHECK(c && conn && xyz, "NULL argument");
   PYN_TRY(mesh_sizes(c, dim, nn, n_elem, n_node));
-  PYN_TRY(dev_upload(&c->d_conn, conn, (size_t)n_elem * nn, c->stream));
-  PYN_TRY(dev_upload(&c->d_xyz, xyz, (size_t)n_node * dim, c->stream));
+  PYN_TRY(dev_upload(c->d_conn, conn, (size_t)n_elem * nn, c->stream));
+  PYN_TRY(dev_upload(c->d_xyz, xyz, (size_t)n_node * dim, c->stream));
   return mesh_installed(c, [conn](int64_t i) { return conn[i]; });
 }
 
@@ -704,8 +640,8 @@ extern "C" int pyn_mesh_box(pyn_ctx* c, int dim, int ngl, const int64_t* nel_loc
     lplane[j] = (int32_t)k;
   }
   PYN_TRY(mesh_sizes(c, dim, nn, n_elem, PS * n_planes));
-  PYN_TRY(dev_upload(&c->d_conn, (const int32_t*)nullptr, (size_t)n_elem * nn, c->stream));
-  PYN_TRY(dev_upload(&c->d_xyz, (const double*)nullptr, (size_t)c->n_node * dim, c->stream));
+  PYN_TRY(dev_upload(c->d_conn, (const int32_t*)nullptr, (size_t)n_elem * nn, c->stream));
+  PYN_TRY(dev_upload(c->d_xyz, (const double*)nullptr, (size_t)c->n_node * dim, c->stream));
   BoxArgs B;
   B.dim = dim;
   B.nn = nn;
@@ -720,13 +656,13 @@ extern "C" int pyn_mesh_box(pyn_ctx* c, int dim, int ngl, const int64_t* nel_loc
     B.N[d] = d < dim ? (int)lattice[d] : 1;
     if (d < dim) n_axes += lattice[d];
   }
-  int32_t *d_loc = nullptr, *d_lplane = nullptr;
-  int64_t* d_planes = nullptr;
-  double* d_axes = nullptr;
-  PYN_TRY(dev_upload(&d_loc, loc, (size_t)nn * dim, c->stream));
-  PYN_TRY(dev_upload(&d_lplane, lplane.data(), (size_t)n_planes, c->stream));
-  PYN_TRY(dev_upload(&d_planes, planes, (size_t)n_planes, c->stream));
-  PYN_TRY(dev_upload(&d_axes, axes, (size_t)n_axes, c->stream));
+  DevBuf<int32_t> d_loc, d_lplane;
+  DevBuf<int64_t> d_planes;
+  DevBuf<double> d_axes;
+  PYN_TRY(dev_upload(d_loc, loc, (size_t)nn * dim, c->stream));
+  PYN_TRY(dev_upload(d_lplane, (const int32_t*)lplane.data(), (size_t)n_planes, c->stream));
+  PYN_TRY(dev_upload(d_planes, planes, (size_t)n_planes, c->stream));
+  PYN_TRY(dev_upload(d_axes, axes, (size_t)n_axes, c->stream));
   B.loc = d_loc;
   B.lplane = d_lplane;
   B.planes = d_planes;
@@ -735,10 +671,6 @@ extern "C" int pyn_mesh_box(pyn_ctx* c, int dim, int ngl, const int64_t* nel_loc
   box_xyz_kernel<<<(unsigned)((c->n_node + 255) / 256), 256, 0, c->stream>>>(B, c->d_xyz);
   PYN_HIP(hipGetLastError());
   PYN_HIP(hipStreamSynchronize(c->stream));   // the uploads above read host memory of this frame
-  (void)hipFree(d_loc);
-  (void)hipFree(d_lplane);
-  (void)hipFree(d_planes);
-  (void)hipFree(d_axes);
   // the same closed form for the handful of entries the topology detection asks the host for
   const int E0 = B.E[0], E1 = B.E[1], N0 = B.N[0];
   std::vector<int32_t> locv(loc, loc + (size_t)nn * dim);
@@ -783,11 +715,12 @@ extern "C" int pyn_elem_tables_set(pyn_ctx* c, int which, int ngp, const double*
   PYN_CHECK(c->nn > 0, "pyn_mesh_set first");
   PYN_CHECK(ngp > 0, "ngp must be positive");
   QuadTab& q = c->quad[which];
+  q = QuadTab();   // a failed upload leaves the slot empty, not a mix of two rules
+  PYN_TRY(dev_upload(q.w, w, (size_t)ngp, c->stream));
+  PYN_TRY(dev_upload(q.H, H, (size_t)ngp * c->nn, c->stream));
+  PYN_TRY(dev_upload(q.Hrs, Hrs, (size_t)ngp * c->dim * c->nn, c->stream));
+  PYN_TRY(dev_upload(q.HrsCoo, HrsCoo, (size_t)ngp * c->dim * c->nc, c->stream));
   q.ngp = ngp;
-  PYN_TRY(dev_upload(&q.w, w, (size_t)ngp, c->stream));
-  PYN_TRY(dev_upload(&q.H, H, (size_t)ngp * c->nn, c->stream));
-  PYN_TRY(dev_upload(&q.Hrs, Hrs, (size_t)ngp * c->dim * c->nn, c->stream));
-  PYN_TRY(dev_upload(&q.HrsCoo, HrsCoo, (size_t)ngp * c->dim * c->nc, c->stream));
   q.wsum = 0.0;
   for (int g = 0; g < ngp; ++g) q.wsum += w[g];
   PYN_TRY(pyn_ho3_tables(c, which, ngp, w, H, Hrs));   // ngl = 3: reference matrices of the closed-form blocks
@@ -839,7 +772,7 @@ extern "C" int pyn_elem_tables_set(pyn_ctx* c, int which, int ngp, const double*
     c->aff_standard = pyn_q1_affine_tables_standard(aff);
     c->aff_rw_standard = pyn_q1_mixed_tables_standard(w, H, Hrs);
     c->q1_gauss_standard = pyn_q1_gauss_tables_standard(w, H, Hrs, HrsCoo);
-    PYN_TRY(dev_upload(&c->d_aff, aff, (size_t)(6 * 36 + 32 + 9), c->stream));
+    PYN_TRY(dev_upload(c->d_aff, (const double*)aff, (size_t)(6 * 36 + 32 + 9), c->stream));
   }
   if (which == PYN_Q_RED && c->dim == 3 && c->nn == 8) {
     // one point at the centroid, weight 8, gradients s_d(a) / 8, values 1 / 8 (corner order of SURVEY.md A.2)?
@@ -861,13 +794,12 @@ extern "C" int pyn_bc_set(pyn_ctx* c, int ndof, const uint8_t* mask) {
   c->bc_stamp++;
   PYN_CHECK(c->n_node > 0, "pyn_mesh_set first");
   if (!mask) {
-    (void)hipFree(c->d_bcmask);
-    c->d_bcmask = nullptr;
+    c->d_bcmask.reset();
     c->bc_ndof = 0;
     return PYN_OK;
   }
   PYN_CHECK(ndof >= 1 && ndof <= 3, "ndof must be 1..3");
-  PYN_TRY(dev_upload(&c->d_bcmask, mask, (size_t)c->n_node * ndof, c->stream));
+  PYN_TRY(dev_upload(c->d_bcmask, mask, (size_t)c->n_node * ndof, c->stream));
   PYN_HIP(hipStreamSynchronize(c->stream));
   c->bc_ndof = ndof;
   return PYN_OK;
@@ -894,12 +826,11 @@ extern "C" int pyn_mat_create(pyn_ctx* c, int br, int bc, int* mat_id) {
   m.br = br;
   m.bc = bc;
   size_t n = (size_t)c->nnzb * br * bc;
-  PYN_HIP(hipMalloc((void**)&m.val, n * sizeof(double)));
+  PYN_HIP(m.val.alloc(n));
   PYN_HIP(hipMemsetAsync(m.val, 0, n * sizeof(double), c->stream));
-  if (getenv("PYNAMA_DEBUG_ALLOC")) fprintf(stderr, "[pynama] matrix %d: %zu bytes at %p\n", (int)c->mats.size(), n * sizeof(double), (void*)m.val);
   m.rhs_clean = PYN_RHS_ANY;
   m.live = true;
-  c->mats.push_back(m);
+  c->mats.push_back(std::move(m));   // only a matrix whose allocation succeeded gets a handle
   *mat_id = (int)c->mats.size() - 1;
   return PYN_OK;
 }
@@ -908,12 +839,6 @@ extern "C" int pyn_mat_destroy(pyn_ctx* c, int id) {
   PYN_TRY(pyn_check_mat(c, id, "pyn_mat_destroy"));
   DMat& m = c->mats[id];
   PYN_HIP(hipStreamSynchronize(c->stream));   // no kernel in flight may still read the arrays
-  (void)hipFree(m.val);
-  (void)hipFree(m.sell_val);
-  (void)hipFree(m.dinv);
-  m.release_lu();
-  m.release_mg();
-  pyn_rhs_release(m);
   m = DMat();   // live = false: the handle is dead, its slot is not reused (handles stay stable)
   return PYN_OK;
 }
@@ -1003,7 +928,7 @@ extern "C" int pyn_mat_get_values(pyn_ctx* c, int id, double* val) {
     DevTmp full;
     PYN_HIP(full.alloc(bytes));
     PYN_TRY(pyn_rhs_expand(c, m, full.as<double>()));
-    PYN_HIP(hipMemcpyAsync(val, full.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    PYN_HIP(hipMemcpyAsync(val, full.get(), bytes, hipMemcpyDeviceToHost, c->stream));
     PYN_HIP(hipStreamSynchronize(c->stream));
     return PYN_OK;
   }
@@ -1019,16 +944,16 @@ extern "C" int pyn_vec_create(pyn_ctx* c, int bs, int* vec_id) {
   DVec v;
   v.bs = bs;
   size_t n = (size_t)n_local(c) * bs;
-  PYN_HIP(hipMalloc((void**)&v.d, n * sizeof(double)));
+  PYN_HIP(v.d.alloc(n));
   PYN_HIP(hipMemsetAsync(v.d, 0, n * sizeof(double), c->stream));
   v.live = true;
   for (size_t i = 0; i < c->vecs.size(); ++i)
     if (!c->vecs[i].live) {
-      c->vecs[i] = v;
+      c->vecs[i] = std::move(v);
       *vec_id = (int)i;
       return PYN_OK;
     }
-  c->vecs.push_back(v);
+  c->vecs.push_back(std::move(v));
   *vec_id = (int)c->vecs.size() - 1;
   return PYN_OK;
 }
@@ -1036,7 +961,6 @@ extern "C" int pyn_vec_create(pyn_ctx* c, int bs, int* vec_id) {
 extern "C" int pyn_vec_destroy(pyn_ctx* c, int id) {
   PYN_TRY(pyn_check_vec(c, id, "pyn_vec_destroy"));
   PYN_HIP(hipStreamSynchronize(c->stream));
-  PYN_HIP(hipFree(c->vecs[id].d));
   c->vecs[id] = DVec();
   return PYN_OK;
 }

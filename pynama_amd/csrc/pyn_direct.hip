@@ -310,8 +310,8 @@ static int direct_factor(pyn_ctx* c, DMat& A) {
   const int64_t n = c->n_owned * A.br;
   if (A.lu_valid && A.lu_n == n) return PYN_OK;
   if (A.lu_n != n) A.release_lu();
-  if (!A.lu) PYN_HIP(hipMalloc((void**)&A.lu, (size_t)n * n * sizeof(double)));
-  if (!A.lu_piv) PYN_HIP(hipMalloc((void**)&A.lu_piv, (size_t)(2 * n + 1) * sizeof(int)));
+  if (!A.lu) PYN_HIP(A.lu.alloc((size_t)n * n));
+  if (!A.lu_piv) PYN_HIP(A.lu_piv.alloc((size_t)(2 * n + 1)));
   A.lu_n = n;
   hipStream_t s = c->stream;
   PYN_HIP(hipMemsetAsync(A.lu, 0, (size_t)n * n * sizeof(double), s));

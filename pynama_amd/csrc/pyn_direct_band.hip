@@ -448,8 +448,8 @@ int band_factor(pyn_ctx* c, DMat& A, const BandShape& s, int64_t max_bytes) {
     PYN_CHECK((size_t)s.bytes + ((size_t)64 << 20) <= fr,
               "banded LU: the factors take %lld bytes, more than the free device memory (%lld bytes; kl %lld, ku %lld, %lld rows)",
               (long long)s.bytes, (long long)fr, (long long)s.kl, (long long)s.ku, (long long)s.n);
-    PYN_HIP(hipMalloc((void**)&A.band, (size_t)s.band_bytes));
-    PYN_HIP(hipMalloc((void**)&A.band_perm, (size_t)s.perm_bytes + sizeof(int)));
+    PYN_HIP(A.band.alloc((size_t)(s.n * s.W)));
+    PYN_HIP(A.band_perm.alloc((size_t)(s.npanel * (BNB + s.kl)) + 1));
     A.band_n = s.n;
     A.band_kl = s.kl;
     A.band_ku = s.ku;

@@ -19,13 +19,6 @@
 
 #pragma clang fp contract(off)
 
-void pyn_nodesets_release(pyn_ctx* c) {
-  for (auto& s : c->nodesets) {
-    (void)hipFree(s.d);
-    s = DNodeSet();
-  }
-}
-
 namespace {
 
 struct FieldInfo {
@@ -160,17 +153,10 @@ extern "C" int pyn_nodeset_create(pyn_ctx* c, int64_t n, const int32_t* nodes, i
   PYN_HIP(hipSetDevice(c->device));
   DNodeSet s;
   s.n = n;
-  if (n) {
-    PYN_HIP(hipMalloc((void**)&s.d, (size_t)n * sizeof(int32_t)));
-    hipError_t e = hipMemcpyAsync(s.d, nodes, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // nodes is borrowed for the call only
-    if (e != hipSuccess) {
-      (void)hipFree(s.d);
-      PYN_HIP(e);
-    }
-  }
+  PYN_TRY(dev_upload(s.d, nodes, (size_t)n, c->stream));
+  if (n) PYN_HIP(hipStreamSynchronize(c->stream));   // nodes is borrowed for the call only
   s.live = true;
-  c->nodesets.push_back(s);
+  c->nodesets.push_back(std::move(s));
   *set_id = (int)c->nodesets.size() - 1;
   return PYN_OK;
 }
@@ -180,7 +166,6 @@ extern "C" int pyn_nodeset_destroy(pyn_ctx* c, int set_id) {
   PYN_CHECK(set_id >= 0 && set_id < (int)c->nodesets.size() && c->nodesets[set_id].live, "pyn_nodeset_destroy: invalid node set handle %d",
             set_id);
   PYN_HIP(hipStreamSynchronize(c->stream));   // a queued launch may still read it
-  PYN_HIP(hipFree(c->nodesets[set_id].d));
   c->nodesets[set_id] = DNodeSet();
   return PYN_OK;
 }

@@ -31,43 +31,24 @@ struct IbmState {
   int N[3] = {1, 1, 1};
   double lower[3] = {0, 0, 0}, h[3] = {1, 1, 1};
   int64_t cap_n = 0, cap_pairs = 0;
-  double* X = nullptr;          // [n][dim]
-  double* cw = nullptr;         // [n] c_k = dl_k / prod h
-  int32_t* base = nullptr;      // [n][dim] first lattice line of the marker's stencil per axis
-  double* A = nullptr;          // [n][n] row-major
-  double* lu = nullptr;         // its factors
-  int* piv = nullptr;           // [2 n + 1]
-  double* rq = nullptr;         // [dim][n] residual, [dim][n] forcing, [n] solve scratch, [n][dim] host-layout staging
-  int32_t *key0 = nullptr, *key1 = nullptr, *val0 = nullptr, *val1 = nullptr;   // (node, pair) before / after the sort
-  int32_t* flag = nullptr;      // [pairs] run heads
-  int32_t* segptr = nullptr;    // [naff + 1] first sorted pair of every affected node
-  int32_t* nodes = nullptr;     // [naff]
-  int32_t* smk = nullptr;       // [pairs] marker of the sorted pair
-  double* sw = nullptr;         // [pairs] W_kj c_k of the sorted pair
-  void* tmp = nullptr;          // hipCUB scratch (grown on demand)
-  size_t tmp_bytes = 0;
-  int64_t* d_cnt = nullptr;
-
-  void free_sized() {
-    for (void* p : {(void*)X, (void*)cw, (void*)base, (void*)A, (void*)lu, (void*)piv, (void*)rq, (void*)key0, (void*)key1, (void*)val0,
-                    (void*)val1, (void*)flag, (void*)segptr, (void*)nodes, (void*)smk, (void*)sw})
-      (void)hipFree(p);
-    X = cw = A = lu = rq = sw = nullptr;
-    base = key0 = key1 = val0 = val1 = flag = segptr = nodes = smk = nullptr;
-    piv = nullptr;
-    cap_n = cap_pairs = 0;
-  }
-  ~IbmState() {
-    free_sized();
-    (void)hipFree(tmp);
-    (void)hipFree(d_cnt);
-  }
+  DevBuf<double> X;             // [n][dim]
+  DevBuf<double> cw;            // [n] c_k = dl_k / prod h
+  DevBuf<int32_t> base;         // [n][dim] first lattice line of the marker's stencil per axis
+  DevBuf<double> A;             // [n][n] row-major
+  DevBuf<double> lu;            // its factors
+  DevBuf<int> piv;              // [2 n + 1]
+  DevBuf<double> rq;            // [dim][n] residual, [dim][n] forcing, [n] solve scratch, [n][dim] host-layout staging
+  DevBuf<int32_t> key0, key1, val0, val1;   // (node, pair) before / after the sort
+  DevBuf<int32_t> flag;         // [pairs] run heads
+  DevBuf<int32_t> segptr;       // [naff + 1] first sorted pair of every affected node
+  DevBuf<int32_t> nodes;        // [naff]
+  DevBuf<int32_t> smk;          // [pairs] marker of the sorted pair
+  DevBuf<double> sw;            // [pairs] W_kj c_k of the sorted pair
+  DevBuf<unsigned char> tmp;    // hipCUB scratch (grown on demand)
+  DevBuf<int64_t> d_cnt;
 };
 
-void pyn_ibm_release(pyn_ctx* c) {
-  delete c->ibm;
-  c->ibm = nullptr;
-}
+void IbmStateDelete::operator()(IbmState* s) const { delete s; }
 
 namespace {
 
@@ -259,29 +240,19 @@ IbmGrid grid_of(const IbmState& S) {
   return G;
 }
 
-int ibm_tmp(IbmState& S, size_t bytes) {
-  if (bytes <= S.tmp_bytes) return PYN_OK;
-  (void)hipFree(S.tmp);
-  S.tmp = nullptr;
-  S.tmp_bytes = 0;
-  PYN_HIP(hipMalloc(&S.tmp, bytes));
-  S.tmp_bytes = bytes;
-  return PYN_OK;
-}
-
 int ibm_alloc(IbmState& S, int64_t n, int dim, int64_t pairs) {
   if (n <= S.cap_n && pairs <= S.cap_pairs) return PYN_OK;
-  S.free_sized();
-  PYN_HIP(hipMalloc((void**)&S.X, (size_t)n * 3 * sizeof(double)));
-  PYN_HIP(hipMalloc((void**)&S.cw, (size_t)n * sizeof(double)));
-  PYN_HIP(hipMalloc((void**)&S.base, (size_t)n * 3 * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&S.A, (size_t)n * n * sizeof(double)));
-  PYN_HIP(hipMalloc((void**)&S.lu, (size_t)n * n * sizeof(double)));
-  PYN_HIP(hipMalloc((void**)&S.piv, (size_t)(2 * n + 1) * sizeof(int)));
-  PYN_HIP(hipMalloc((void**)&S.rq, (size_t)n * 10 * sizeof(double)));
-  for (int32_t** p : {&S.key0, &S.key1, &S.val0, &S.val1, &S.flag, &S.nodes, &S.smk}) PYN_HIP(hipMalloc((void**)p, (size_t)pairs * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&S.segptr, (size_t)(pairs + 1) * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&S.sw, (size_t)pairs * sizeof(double)));
+  S.cap_n = S.cap_pairs = 0;   // a failure below leaves no capacity (and no valid set): the next pyn_ibm_set allocates all of them again
+  PYN_HIP(S.X.alloc((size_t)n * 3));
+  PYN_HIP(S.cw.alloc((size_t)n));
+  PYN_HIP(S.base.alloc((size_t)n * 3));
+  PYN_HIP(S.A.alloc((size_t)n * n));
+  PYN_HIP(S.lu.alloc((size_t)n * n));
+  PYN_HIP(S.piv.alloc((size_t)(2 * n + 1)));
+  PYN_HIP(S.rq.alloc((size_t)n * 10));
+  for (DevBuf<int32_t>* p : {&S.key0, &S.key1, &S.val0, &S.val1, &S.flag, &S.nodes, &S.smk}) PYN_HIP(p->alloc((size_t)pairs));
+  PYN_HIP(S.segptr.alloc((size_t)(pairs + 1)));
+  PYN_HIP(S.sw.alloc((size_t)pairs));
   S.cap_n = n;
   S.cap_pairs = pairs;
   return PYN_OK;
@@ -298,14 +269,14 @@ int ibm_build(pyn_ctx* c, IbmState& S) {
   PYN_HIP(hipGetLastError());
   // stable sort by node: markers keep their index order inside a node's run
   size_t tb = 0, tb2 = 0;
-  PYN_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, S.key0, S.key1, S.val0, S.val1, total, 0, 32, s));
+  PYN_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, S.key0.get(), S.key1.get(), S.val0.get(), S.val1.get(), total, 0, 32, s));
   hipcub::CountingInputIterator<int32_t> ids(0);
-  PYN_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb2, ids, S.flag, S.segptr, S.d_cnt, total, s));
-  PYN_TRY(ibm_tmp(S, std::max(tb, tb2)));
-  PYN_HIP(hipcub::DeviceRadixSort::SortPairs(S.tmp, tb, S.key0, S.key1, S.val0, S.val1, total, 0, 32, s));
+  PYN_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb2, ids, S.flag.get(), S.segptr.get(), S.d_cnt.get(), total, s));
+  PYN_HIP(S.tmp.grow(std::max(tb, tb2)));
+  PYN_HIP(hipcub::DeviceRadixSort::SortPairs(S.tmp.get(), tb, S.key0.get(), S.key1.get(), S.val0.get(), S.val1.get(), total, 0, 32, s));
   ibm_sorted_kernel<KERN><<<(unsigned)((pairs + 255) / 256), 256, 0, s>>>(G, S.ns, S.X, S.cw, S.base, S.key1, S.val1, S.smk, S.sw, S.flag);
   PYN_HIP(hipGetLastError());
-  PYN_HIP(hipcub::DeviceSelect::Flagged(S.tmp, tb2, ids, S.flag, S.segptr, S.d_cnt, total, s));
+  PYN_HIP(hipcub::DeviceSelect::Flagged(S.tmp.get(), tb2, ids, S.flag.get(), S.segptr.get(), S.d_cnt.get(), total, s));
   int64_t naff = 0;
   PYN_HIP(hipMemcpyAsync(&naff, S.d_cnt, sizeof(naff), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipStreamSynchronize(s));
@@ -395,10 +366,10 @@ extern "C" int pyn_ibm_set(pyn_ctx* c, int kernel, int dim, int64_t n, const dou
     }
   }
   PYN_HIP(hipSetDevice(c->device));
-  if (!c->ibm) c->ibm = new IbmState();
+  if (!c->ibm) c->ibm.reset(new IbmState());
   IbmState& S = *c->ibm;
   hipStream_t s = c->stream;
-  if (!S.d_cnt) PYN_HIP(hipMalloc((void**)&S.d_cnt, sizeof(int64_t)));
+  if (!S.d_cnt) PYN_HIP(S.d_cnt.alloc(1));
   bool same = S.lattice_ok && S.dim == dim;
   for (int d = 0; d < dim && same; ++d) same = S.N[d] == N[d] && S.lower[d] == lower[d] && S.h[d] == h[d];
   S.dim = dim;
@@ -411,7 +382,7 @@ extern "C" int pyn_ibm_set(pyn_ctx* c, int kernel, int dim, int64_t n, const dou
     S.lattice_ok = false;
     IbmGrid G = grid_of(S);
     int bad = 0;
-    int* d_bad = (int*)S.d_cnt;
+    int* d_bad = reinterpret_cast<int*>(S.d_cnt.get());
     PYN_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), s));
     ibm_lattice_check_kernel<<<(unsigned)((c->n_node + 255) / 256), 256, 0, s>>>(G, c->d_xyz, c->n_node, d_bad);
     PYN_HIP(hipGetLastError());
@@ -502,6 +473,6 @@ extern "C" int pyn_ibm_clear(pyn_ctx* c) {
   PYN_TRY(ibm_ready(c, "pyn_ibm_clear", -1));
   PYN_HIP(hipSetDevice(c->device));
   PYN_HIP(hipStreamSynchronize(c->stream));
-  pyn_ibm_release(c);
+  c->ibm.reset();
   return PYN_OK;
 }

@@ -4,11 +4,14 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
 #include <map>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -48,32 +51,81 @@ void pyn_set_error(const char* fmt, ...);
     if (rc_ != PYN_OK) return rc_;                                                            \
   } while (0)
 
-// scratch device allocation released on every exit path of a set-up routine
-struct DevTmp {
-  void* p = nullptr;
-  DevTmp() = default;
-  DevTmp(const DevTmp&) = delete;
-  DevTmp& operator=(const DevTmp&) = delete;
-  ~DevTmp() {
-    if (p) (void)hipFree(p);
+// ---- device memory ownership ---------------------------------------------------------------------------------------------------
+// Every device (and pinned host) allocation of the library is held by one Buf: move-only, freed by its destructor, and the only
+// caller of the allocator.  Set-up routines build into local Bufs and move them into the object after the last step that can fail.
+// The two process-wide counters (pyn_alloc_live) make "every buffer has an owner" an equality a test can check.
+inline std::atomic<int64_t> pyn_live_buffers{0}, pyn_live_bytes{0};
+
+template <typename T, bool PINNED = false>
+class Buf {
+  T* p_ = nullptr;
+  size_t n_ = 0;
+
+ public:
+  Buf() = default;
+  Buf(Buf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+  Buf& operator=(Buf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = std::exchange(o.p_, nullptr);
+      n_ = std::exchange(o.n_, 0);
+    }
+    return *this;
   }
-  hipError_t alloc(size_t bytes) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    return bytes ? hipMalloc(&p, bytes) : hipSuccess;
+  ~Buf() { reset(); }
+  hipError_t alloc(size_t n) {   // frees what it holds, then n elements (uninitialised); n == 0: empty.  Empty on failure.
+    reset();
+    if (n == 0) return hipSuccess;
+    void* p = nullptr;
+    const hipError_t e = PINNED ? hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) : hipMalloc(&p, n * sizeof(T));
+    if (e != hipSuccess) return e;
+    p_ = static_cast<T*>(p);
+    n_ = n;
+    pyn_live_buffers += 1;
+    pyn_live_bytes += (int64_t)(n * sizeof(T));
+    return hipSuccess;
   }
+  hipError_t grow(size_t n) { return n <= n_ ? hipSuccess : alloc(n); }   // at least n elements; contents are not kept
+  void reset() {
+    if (!p_) return;
+    (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+    pyn_live_buffers -= 1;
+    pyn_live_bytes -= (int64_t)(n_ * sizeof(T));
+    p_ = nullptr;
+    n_ = 0;
+  }
+  size_t size() const { return n_; }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+};
+template <typename T>
+using DevBuf = Buf<T, false>;
+template <typename T>
+using PinBuf = Buf<T, true>;   // pinned host memory
+
+// scratch bytes of a set-up routine
+struct DevTmp : DevBuf<unsigned char> {
   template <typename T>
   T* as() const {
-    return static_cast<T*>(p);
+    return reinterpret_cast<T*>(get());
   }
 };
 
+// n elements of `src` (null: left uninitialised) in a fresh allocation of `dst`, stream ordered
+template <typename T>
+inline int dev_upload(DevBuf<T>& dst, const T* src, size_t n, hipStream_t s) {
+  PYN_HIP(dst.alloc(n));
+  if (n && src) PYN_HIP(hipMemcpyAsync(dst.get(), src, n * sizeof(T), hipMemcpyHostToDevice, s));
+  return PYN_OK;
+}
+
 struct QuadTab {
   int ngp = 0;
-  double* w = nullptr;       // [ngp]
-  double* H = nullptr;       // [ngp][nn]
-  double* Hrs = nullptr;     // [ngp][dim][nn]
-  double* HrsCoo = nullptr;  // [ngp][dim][nc]
+  DevBuf<double> w;          // [ngp]
+  DevBuf<double> H;          // [ngp][nn]
+  DevBuf<double> Hrs;        // [ngp][dim][nn]
+  DevBuf<double> HrsCoo;     // [ngp][dim][nc]
   // host facts about the tables (set by pyn_elem_tables_set)
   double wsum = 0.0;         // sum of the weights
   bool const_grad = false;   // Hrs and HrsCoo identical at every point and to each other (affine simplex)
@@ -91,23 +143,29 @@ struct ProductPlan {
   int max_grid = INT32_MAX;   // PYNAMA_SPMV_MAX_GRID
 };
 
+// complete only in pyn_mg.hip / pyn_ibm.hip, where the deleters are defined
+struct MgHier;
+struct IbmState;
+struct MgHierDelete { void operator()(MgHier* h) const; };
+struct IbmStateDelete { void operator()(IbmState* s) const; };
+
 struct DMat {
   int br = 0, bc = 0;
-  double* val = nullptr;  // [nnzb*br*bc], layout in pynama_hip.h
-  double* sell_val = nullptr;  // SELL-64 image of `val` (the PK_SELL* kinds); it outlives a plan: a one-off block-CSR product keeps it
+  DevBuf<double> val;     // [nnzb*br*bc], layout in pynama_hip.h
+  DevBuf<double> sell_val;     // SELL-64 image of `val` (the PK_SELL* kinds); it outlives a plan: a one-off block-CSR product keeps it
   bool sell_valid = false;     // the image holds the current values
   ProductPlan plan;            // how the current values are multiplied (pyn_sell_ensure); PK_NONE: not resolved yet
-  double* dinv = nullptr;      // 1 / diagonal per scalar row (Jacobi), written by the lattice assemblies in their store
+  DevBuf<double> dinv;         // 1 / diagonal per scalar row (Jacobi), written by the lattice assemblies in their store
   bool dinv_valid = false;     // phase, else extracted once per matrix version (pyn_dinv_ensure)
-  double* lu = nullptr;        // dense LU factors of small systems (pyn_direct.hip), [n][n] row-major, multipliers in place
-  int* lu_piv = nullptr;       // [n] row interchanges + [1] singular-column flag + [n] the same as a gather
+  DevBuf<double> lu;           // dense LU factors of small systems (pyn_direct.hip), [n][n] row-major, multipliers in place
+  DevBuf<int> lu_piv;          // [n] row interchanges + [1] singular-column flag + [n] the same as a gather
   int64_t lu_n = 0;            // order the two buffers were sized for
   bool lu_valid = false;
-  double* band = nullptr;      // banded LU factors (pyn_direct_band.hip): [n][2 kl + ku + 64] row-major, layout there
-  int* band_perm = nullptr;    // per panel of 64 columns: the window's row interchanges as a gather [64 + kl], + [1] singular-column flag
+  DevBuf<double> band;         // banded LU factors (pyn_direct_band.hip): [n][2 kl + ku + 64] row-major, layout there
+  DevBuf<int> band_perm;       // per panel of 64 columns: the window's row interchanges as a gather [64 + kl], + [1] singular-column flag
   int64_t band_n = 0, band_kl = 0, band_ku = 0;   // shape the two buffers were sized for
   bool band_valid = false;
-  struct MgHier* mg = nullptr; // geometric multigrid hierarchy (pyn_mg.hip): coarse stencils, diagonals, eigenvalue estimates, coarsest LU
+  std::unique_ptr<MgHier, MgHierDelete> mg;   // geometric multigrid hierarchy (pyn_mg.hip): coarse stencils, diagonals, eigenvalue estimates, coarsest LU
   bool mg_valid = false;
   // "imposed-column" matrices (Krhs / Arhs of an assembly) are zero except in rows next to imposed nodes.  rhs_clean records for
   // which Dirichlet set (pyn_ctx::bc_stamp) the stored values are known to be exactly that matrix -- or all zero (PYN_RHS_ANY: a fresh
@@ -119,39 +177,34 @@ struct DMat {
   bool rhs_compact = false;
   int64_t c_stamp = -1;        // pyn_ctx::bc_stamp of the selection (-1: none yet)
   int64_t c_nr = 0, c_nnzb = 0;
-  int32_t* c_crow = nullptr;   // [n_owned] first block of the node's row in `val`, -1: row not stored
-  int32_t* c_rsel = nullptr;   // [c_nr] stored node rows, ascending
-  int32_t* c_cptr = nullptr;   // [c_nr + 1] first block of every stored row
+  DevBuf<int32_t> c_crow;      // [n_owned] first block of the node's row in `val`, -1: row not stored
+  DevBuf<int32_t> c_rsel;      // [c_nr] stored node rows, ascending
+  DevBuf<int32_t> c_cptr;      // [c_nr + 1] first block of every stored row
   bool live = false;
   void touch() {               // the values are about to change
     sell_valid = dinv_valid = lu_valid = band_valid = mg_valid = false;
     plan = ProductPlan();
     rhs_clean = -2;
   }
-  void release_lu() {
-    (void)hipFree(lu);
-    (void)hipFree(lu_piv);
-    lu = nullptr;
-    lu_piv = nullptr;
+  void release_band() {
+    band.reset();
+    band_perm.reset();
+    band_n = band_kl = band_ku = 0;
+    band_valid = false;
+  }
+  void release_lu() {          // both direct factorisations
+    lu.reset();
+    lu_piv.reset();
     lu_n = 0;
     lu_valid = false;
     release_band();
   }
-  void release_band() {
-    (void)hipFree(band);
-    (void)hipFree(band_perm);
-    band = nullptr;
-    band_perm = nullptr;
-    band_n = band_kl = band_ku = 0;
-    band_valid = false;
-  }
-  void release_mg();           // pyn_mg.hip
 };
 
 struct PatchPlan {
   bool user = false;  // set through the C ABI (not the automatic consecutive-row plan)
-  int32_t *rowptr = nullptr, *rows = nullptr, *eptr = nullptr, *elem = nullptr;
-  void *rowslot4 = nullptr, *kmap4 = nullptr;
+  DevBuf<int32_t> rowptr, rows, eptr, elem;
+  DevBuf<uint4> rowslot4, kmap4;
   int npatch = 0, maxrows = 0, maxlen = 0;
   int64_t npe = 0;
 };
@@ -168,7 +221,7 @@ struct BoxLattice {
   int EX = 0, EY = 0, EL = 0;   // local cells along x, y (1 in 2-D), the slow axis
   int NX = 0, NY = 0;           // nodes per x-line; x-lines per plane (1 in 2-D)
   int npl = 0, p_own0 = 0, n_own = 0;
-  int32_t* d_P = nullptr;       // [npl]
+  DevBuf<int32_t> d_P;          // [npl]
   std::vector<int32_t> P;
   int64_t plane() const { return (int64_t)NX * NY; }
   // nodes along y and z as pyn_mesh_topology reports them (2-D: the planes are the y axis, nz = 1)
@@ -187,7 +240,7 @@ struct Lattice {
   bool valid = false;
   bool std_shape = false;      // ids follow the slab numbering: owned planes, ghost planes below, ghost planes above (one rank, or a rank's slab)
   int std_ok = -1;             // closed-form row offsets verified against the graph (-1: not checked yet)
-  int32_t* d_zord = nullptr;   // [npl]: count | (dz+1) codes of the z-neighbour planes sorted by node id
+  DevBuf<int32_t> d_zord;      // [npl]: count | (dz+1) codes of the z-neighbour planes sorted by node id
 };
 
 // View of orders ngl 2 and 3 (pyn_assemble_ho3.hip: row-run assembly; ngl 3, the order all of the reference's cases run,
@@ -196,10 +249,10 @@ struct Ho3View {
   bool valid = false;
   int affine = -1;              // every element a parallelogram / parallelepiped? (-1: not checked yet)
   int diag = 0;                 // ... and axis-aligned (J diagonal): set with `affine`
-  double* d_geom = nullptr;     // [n_elem][6 | 10]: J^-1 (row = physical axis) and det J, rewritten by every assembly
-  uint8_t* d_nbits = nullptr;   // per local node: bit p = DOF p imposed (packed copy of d_bcmask)
+  DevBuf<double> d_geom;        // [n_elem][6 | 10]: J^-1 (row = physical axis) and det J, rewritten by every assembly
+  DevBuf<uint8_t> d_nbits;      // per local node: bit p = DOF p imposed (packed copy of d_bcmask)
   int64_t nbits_stamp = -1;     // pyn_ctx::bc_stamp the packed copy belongs to
-  uint8_t* d_runflag = nullptr; // per owned node that starts a run: does the run's node box hold an imposed DOF?
+  DevBuf<uint8_t> d_runflag;    // per owned node that starts a run: does the run's node box hold an imposed DOF?
   int64_t runflag_stamp = -1;   // ... for this Dirichlet set
   int runflag_R = 0;            // ... and this run length
 };
@@ -221,24 +274,31 @@ constexpr int PYN_HO_MAX_NGL_2D = 12, PYN_HO_MAX_NGL_3D = 8;   // orders the mat
 struct SellShape {
   int br = 0, bc = 0, maxw = 0;
   int64_t ns = 0, total = 0;
-  int64_t* ptr = nullptr;   // [ns+1] slice offsets
-  int* w = nullptr;         // [ns] slice widths (entries per scalar row)
-  int32_t* col = nullptr;   // explicit expanded columns (only when the dictionary does not apply)
+  DevBuf<int64_t> ptr;      // [ns+1] slice offsets
+  DevBuf<int> w;            // [ns] slice widths (entries per scalar row)
+  DevBuf<int32_t> col;      // explicit expanded columns (only when the dictionary does not apply)
   int64_t int_begin = -1, int_end = -1;  // slices without ghost columns, when they are one contiguous range
 };
 
 struct DVec {
   int bs = 0;
-  double* d = nullptr;  // [(n_owned+n_ghost)*bs]
+  DevBuf<double> d;     // [(n_owned+n_ghost)*bs]
   bool live = false;
 };
 
 // a set of owned local nodes on the device (pyn_fields.hip): strictly increasing, range-checked when it was created
 struct DNodeSet {
-  int32_t* d = nullptr;  // [n]; null when n == 0
+  DevBuf<int32_t> d;     // [n]; null when n == 0
   int64_t n = 0;
   bool live = false;
 };
+
+static_assert(!std::is_copy_constructible<DMat>::value && !std::is_copy_constructible<DVec>::value &&
+                  !std::is_copy_constructible<SellShape>::value && !std::is_copy_constructible<DevBuf<double>>::value,
+              "a struct that owns device memory must not be copyable");
+static_assert(std::is_nothrow_move_constructible<DMat>::value && std::is_nothrow_move_constructible<DVec>::value &&
+                  std::is_nothrow_move_constructible<SellShape>::value && std::is_nothrow_move_constructible<DevBuf<double>>::value,
+              "std::vector must move, not copy, the owners it holds");
 
 constexpr int64_t PYN_RHS_UNKNOWN = -2, PYN_RHS_ANY = -1;   // DMat::rhs_clean
 constexpr int PYN_MAX_PARTIALS = 2048;  // grid cap of every reducing kernel
@@ -259,6 +319,8 @@ __device__ inline void block_partial(double acc, double* __restrict__ part) {
 }
 
 struct pyn_ctx {
+  pyn_ctx() = default;
+  ~pyn_ctx();   // pyn_ctx.hip: drains the streams and destroys what is not memory; the members then free themselves
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t comm_stream = nullptr;            // halo exchange overlapped with the interior SpMV rows
@@ -277,38 +339,38 @@ struct pyn_ctx {
   int64_t n_owned = 0, n_ghost = 0;
   std::vector<int> neigh;
   std::vector<int64_t> send_ptr, recv_ptr;
-  int32_t* d_send_idx = nullptr;
-  double* d_send_buf = nullptr;  // [n_send * max_bs]
+  DevBuf<int32_t> d_send_idx;
+  DevBuf<double> d_send_buf;     // [n_send * max_bs]
   int64_t n_send = 0;
   bool halo_set = false;
 
   // mesh
   int dim = 0, nn = 0, nc = 0, ngl = 0;
   int64_t n_elem = 0, n_node = 0;
-  int32_t* d_conn = nullptr;
-  double* d_xyz = nullptr;
+  DevBuf<int32_t> d_conn;
+  DevBuf<double> d_xyz;
   QuadTab quad[3];
   int mesh_affine = -1;          // every element a parallelepiped? (-1: not checked yet; reset by pyn_mesh_set)
   bool aff_rw_standard = false;  // ... and so is int N_a d N_b (affine Rw path)
   bool aff_standard = false;  // the uploaded tables are those of the trilinear hexahedron in closed form
   bool q1_red_standard = false;    // reduced rule = the centroid, weight 8, trilinear tables (lean KLE kernel)
   bool q1_gauss_standard = false;  // ... pointwise: 2x2x2 Gauss rule, unit weights (lean general-geometry kernels)
-  double* d_aff = nullptr;  // Q1-hex affine tables: [6][36] reference matrices + [4][8] non-affine monomial signs + [3][3] S
+  DevBuf<double> d_aff;     // Q1-hex affine tables: [6][36] reference matrices + [4][8] non-affine monomial signs + [3][3] S
 
   // boundary condition
   int bc_ndof = 0;
   // matrix-free operators (pyn_matfree_set), slot = PYN_MATFREE_*: the Dirichlet mask is SNAPSHOT at set time, so later
   // pyn_bc_set calls (operator assembly, other matrices) do not change the operator
   bool mf_set[PYN_MATFREE_SLOTS] = {};
-  uint8_t* mf_mask[PYN_MATFREE_SLOTS] = {};   // null = no imposed DOF
+  DevBuf<uint8_t> mf_mask[PYN_MATFREE_SLOTS];   // null = no imposed DOF
   double mf_alpha_d[PYN_MATFREE_SLOTS] = {}, mf_alpha_w[PYN_MATFREE_SLOTS] = {};   // penalty weights of each KLE operator's snapshot
   Ho3MfBasis mf_ho3;     // the KLE operator on a second-order lattice (pyn_matfree_ho3.hip): its 1-D point bases, set with mf_set[KLE]
   int64_t bc_stamp = 0;  // bumped by every pyn_bc_set
-  uint8_t* d_bcmask = nullptr;
+  DevBuf<uint8_t> d_bcmask;
 
   // node graph
-  int32_t* d_rowptr = nullptr;
-  int32_t* d_colidx = nullptr;
+  DevBuf<int32_t> d_rowptr;
+  DevBuf<int32_t> d_colidx;
   int64_t nnzb = 0;
 
   // patch plans of the tiled assemblies (pyn_assemble_tiled.hip): [0] scalar forms, [1] KLE (3x3 blocks)
@@ -318,17 +380,17 @@ struct pyn_ctx {
   Lattice lat;      // 3-D first-order cells (pyn_assemble_lattice.hip)
   Ho3View ho3;      // ngl 2 and 3 (pyn_assemble_ho3.hip)
   bool ho_valid = false;        // 4 <= ngl <= pyn_ho_matfree_max_ngl(dim) (pyn_matfree_ho.hip); pyn_mesh_topology says kind 0 for these
-  double* d_ho_tab = nullptr;   // its matrix-free KLE operator: the 1-D tables of the order (set by pyn_matfree_set) ...
-  double* d_ho_ye = nullptr;    // ... and the per-cell results between the two passes [n_elem][dim][nn]
+  DevBuf<double> d_ho_tab;      // its matrix-free KLE operator: the 1-D tables of the order (set by pyn_matfree_set) ...
+  DevBuf<double> d_ho_ye;       // ... and the per-cell results between the two passes [n_elem][dim][nn]
   // PYN_MATFREE_KLE_GENERAL (pyn_matfree_ho_general.hip), any quadrilateral / hexahedral mesh of these orders; shares d_ho_tab / d_ho_ye
-  int32_t* d_hog_aoft = nullptr;      // [nn] local node at tensor position t (the inverse of mesh_local_lattice)
-  int32_t* d_hog_inc_ptr = nullptr;   // [n_node + 1] node -> (cell, t) incidence list in CSR form ...
-  int32_t* d_hog_inc = nullptr;       // ... [n_elem * nn] entries cell * nn + t, ascending within a row
+  DevBuf<int32_t> d_hog_aoft;         // [nn] local node at tensor position t (the inverse of mesh_local_lattice)
+  DevBuf<int32_t> d_hog_inc_ptr;      // [n_node + 1] node -> (cell, t) incidence list in CSR form ...
+  DevBuf<int32_t> d_hog_inc;          // ... [n_elem * nn] entries cell * nn + t, ascending within a row
   // reference matrices of the ngl = 3 element in tensor (lattice) order, from the uploaded tables (pyn_elem_tables_set):
   // Tf / Tr[r][s][a][b] = sum_g w Hrs_r[a] Hrs_s[b] (full / reduced rule), Uf / Ur[r][a][b] = sum_g w H[a] Hrs_r[b]
-  double* d_ho3_tabs = nullptr;
+  DevBuf<double> d_ho3_tabs;
   std::vector<double> ho3_t1d_host;    // 1-D factors M, D, S of the three rules; the records are their tensor products when ho3_tens_ok
-  double* d_ho3_t1d = nullptr;
+  DevBuf<double> d_ho3_t1d;
   bool ho3_tens_ok = false;
   std::vector<double> ho3_tabs_host;   // host image of the records (the three rules arrive in separate pyn_elem_tables_set calls)
   bool ho3_tabs_ok[3] = {false, false, false};   // full, reduced, nodal rule
@@ -336,8 +398,8 @@ struct pyn_ctx {
 
   // SELL-64 structures, one per block shape, + the node-level column-pattern dictionary (pyn_sell.hip)
   std::vector<SellShape> sell_shapes;
-  int32_t* sell_pid = nullptr;   // per-node column-pattern id (dictionary mode), else null
-  int32_t* sell_tab = nullptr;   // [npat][32] relative node offsets
+  DevBuf<int32_t> sell_pid;      // per-node column-pattern id (dictionary mode), else null
+  DevBuf<int32_t> sell_tab;      // [npat][32] relative node offsets
   int sell_npat = 0;
   bool sell_dict_built = false;
   int64_t prod_last[8] = {0};    // pyn_product_last: the most recent product launch (pyn_product_record)
@@ -347,29 +409,26 @@ struct pyn_ctx {
   std::vector<DNodeSet> nodesets;   // ids are never reused: a released set stays dead (pyn_fields.hip)
 
   // reduction / solver scratch
-  double* d_part = nullptr;    // [8][PYN_MAX_PARTIALS]
-  double* d_scal = nullptr;    // [64] device scalars
-  int* d_flag = nullptr;       // [8]  device flags (done, iters, reason ...)
-  double* h_scal = nullptr;    // pinned host mirror [64]
-  int* h_flag = nullptr;       // pinned host mirror [8]
+  DevBuf<double> d_part;       // [8][PYN_MAX_PARTIALS]
+  DevBuf<double> d_scal;       // [64] device scalars
+  DevBuf<int> d_flag;          // [8]  device flags (done, iters, reason ...)
+  PinBuf<double> h_scal;       // pinned host mirror [64]
+  PinBuf<int> h_flag;          // pinned host mirror [8]
   // CG work vectors (length n_local*bs_max), reallocated on demand
-  double* d_work = nullptr;
-  size_t work_bytes = 0;
+  DevBuf<double> d_work;
   std::vector<hipEvent_t> prof_ev;  // event pool for per-kernel timing
   int64_t asm_last[8] = {0};     // pyn_assemble_last: what the most recent numeric assembly launched (pyn_assemble.hip)
   // per-context kernel attributes (pyn_kernel_lds / pyn_kernel_occupancy): a second context on another device sets its own
   std::map<const void*, size_t> kern_lds;                      // dynamic-LDS limit this context has raised the kernel to
   std::map<std::pair<const void*, size_t>, int> kern_occ;      // workgroups per CU of (kernel, dynamic LDS)
   // elements with an imposed node (the only ones that feed an imposed-column matrix), per Dirichlet set
-  int32_t* d_esel = nullptr;
+  DevBuf<int32_t> d_esel;
   int64_t n_esel = 0, esel_stamp = -1;
   // general-geometry KLE: off-diagonal element Laplacians [28][ne] between the pre-pass and the tile kernel (grown on demand)
-  double* d_kle_lel = nullptr;
-  size_t kle_lel_bytes = 0;
+  DevBuf<double> d_kle_lel;
   // element-local scratch for pyn_elem_local
-  double* d_eloc = nullptr;
-  size_t eloc_bytes = 0;
-  struct IbmState* ibm = nullptr;   // immersed-boundary marker set (pyn_ibm.hip): stencils, node-major spreading lists, A = H S and its LU
+  DevBuf<double> d_eloc;
+  std::unique_ptr<IbmState, IbmStateDelete> ibm;   // immersed-boundary marker set (pyn_ibm.hip): stencils, node-major spreading lists, A = H S and its LU
 };
 
 inline int64_t n_local(const pyn_ctx* c) { return c->n_owned + c->n_ghost; }
@@ -394,15 +453,6 @@ inline int pyn_lattice_kind(const pyn_ctx* c) {
 
 // ---- cross-TU helpers ---------------------------------------------------------------------
 int pyn_ensure_work(pyn_ctx* c, size_t bytes);
-inline int pyn_grow(double** p, size_t* have, size_t need) {   // a scratch buffer of at least `need` bytes (contents not kept)
-  if (need <= *have) return PYN_OK;
-  if (*p) PYN_HIP(hipFree(*p));
-  *p = nullptr;
-  *have = 0;
-  PYN_HIP(hipMalloc((void**)p, need));
-  *have = need;
-  return PYN_OK;
-}
 int pyn_halo_exchange(pyn_ctx* c, double* x, int bs);  // fills ghost part of x (stream ordered)
 int pyn_halo_exchange_on(pyn_ctx* c, double* x, int bs, hipStream_t st);
 int pyn_check_mat(pyn_ctx* c, int id, const char* what);
@@ -427,7 +477,6 @@ void pyn_sell_drop_structure(pyn_ctx* c);
 const SellShape* pyn_sell_shape(pyn_ctx* c, const DMat& A);
 // compact imposed-column matrices (pyn_rhs.hip)
 int pyn_rhs_ensure(pyn_ctx* c, DMat& M, bool relayout = false);   // row selection + storage (values zeroed when laid out); relayout: for the CURRENT Dirichlet set
-void pyn_rhs_release(DMat& M);
 int pyn_rhs_expand(pyn_ctx* c, const DMat& M, double* full);   // full-pattern copy of the values (zeros in the rows not stored)
 int pyn_bc_elements(pyn_ctx* c);                        // c->d_esel / n_esel for the current Dirichlet set
 int64_t pyn_mat_blocks(const pyn_ctx* c, const DMat& M);        // blocks stored by the matrix (graph entries, or the compact count)
@@ -435,7 +484,6 @@ int64_t pyn_mat_blocks(const pyn_ctx* c, const DMat& M);        // blocks stored
 using ConnAt = std::function<int32_t(int64_t)>;
 // pyn_box_lattice.hip: c->box from the connectivity; the local node offsets of the box mesh (reference position / flipped in 2-D)
 int pyn_box_detect(pyn_ctx* c, const ConnAt& at);
-void pyn_box_release(pyn_ctx* c);
 void ref_local_lattice(int n, int dim, std::vector<int>& out);
 void mesh_local_lattice(int ngl, int dim, std::vector<int>& loc);
 // the three views of c->box, each next to its kernels (once per pyn_mesh_set, after pyn_box_detect)
@@ -450,15 +498,11 @@ bool pyn_q1_mixed_tables_standard(const double* w, const double* H, const double
 bool pyn_q1_gauss_tables_standard(const double* w, const double* H, const double* Hrs, const double* HrsCoo);   // pyn_assemble_march.hip
 // second-order (ngl = 3) lattices (pyn_assemble_ho3.hip)
 void pyn_ho3_view(pyn_ctx* c);
-void pyn_ho3_release(pyn_ctx* c);
 int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double* H, const double* Hrs);
 int pyn_ho3_symbolic(pyn_ctx* c, bool* done);
 int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]);   // every cell affine / axis-aligned; corner derivatives
 // box lattices of order ngl >= 4 (pyn_matfree_ho.hip)
 void pyn_ho_view(pyn_ctx* c);
-void pyn_ho_release(pyn_ctx* c);
-void pyn_ibm_release(pyn_ctx* c);   // pyn_ibm.hip: the marker set belongs to the mesh
-void pyn_nodesets_release(pyn_ctx* c);   // pyn_fields.hip: ... and so do the node sets
 // dense LU shared by the direct solve, the coarsest multigrid level and the immersed-boundary force solve (pyn_direct.hip): piv holds 2 n + 1 ints
 int pyn_dense_lu_factor(pyn_ctx* c, double* D, int* piv, int64_t n);
 int pyn_dense_lu_solve(pyn_ctx* c, const double* D, const int* piv, int64_t n, const double* b, double* x, double* z);

@@ -583,7 +583,7 @@ int pyn_extract_diag_inv(pyn_ctx* c, const DMat& A, double* d, bool invert) {
 
 int pyn_dinv_ensure(pyn_ctx* c, DMat& A) {
   PYN_CHECK(A.br == A.bc, "diagonal of a non-square block matrix");
-  if (!A.dinv) PYN_HIP(hipMalloc((void**)&A.dinv, (size_t)c->n_owned * A.br * sizeof(double)));
+  if (!A.dinv) PYN_HIP(A.dinv.alloc((size_t)c->n_owned * A.br));
   if (!A.dinv_valid) {
     PYN_TRY(pyn_extract_diag_inv(c, A, A.dinv, true));
     A.dinv_valid = true;
@@ -696,14 +696,15 @@ extern "C" int pyn_matfree_set(pyn_ctx* c, int op, double alpha_d, double alpha_
   const int bs = mf->bs(c, op);
   PYN_CHECK(!c->d_bcmask || c->bc_ndof == bs, "matrix-free operator %d: the current Dirichlet mask must have %d DOF(s) per node", op, bs);
   PYN_HIP(hipSetDevice(c->device));
-  (void)hipFree(c->mf_mask[op]);
-  c->mf_mask[op] = nullptr;
+  c->mf_mask[op].reset();
   c->mf_set[op] = false;
   if (c->d_bcmask) {
     const size_t nb = (size_t)c->n_node * bs;
-    PYN_HIP(hipMalloc((void**)&c->mf_mask[op], nb));
-    PYN_HIP(hipMemcpyAsync(c->mf_mask[op], c->d_bcmask, nb, hipMemcpyDeviceToDevice, c->stream));
+    DevBuf<uint8_t> snap;
+    PYN_HIP(snap.alloc(nb));
+    PYN_HIP(hipMemcpyAsync(snap, c->d_bcmask, nb, hipMemcpyDeviceToDevice, c->stream));
     PYN_HIP(hipStreamSynchronize(c->stream));
+    c->mf_mask[op] = std::move(snap);
   }
   c->mf_alpha_d[op] = alpha_d;
   c->mf_alpha_w[op] = alpha_w;

@@ -554,18 +554,12 @@ extern "C" int pyn_mesh_ho_lattice(pyn_ctx* c, int* ngl, int* nx, int* ny, int* 
   return PYN_OK;
 }
 
-void pyn_ho_release(pyn_ctx* c) {
-  (void)hipFree(c->d_ho_tab);
-  (void)hipFree(c->d_ho_ye);
-  c->d_ho_tab = c->d_ho_ye = nullptr;
-  c->ho_valid = false;
-  pyn_hog_release(c);
-}
-
 // The ngl >= 4 view of c->box: the orders the kernels are instantiated for.  pyn_mesh_topology keeps reporting kind 0 for these meshes:
 // only the matrix-free operator uses the view.
 void pyn_ho_view(pyn_ctx* c) {
-  pyn_ho_release(c);
+  c->d_ho_tab.reset();   // the operator's tables and scratch belong to the mesh
+  c->d_ho_ye.reset();
+  pyn_hog_release(c);
   const BoxLattice& B = c->box;
   c->ho_valid = B.valid && B.ngl >= 4 && B.ngl <= pyn_ho_matfree_max_ngl(B.dim) && B.plane() <= INT32_MAX / 4 && B.n_own >= 1 &&
                 c->n_elem < INT32_MAX && !getenv("PYNAMA_NO_HO_LATTICE");
@@ -603,11 +597,11 @@ int pyn_ho_check_rules(pyn_ctx* c, const HoTab1D& T, const char* what) {
 
 int pyn_ho_tab_upload(pyn_ctx* c, const HoTab1D& T) {
   const std::vector<double> packed = T.packed();
-  (void)hipFree(c->d_ho_tab);
-  c->d_ho_tab = nullptr;
-  PYN_HIP(hipMalloc((void**)&c->d_ho_tab, packed.size() * sizeof(double)));
-  PYN_HIP(hipMemcpy(c->d_ho_tab, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (!c->d_ho_ye) PYN_HIP(hipMalloc((void**)&c->d_ho_ye, (size_t)c->n_elem * c->nn * c->dim * sizeof(double)));
+  DevBuf<double> tab;
+  PYN_HIP(tab.alloc(packed.size()));
+  PYN_HIP(hipMemcpy(tab, packed.data(), packed.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (!c->d_ho_ye) PYN_HIP(c->d_ho_ye.alloc((size_t)c->n_elem * c->nn * c->dim));
+  c->d_ho_tab = std::move(tab);   // the one commit: a failure above leaves the tables of the last set
   return PYN_OK;
 }
 
@@ -631,14 +625,14 @@ static int ho_matfree_set(pyn_ctx* c, int op) {
     DevTmp flag;
     int h = 0;
     PYN_HIP(flag.alloc(sizeof(int)));
-    PYN_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), c->stream));
+    PYN_HIP(hipMemsetAsync(flag.get(), 0, sizeof(int), c->stream));
     const int ge = (A.n_cells + 255) / 256;
     if (dim == 3)
       ho_affine_kernel<3><<<ge, 256, 0, c->stream>>>(A, ngl - 1, flag.as<int>());
     else
       ho_affine_kernel<2><<<ge, 256, 0, c->stream>>>(A, ngl - 1, flag.as<int>());
     PYN_HIP(hipGetLastError());
-    PYN_HIP(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     PYN_HIP(hipStreamSynchronize(c->stream));
     PYN_CHECK(!h, "matrix-free KLE operator (ngl %d): needs affine cells (parallelograms / parallelepipeds); this mesh has a cell "
                   "that is not affine", ngl);

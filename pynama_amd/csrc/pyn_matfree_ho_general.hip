@@ -550,10 +550,9 @@ int hog_check_geometry_tables(pyn_ctx* c, const HoTab1D& T) {
 }  // namespace
 
 void pyn_hog_release(pyn_ctx* c) {
-  (void)hipFree(c->d_hog_aoft);
-  (void)hipFree(c->d_hog_inc_ptr);
-  (void)hipFree(c->d_hog_inc);
-  c->d_hog_aoft = c->d_hog_inc_ptr = c->d_hog_inc = nullptr;
+  c->d_hog_aoft.reset();
+  c->d_hog_inc_ptr.reset();
+  c->d_hog_inc.reset();
 }
 
 // pyn_matfree_set(PYN_MATFREE_KLE_GENERAL): the refusals, the tables, a_of_t, the sign of det J everywhere, the incidence list
@@ -586,21 +585,23 @@ int pyn_hog_set(pyn_ctx* c) {
     aoft[t] = a;
     t_of_a[a] = t;
   }
-  PYN_HIP(hipMalloc((void**)&c->d_hog_aoft, (size_t)nn * sizeof(int32_t)));
-  PYN_HIP(hipMemcpy(c->d_hog_aoft, aoft.data(), (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice));
+  DevBuf<int32_t> d_aoft, d_inc_ptr, d_inc;   // committed together at the end: a refused set leaves no lists behind
+  PYN_HIP(d_aoft.alloc((size_t)nn));
+  PYN_HIP(hipMemcpy(d_aoft, aoft.data(), (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice));
   {   // det J > 0 everywhere, before anything else touches the cells
-    const HogArgs A = hog_args(c);
+    HogArgs A = hog_args(c);
+    A.aoft = d_aoft;
     DevTmp flag;
     int h = 0;
     PYN_HIP(flag.alloc(sizeof(int)));
-    PYN_HIP(hipMemsetAsync(flag.p, 0, sizeof(int), c->stream));
+    PYN_HIP(hipMemsetAsync(flag.get(), 0, sizeof(int), c->stream));
     const int ge = (A.n_cells + 63) / 64, tab_pts = (int)(T.packed().size() - T.xl.size() - T.xr.size());
     if (dim == 3)
       hog_det_kernel<3><<<ge, 64, 0, c->stream>>>(A, ngl, tab_pts, flag.as<int>());
     else
       hog_det_kernel<2><<<ge, 64, 0, c->stream>>>(A, ngl, tab_pts, flag.as<int>());
     PYN_HIP(hipGetLastError());
-    PYN_HIP(hipMemcpyAsync(&h, flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     PYN_HIP(hipStreamSynchronize(c->stream));
     PYN_CHECK(!h, "%s (ngl %d): non-positive Jacobian: a cell has det J <= 0 at a Lobatto node or a Gauss point (inverted or "
                   "degenerate cell, or a connectivity that does not follow the reference's local node order)", WHAT, ngl);
@@ -619,10 +620,13 @@ int pyn_hog_set(pyn_ctx* c) {
     for (int64_t e = 0; e < c->n_elem; ++e)
       for (int t = 0; t < nn; ++t) inc[fill[conn[e * nn + aoft[t]]]++] = (int32_t)(e * nn + t);
   }
-  PYN_HIP(hipMalloc((void**)&c->d_hog_inc_ptr, ((size_t)n_node + 1) * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&c->d_hog_inc, std::max<size_t>(1, (size_t)n_ent) * sizeof(int32_t)));
-  PYN_HIP(hipMemcpy(c->d_hog_inc_ptr, ptr.data(), ((size_t)n_node + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  PYN_HIP(hipMemcpy(c->d_hog_inc, inc.data(), (size_t)n_ent * sizeof(int32_t), hipMemcpyHostToDevice));
+  PYN_HIP(d_inc_ptr.alloc((size_t)n_node + 1));
+  PYN_HIP(d_inc.alloc(std::max<size_t>(1, (size_t)n_ent)));
+  PYN_HIP(hipMemcpy(d_inc_ptr, ptr.data(), ((size_t)n_node + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  PYN_HIP(hipMemcpy(d_inc, inc.data(), (size_t)n_ent * sizeof(int32_t), hipMemcpyHostToDevice));
+  c->d_hog_aoft = std::move(d_aoft);
+  c->d_hog_inc_ptr = std::move(d_inc_ptr);
+  c->d_hog_inc = std::move(d_inc);
   return PYN_OK;
 }
 

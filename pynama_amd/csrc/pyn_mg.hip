@@ -596,15 +596,15 @@ double tridiag_max_eig(const std::vector<double>& a, const std::vector<double>& 
 struct MgLevel {
   int nx = 0, ny = 0, nz = 0;
   int64_t nn = 0;                // nodes
-  int32_t* P = nullptr;          // [planes]
-  int32_t* invP = nullptr;       // [planes]
-  double* S = nullptr;           // stencil (levels >= 1)
-  double* dinv = nullptr;        // levels >= 1 (level 0: the matrix's own DMat::dinv)
-  double* diag = nullptr;        // a_ii [nn b]
-  uint8_t* dec = nullptr;        // decoupled DOF [nn b]
-  double* b = nullptr;           // right-hand side of the level's cycle (levels >= 1)
-  double* z[2] = {nullptr, nullptr};   // ping-pong iterates (levels >= 1); z[0] also the product scratch of level 0
-  double* d = nullptr;           // Chebyshev direction
+  DevBuf<int32_t> P;             // [planes]
+  DevBuf<int32_t> invP;          // [planes]
+  DevBuf<double> S;              // stencil (levels >= 1)
+  DevBuf<double> dinv;           // levels >= 1 (level 0: the matrix's own DMat::dinv)
+  DevBuf<double> diag;           // a_ii [nn b]
+  DevBuf<uint8_t> dec;           // decoupled DOF [nn b]
+  DevBuf<double> b;              // right-hand side of the level's cycle (levels >= 1)
+  DevBuf<double> z[2];           // ping-pong iterates (levels >= 1); z[0] also the product scratch of level 0
+  DevBuf<double> d;              // Chebyshev direction
   double lam = 0.0;              // lambda_max(D^-1 A) estimate
 };
 
@@ -612,43 +612,30 @@ struct MgHier {
   pyn_mg_opts opts{};
   int dim = 0, b = 0, nlev = 0;
   MgLevel L[PYN_MG_MAX_LEVELS];
-  double* lu = nullptr;
-  int* piv = nullptr;
+  DevBuf<double> lu;
+  DevBuf<int> piv;
   int64_t lu_n = 0;
   double setup_ms = 0.0;
   int builds = 0;
   // level 0 of order ngl >= 4 (ho_m = ngl - 1 > 0): level 1 is the Q1 lattice of the same cells, the 0 <-> 1 transfers are the
   // mg_ho kernels; 0: every step halves (kinds 1, 2, 3)
   int ho_m = 0;
-  double* ho_hat = nullptr;                    // [2 ho_m + 1] 1-D weights
-  double* ho_tmp[2] = {nullptr, nullptr};      // stages of the axis-by-axis restriction
-  void free_levels() {
-    for (void* p : {(void*)ho_hat, (void*)ho_tmp[0], (void*)ho_tmp[1]}) (void)hipFree(p);
-    ho_hat = ho_tmp[0] = ho_tmp[1] = nullptr;
+  DevBuf<double> ho_hat;         // [2 ho_m + 1] 1-D weights
+  DevBuf<double> ho_tmp[2];      // stages of the axis-by-axis restriction
+  void free_levels() {           // a rebuild keeps the options and the counters
+    ho_hat.reset();
+    ho_tmp[0].reset();
+    ho_tmp[1].reset();
     ho_m = 0;
-    for (auto& l : L) {
-      for (void* p : {(void*)l.P, (void*)l.invP, (void*)l.S, (void*)l.dinv, (void*)l.diag, (void*)l.dec, (void*)l.b, (void*)l.z[0],
-                      (void*)l.z[1], (void*)l.d})
-        (void)hipFree(p);
-      l = MgLevel();
-    }
-    (void)hipFree(lu);
-    (void)hipFree(piv);
-    lu = nullptr;
-    piv = nullptr;
+    for (auto& l : L) l = MgLevel();
+    lu.reset();
+    piv.reset();
     lu_n = 0;
     nlev = 0;
   }
 };
 
-void DMat::release_mg() {
-  if (mg) {
-    mg->free_levels();
-    delete mg;
-  }
-  mg = nullptr;
-  mg_valid = false;
-}
+void MgHierDelete::operator()(MgHier* h) const { delete h; }
 
 static pyn_mg_opts mg_defaults(const pyn_mg_opts* in) {
   pyn_mg_opts o{};
@@ -768,7 +755,7 @@ static int mg_estimate(pyn_ctx* c, DMat& A, MgHier& H, int l, double* lam) {
     h[i] = (double)(v >> 11) * (2.0 / 9007199254740992.0) - 1.0;
   }
   PYN_HIP(hipMemcpyAsync(r, h.data(), n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  const double* dinv = l == 0 ? A.dinv : L.dinv;
+  const double* dinv = l == 0 ? A.dinv.get() : L.dinv.get();
   const Grid g = grid_of(H, l);
   mg_eig_update_kernel<<<grid_for(n), 256, 0, c->stream>>>(r, nullptr, dinv, z, 0.0, n);
   PYN_HIP(hipMemcpyAsync(p, z, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -875,7 +862,7 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
             dims[nlev - 1][0], dims[nlev - 1][1], dims[nlev - 1][2], (long long)rows(nlev - 1), pyn_direct_max_rows());
 
   const auto t0 = std::chrono::steady_clock::now();
-  if (!A.mg) A.mg = new MgHier();
+  if (!A.mg) A.mg.reset(new MgHier());
   MgHier& H = *A.mg;
   H.free_levels();
   A.mg_valid = false;
@@ -892,10 +879,10 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
       hat[ho_m + i] = 0.5 * (1.0 - xi[i]);
       hat[i] = 0.5 * (1.0 + xi[i]);
     }
-    PYN_HIP(hipMalloc((void**)&H.ho_hat, hat.size() * sizeof(double)));
+    PYN_HIP(H.ho_hat.alloc(hat.size()));
     PYN_HIP(hipMemcpy(H.ho_hat, hat.data(), hat.size() * sizeof(double), hipMemcpyHostToDevice));
-    PYN_HIP(hipMalloc((void**)&H.ho_tmp[0], (size_t)dims[1][0] * ny * nz * b * sizeof(double)));
-    if (dim == 3) PYN_HIP(hipMalloc((void**)&H.ho_tmp[1], (size_t)dims[1][0] * dims[1][1] * nz * b * sizeof(double)));
+    PYN_HIP(H.ho_tmp[0].alloc((size_t)dims[1][0] * ny * nz * b));
+    if (dim == 3) PYN_HIP(H.ho_tmp[1].alloc((size_t)dims[1][0] * dims[1][1] * nz * b));
   }
   for (int l = 0; l < nlev; ++l) {
     MgLevel& L = H.L[l];
@@ -911,27 +898,27 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
       li[j] = l == 0 ? invP[j] : j;
     }
     const int64_t n = L.nn * b;
-    PYN_HIP(hipMalloc((void**)&L.P, pl * sizeof(int32_t)));
-    PYN_HIP(hipMalloc((void**)&L.invP, pl * sizeof(int32_t)));
+    PYN_HIP(L.P.alloc(pl));
+    PYN_HIP(L.invP.alloc(pl));
     PYN_HIP(hipMemcpy(L.P, lp.data(), pl * sizeof(int32_t), hipMemcpyHostToDevice));
     PYN_HIP(hipMemcpy(L.invP, li.data(), pl * sizeof(int32_t), hipMemcpyHostToDevice));
-    PYN_HIP(hipMalloc((void**)&L.diag, n * sizeof(double)));
-    PYN_HIP(hipMalloc((void**)&L.dec, n));
-    PYN_HIP(hipMalloc((void**)&L.z[0], n * sizeof(double)));
-    PYN_HIP(hipMalloc((void**)&L.d, n * sizeof(double)));
+    PYN_HIP(L.diag.alloc(n));
+    PYN_HIP(L.dec.alloc(n));
+    PYN_HIP(L.z[0].alloc(n));
+    PYN_HIP(L.d.alloc(n));
     if (l > 0) {
       const int nst = dim == 3 ? 27 : 9;
-      PYN_HIP(hipMalloc((void**)&L.S, (size_t)L.nn * nst * b * b * sizeof(double)));
-      PYN_HIP(hipMalloc((void**)&L.dinv, n * sizeof(double)));
-      PYN_HIP(hipMalloc((void**)&L.b, n * sizeof(double)));
-      PYN_HIP(hipMalloc((void**)&L.z[1], n * sizeof(double)));
+      PYN_HIP(L.S.alloc((size_t)L.nn * nst * b * b));
+      PYN_HIP(L.dinv.alloc(n));
+      PYN_HIP(L.b.alloc(n));
+      PYN_HIP(L.z[1].alloc(n));
     }
   }
   PYN_TRY(pyn_dinv_ensure(c, A));
   mg_decouple0_kernel<<<grid_for(c->n_owned * b), 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, c->n_owned, b, H.L[0].dec, H.L[0].diag);
   DevTmp dbad;
   PYN_HIP(dbad.alloc(sizeof(int)));
-  PYN_HIP(hipMemsetAsync(dbad.p, 0, sizeof(int), s));
+  PYN_HIP(hipMemsetAsync(dbad.get(), 0, sizeof(int), s));
   for (int l = 1; l < nlev; ++l) {
     MgLevel &F = H.L[l - 1], &C = H.L[l];
     const Grid gf = grid_of(H, l - 1), gc = grid_of(H, l);
@@ -946,7 +933,7 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
     PYN_MG_DISPATCH(b, dim, (mg_dinv_kernel<B_, D_><<<grid_for(C.nn * b), 256, 0, s>>>(C.nn, C.S, C.dinv)));
   }
   int bad = 0;
-  PYN_HIP(hipMemcpyAsync(&bad, dbad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipMemcpyAsync(&bad, dbad.get(), sizeof(int), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipStreamSynchronize(s));
   PYN_HIP(hipGetLastError());
   PYN_CHECK(!bad, "multigrid: a row of the matrix reaches further than 2 lattice nodes (not a Q1 / ngl 3 lattice operator)");
@@ -954,8 +941,8 @@ static int mg_build(pyn_ctx* c, DMat& A, const pyn_mg_opts& o) {
   {
     MgLevel& C = H.L[nlev - 1];
     const int64_t n = C.nn * b;
-    PYN_HIP(hipMalloc((void**)&H.lu, (size_t)n * n * sizeof(double)));
-    PYN_HIP(hipMalloc((void**)&H.piv, (size_t)(2 * n + 1) * sizeof(int)));
+    PYN_HIP(H.lu.alloc((size_t)n * n));
+    PYN_HIP(H.piv.alloc((size_t)(2 * n + 1)));
     H.lu_n = n;
     PYN_HIP(hipMemsetAsync(H.lu, 0, (size_t)n * n * sizeof(double), s));
     const Grid gc = grid_of(H, nlev - 1);

@@ -73,11 +73,10 @@ __global__ void bc_elem_flag_kernel(const int32_t* __restrict__ conn, int nn, in
 
 }  // namespace
 
-void pyn_rhs_release(DMat& M) {
-  (void)hipFree(M.c_crow);
-  (void)hipFree(M.c_rsel);
-  (void)hipFree(M.c_cptr);
-  M.c_crow = M.c_rsel = M.c_cptr = nullptr;
+static void rhs_release(DMat& M) {   // the row selection of a compact matrix
+  M.c_crow.reset();
+  M.c_rsel.reset();
+  M.c_cptr.reset();
   M.c_nr = M.c_nnzb = 0;
   M.c_stamp = -1;
 }
@@ -91,9 +90,8 @@ int pyn_rhs_ensure(pyn_ctx* c, DMat& M, bool relayout) {
   hipStream_t s = c->stream;
   const int64_t n = c->n_owned;
   PYN_HIP(hipStreamSynchronize(s));   // no kernel in flight may still read the old arrays
-  (void)hipFree(M.val);
-  M.val = nullptr;
-  pyn_rhs_release(M);
+  M.val.reset();   // a failure below leaves the matrix without a layout (c_crow empty): the next call lays it out again
+  rhs_release(M);
   DevTmp tflag, tlen, tscan, tmp, tnr;
   PYN_HIP(tflag.alloc((n + 1) * sizeof(int32_t)));
   PYN_HIP(tlen.alloc((n + 1) * sizeof(int32_t)));
@@ -104,28 +102,34 @@ int pyn_rhs_ensure(pyn_ctx* c, DMat& M, bool relayout) {
   size_t tb = 0;
   PYN_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, tlen.as<int32_t>(), tscan.as<int32_t>(), (int)(n + 1), s));
   PYN_HIP(tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, tlen.as<int32_t>(), tscan.as<int32_t>(), (int)(n + 1), s));
-  PYN_HIP(hipMalloc((void**)&M.c_crow, std::max<int64_t>(n, 1) * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&M.c_rsel, std::max<int64_t>(n, 1) * sizeof(int32_t)));   // upper bound; trimmed below
-  rhs_crow_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(tflag.as<int32_t>(), tscan.as<int32_t>(), n, M.c_crow);
+  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.get(), tb, tlen.as<int32_t>(), tscan.as<int32_t>(), (int)(n + 1), s));
+  DevBuf<int32_t> crow, rsel, cptr;   // built here, committed together with the values at the end
+  DevBuf<double> val;
+  PYN_HIP(crow.alloc(std::max<int64_t>(n, 1)));
+  PYN_HIP(rsel.alloc(std::max<int64_t>(n, 1)));   // upper bound; trimmed below
+  rhs_crow_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(tflag.as<int32_t>(), tscan.as<int32_t>(), n, crow);
   hipcub::CountingInputIterator<int32_t> ids(0);
   tb = 0;
-  PYN_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, ids, tflag.as<int32_t>(), M.c_rsel, tnr.as<int64_t>(), (int)n, s));
+  PYN_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, ids, tflag.as<int32_t>(), rsel.get(), tnr.as<int64_t>(), (int)n, s));
   PYN_HIP(tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceSelect::Flagged(tmp.p, tb, ids, tflag.as<int32_t>(), M.c_rsel, tnr.as<int64_t>(), (int)n, s));
+  PYN_HIP(hipcub::DeviceSelect::Flagged(tmp.get(), tb, ids, tflag.as<int32_t>(), rsel.get(), tnr.as<int64_t>(), (int)n, s));
   int64_t nr = 0;
   int32_t total = 0;
-  PYN_HIP(hipMemcpyAsync(&nr, tnr.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipMemcpyAsync(&nr, tnr.get(), sizeof(int64_t), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipMemcpyAsync(&total, tscan.as<int32_t>() + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipStreamSynchronize(s));
-  PYN_HIP(hipMalloc((void**)&M.c_cptr, (nr + 1) * sizeof(int32_t)));
-  rhs_cptr_kernel<<<(int)((nr + 1 + 255) / 256), 256, 0, s>>>(M.c_rsel, tscan.as<int32_t>(), nr, n, M.c_cptr);
+  PYN_HIP(cptr.alloc(nr + 1));
+  rhs_cptr_kernel<<<(int)((nr + 1 + 255) / 256), 256, 0, s>>>(rsel, tscan.as<int32_t>(), nr, n, cptr);
+  const size_t nval = (size_t)std::max<int64_t>(total, 1) * M.br * M.bc;
+  PYN_HIP(val.alloc(nval));
+  PYN_HIP(hipMemsetAsync(val, 0, nval * sizeof(double), s));
+  PYN_HIP(hipStreamSynchronize(s));   // the scratch arrays go out of scope
+  M.val = std::move(val);
+  M.c_crow = std::move(crow);
+  M.c_rsel = std::move(rsel);
+  M.c_cptr = std::move(cptr);
   M.c_nr = nr;
   M.c_nnzb = total;
-  const size_t bytes = (size_t)std::max<int64_t>(total, 1) * M.br * M.bc * sizeof(double);
-  PYN_HIP(hipMalloc((void**)&M.val, bytes));
-  PYN_HIP(hipMemsetAsync(M.val, 0, bytes, s));
-  PYN_HIP(hipStreamSynchronize(s));   // the scratch arrays go out of scope
   M.touch();
   M.rhs_clean = PYN_RHS_ANY;
   M.c_stamp = c->bc_stamp;
@@ -147,11 +151,13 @@ int pyn_rhs_expand(pyn_ctx* c, const DMat& M, double* full) {
 int pyn_bc_elements(pyn_ctx* c) {
   if (c->esel_stamp == c->bc_stamp && c->d_esel) return PYN_OK;
   hipStream_t s = c->stream;
-  (void)hipFree(c->d_esel);
-  c->d_esel = nullptr;
+  c->d_esel.reset();   // a failure below leaves no list: the next call builds it again
   c->n_esel = 0;
+  c->esel_stamp = -1;
+  DevBuf<int32_t> esel;
   if (!c->d_bcmask) {
-    PYN_HIP(hipMalloc((void**)&c->d_esel, sizeof(int32_t)));
+    PYN_HIP(esel.alloc(1));
+    c->d_esel = std::move(esel);
     c->esel_stamp = c->bc_stamp;
     return PYN_OK;
   }
@@ -159,14 +165,17 @@ int pyn_bc_elements(pyn_ctx* c) {
   PYN_HIP(tflag.alloc((size_t)c->n_elem));
   PYN_HIP(tn.alloc(sizeof(int64_t)));
   bc_elem_flag_kernel<<<(int)((c->n_elem + 255) / 256), 256, 0, s>>>(c->d_conn, c->nn, c->n_elem, c->d_bcmask, c->bc_ndof, tflag.as<uint8_t>());
-  PYN_HIP(hipMalloc((void**)&c->d_esel, (size_t)c->n_elem * sizeof(int32_t)));
+  PYN_HIP(esel.alloc((size_t)c->n_elem));
   hipcub::CountingInputIterator<int32_t> ids(0);
   size_t tb = 0;
-  PYN_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, ids, tflag.as<uint8_t>(), c->d_esel, tn.as<int64_t>(), (int)c->n_elem, s));
+  PYN_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, ids, tflag.as<uint8_t>(), esel.get(), tn.as<int64_t>(), (int)c->n_elem, s));
   PYN_HIP(tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceSelect::Flagged(tmp.p, tb, ids, tflag.as<uint8_t>(), c->d_esel, tn.as<int64_t>(), (int)c->n_elem, s));
-  PYN_HIP(hipMemcpyAsync(&c->n_esel, tn.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipcub::DeviceSelect::Flagged(tmp.get(), tb, ids, tflag.as<uint8_t>(), esel.get(), tn.as<int64_t>(), (int)c->n_elem, s));
+  int64_t n_esel = 0;
+  PYN_HIP(hipMemcpyAsync(&n_esel, tn.get(), sizeof(int64_t), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipStreamSynchronize(s));
+  c->d_esel = std::move(esel);
+  c->n_esel = n_esel;
   c->esel_stamp = c->bc_stamp;
   return PYN_OK;
 }
@@ -181,9 +190,10 @@ extern "C" int pyn_mat_create_rhs(pyn_ctx* c, int br, int bc, int* mat_id) {
   m.bc = bc;
   m.rhs_compact = true;
   m.live = true;
-  c->mats.push_back(m);
+  PYN_TRY(pyn_rhs_ensure(c, m, true));   // rows of the CURRENT Dirichlet set (laid out again by an assembly under another one)
+  c->mats.push_back(std::move(m));      // only a matrix that was laid out gets a handle
   *mat_id = (int)c->mats.size() - 1;
-  return pyn_rhs_ensure(c, c->mats.back(), true);   // rows of the CURRENT Dirichlet set (laid out again by an assembly under another one)
+  return PYN_OK;
 }
 
 extern "C" int pyn_mat_stored_blocks(pyn_ctx* c, int mat_id, int64_t* blocks, int64_t* node_rows) {

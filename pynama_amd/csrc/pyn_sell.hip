@@ -806,29 +806,26 @@ static int lattice_pattern_dictionary(pyn_ctx* c, bool* done) {
   }
   hipStream_t s = c->stream;
   const int64_t n = c->n_owned;
-  PYN_HIP(hipMalloc((void**)&c->sell_pid, n * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&c->sell_tab, (size_t)PAT_MAX * PAT_W * sizeof(int32_t)));
+  DevBuf<int32_t> pid, ptab;   // installed only when the closed form describes the graph
+  PYN_HIP(pid.alloc(n));
+  PYN_HIP(ptab.alloc((size_t)PAT_MAX * PAT_W));
   DevTmp t_len, t_bad;
   PYN_HIP(t_len.alloc(PAT_MAX * sizeof(int32_t)));
   PYN_HIP(t_bad.alloc(sizeof(int)));
-  PYN_HIP(hipMemsetAsync(t_bad.p, 0, sizeof(int), s));
-  PYN_HIP(hipMemcpyAsync(c->sell_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  PYN_HIP(hipMemcpyAsync(t_len.p, tlen.data(), tlen.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  pat_lattice_pid_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(ngl, dim, NX, NY, NZ, n, c->sell_pid);
+  PYN_HIP(hipMemsetAsync(t_bad.get(), 0, sizeof(int), s));
+  PYN_HIP(hipMemcpyAsync(ptab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  PYN_HIP(hipMemcpyAsync(t_len.get(), tlen.data(), tlen.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  pat_lattice_pid_kernel<<<(int)((n + 255) / 256), 256, 0, s>>>(ngl, dim, NX, NY, NZ, n, pid);
   const int64_t stride = std::max<int64_t>(1, n / 65521);      // (a prime-ish count: the sample walks through every class)
   const int64_t ns = (n + stride - 1) / stride + 1;
-  pat_verify_sample_kernel<<<(int)((ns + 255) / 256), 256, 0, s>>>(c->d_rowptr, c->d_colidx, n, stride, c->sell_pid, c->sell_tab,
+  pat_verify_sample_kernel<<<(int)((ns + 255) / 256), 256, 0, s>>>(c->d_rowptr, c->d_colidx, n, stride, pid, ptab,
                                                                   t_len.as<int32_t>(), t_bad.as<int>());
   int hbad = 0;
-  PYN_HIP(hipMemcpyAsync(&hbad, t_bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipMemcpyAsync(&hbad, t_bad.get(), sizeof(int), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipStreamSynchronize(s));
-  if (hbad) {   // not the graph this closed form describes: let the general construction decide
-    PYN_HIP(hipFree(c->sell_pid));
-    PYN_HIP(hipFree(c->sell_tab));
-    c->sell_pid = nullptr;
-    c->sell_tab = nullptr;
-    return PYN_OK;
-  }
+  if (hbad) return PYN_OK;   // not the graph this closed form describes: let the general construction decide
+  c->sell_pid = std::move(pid);
+  c->sell_tab = std::move(ptab);
   c->sell_npat = npat;
   *done = true;
   return PYN_OK;
@@ -856,36 +853,33 @@ static int build_pattern_dictionary(pyn_ctx* c, int maxw) {
   size_t tb = 0;
   PYN_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, h, hs, n, 0, 64, s));
   PYN_HIP(t_tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceRadixSort::SortKeys(t_tmp.p, tb, h, hs, n, 0, 64, s));
+  PYN_HIP(hipcub::DeviceRadixSort::SortKeys(t_tmp.get(), tb, h, hs, n, 0, 64, s));
   tb = 0;
   PYN_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, hs, hu, d_nu, n, s));
   PYN_HIP(hipStreamSynchronize(s));
   PYN_HIP(t_tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceSelect::Unique(t_tmp.p, tb, hs, hu, d_nu, n, s));
+  PYN_HIP(hipcub::DeviceSelect::Unique(t_tmp.get(), tb, hs, hu, d_nu, n, s));
   int64_t nu = 0;
   PYN_HIP(hipMemcpyAsync(&nu, d_nu, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipStreamSynchronize(s));
   if (nu < 1 || nu > PAT_MAX) return PYN_OK;  // irregular numbering: explicit columns
-  PYN_HIP(hipMalloc((void**)&c->sell_pid, n * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&c->sell_tab, (size_t)PAT_MAX * PAT_W * sizeof(int32_t)));
+  DevBuf<int32_t> pid, ptab;   // installed only when every row matches its pattern
+  PYN_HIP(pid.alloc(n));
+  PYN_HIP(ptab.alloc((size_t)PAT_MAX * PAT_W));
   PYN_HIP(t_rep.alloc(PAT_MAX * sizeof(int32_t)));
   PYN_HIP(t_len.alloc(PAT_MAX * sizeof(int32_t)));
   PYN_HIP(t_bad.alloc(sizeof(int)));
-  PYN_HIP(hipMemsetAsync(t_bad.p, 0, sizeof(int), s));
-  PYN_HIP(hipMemsetAsync(c->sell_tab, 0, (size_t)PAT_MAX * PAT_W * sizeof(int32_t), s));
-  pat_assign_kernel<<<grid, 256, 0, s>>>(h, n, hu, (int)nu, c->sell_pid, t_rep.as<int32_t>());
-  pat_table_kernel<<<(int)nu, 64, 0, s>>>(c->d_rowptr, c->d_colidx, t_rep.as<int32_t>(), (int)nu, c->sell_tab, t_len.as<int32_t>());
-  pat_verify_kernel<<<grid, 256, 0, s>>>(c->d_rowptr, c->d_colidx, n, c->sell_pid, c->sell_tab, t_len.as<int32_t>(), t_bad.as<int>());
+  PYN_HIP(hipMemsetAsync(t_bad.get(), 0, sizeof(int), s));
+  PYN_HIP(hipMemsetAsync(ptab, 0, (size_t)PAT_MAX * PAT_W * sizeof(int32_t), s));
+  pat_assign_kernel<<<grid, 256, 0, s>>>(h, n, hu, (int)nu, pid, t_rep.as<int32_t>());
+  pat_table_kernel<<<(int)nu, 64, 0, s>>>(c->d_rowptr, c->d_colidx, t_rep.as<int32_t>(), (int)nu, ptab, t_len.as<int32_t>());
+  pat_verify_kernel<<<grid, 256, 0, s>>>(c->d_rowptr, c->d_colidx, n, pid, ptab, t_len.as<int32_t>(), t_bad.as<int>());
   int hbad = 0;
-  PYN_HIP(hipMemcpyAsync(&hbad, t_bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  PYN_HIP(hipMemcpyAsync(&hbad, t_bad.get(), sizeof(int), hipMemcpyDeviceToHost, s));
   PYN_HIP(hipStreamSynchronize(s));
-  if (hbad != 0) {  // a hash collision shows up here: fall back to explicit columns
-    PYN_HIP(hipFree(c->sell_pid));
-    PYN_HIP(hipFree(c->sell_tab));
-    c->sell_pid = nullptr;
-    c->sell_tab = nullptr;
-    return PYN_OK;
-  }
+  if (hbad != 0) return PYN_OK;  // a hash collision shows up here: fall back to explicit columns
+  c->sell_pid = std::move(pid);
+  c->sell_tab = std::move(ptab);
   c->sell_npat = (int)nu;
   return PYN_OK;
 }
@@ -1005,7 +999,7 @@ static int sell_structure(pyn_ctx* c, const DMat& A, SellShape** out) {
   q.br = A.br;
   q.bc = A.bc;
   q.ns = ns;
-  PYN_HIP(hipMalloc((void**)&q.w, ns * sizeof(int)));
+  PYN_HIP(q.w.alloc(ns));
   sell_width_kernel<<<(int)std::min<int64_t>((ns + 255) / 256, 4096), 256, 0, s>>>(c->d_rowptr, n, A.br, A.bc, ns, q.w);
   std::vector<int> w((size_t)ns);
   PYN_HIP(hipMemcpyAsync(w.data(), q.w, ns * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1017,7 +1011,7 @@ static int sell_structure(pyn_ctx* c, const DMat& A, SellShape** out) {
     q.maxw = std::max(q.maxw, w[i]);
   }
   q.total = ptr[ns];
-  PYN_HIP(hipMalloc((void**)&q.ptr, (ns + 1) * sizeof(int64_t)));
+  PYN_HIP(q.ptr.alloc(ns + 1));
   PYN_HIP(hipMemcpyAsync(q.ptr, ptr.data(), (ns + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
   PYN_HIP(hipStreamSynchronize(s));
   if (c->n_ghost > 0) {
@@ -1028,7 +1022,7 @@ static int sell_structure(pyn_ctx* c, const DMat& A, SellShape** out) {
     slice_ghost_flag_kernel<<<(int)std::min<int64_t>((ns + 255) / 256, 4096), 256, 0, s>>>(c->d_rowptr, c->d_colidx, c->n_owned, A.br,
                                                                                        ns, tf.as<int>());
     std::vector<int> fl((size_t)ns);
-    PYN_HIP(hipMemcpyAsync(fl.data(), tf.p, ns * sizeof(int), hipMemcpyDeviceToHost, s));
+    PYN_HIP(hipMemcpyAsync(fl.data(), tf.get(), ns * sizeof(int), hipMemcpyDeviceToHost, s));
     PYN_HIP(hipStreamSynchronize(s));
     int64_t i0 = 0, i1 = ns;
     while (i0 < ns && fl[i0]) ++i0;
@@ -1040,7 +1034,7 @@ static int sell_structure(pyn_ctx* c, const DMat& A, SellShape** out) {
       q.int_end = i1;
     }
   }
-  c->sell_shapes.push_back(q);
+  c->sell_shapes.push_back(std::move(q));
   *out = &c->sell_shapes.back();
   return PYN_OK;
 }
@@ -1050,28 +1044,28 @@ static int sell_image(pyn_ctx* c, DMat& A, SellShape* S, bool fresh) {
   hipStream_t s = c->stream;
   const int64_t n = c->n_owned * A.br, ns = S->ns;
   if (!A.sell_val) {
-    PYN_HIP(hipMalloc((void**)&A.sell_val, S->total * sizeof(double)));
+    PYN_HIP(A.sell_val.alloc(S->total));
     A.sell_valid = false;
   }
   const bool cols = c->sell_npat == 0 && !S->col;   // this image also writes the shape's explicit column array
-  if (cols) PYN_HIP(hipMalloc((void**)&S->col, S->total * sizeof(int32_t)));
+  if (cols) PYN_HIP(S->col.alloc(S->total));
   if (A.sell_valid && !fresh && !cols) return PYN_OK;
   if (A.br == 1 && A.bc == 1 && (size_t)SH * S->maxw * 12 <= 64 * 1024) {
     const size_t lds = (size_t)SH * S->maxw * (cols ? 12 : 8);
     const int grid = (int)std::min<int64_t>(ns, 256 * 32);
     auto fill = cols ? sell_fill_kernel<true> : sell_fill_kernel<false>;
-    fill<<<grid, 64, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, ns, S->ptr, S->w, S->maxw, A.sell_val, cols ? S->col : nullptr);
+    fill<<<grid, 64, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, ns, S->ptr, S->w, S->maxw, A.sell_val, cols ? S->col.get() : nullptr);
   } else if ((size_t)SH * S->maxw * sizeof(double) <= 96 * 1024 && !getenv("PYNAMA_SELL_FILL_STRIDED")) {
     const size_t lds = (size_t)SH * S->maxw * sizeof(double);
     const int grid = (int)std::min<int64_t>(ns, 256 * 8);
     PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sell_fill_block_lds_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     PYN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(sell_fill_block_lds_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     auto fill = cols ? sell_fill_block_lds_kernel<true> : sell_fill_block_lds_kernel<false>;
-    fill<<<grid, 256, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, cols ? S->col : nullptr);
+    fill<<<grid, 256, lds, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, cols ? S->col.get() : nullptr);
   } else {
     const int grid = (int)std::min<int64_t>((ns + 3) / 4, 256 * 16);
     auto fill = cols ? sell_fill_block_kernel<true> : sell_fill_block_kernel<false>;
-    fill<<<grid, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, cols ? S->col : nullptr);
+    fill<<<grid, 256, 0, s>>>(c->d_rowptr, c->d_colidx, A.val, n, A.br, A.bc, ns, S->ptr, S->w, A.sell_val, cols ? S->col.get() : nullptr);
   }
   PYN_HIP(hipGetLastError());
   A.sell_valid = true;
@@ -1094,10 +1088,7 @@ int pyn_sell_ensure(pyn_ctx* c, DMat& A, bool solver) {
   ProductPlan P = product_choose(f, k, &keep_image);
   PYN_CHECK(P.kind != PK_NONE, "no block-CSR product for block shape %dx%d", A.br, A.bc);
   if (!keep_image) {   // the products read A.val
-    if (A.sell_val) {
-      (void)hipFree(A.sell_val);
-      A.sell_val = nullptr;
-    }
+    A.sell_val.reset();
     A.sell_valid = false;
   }
   if (P.kind >= PK_SELL && P.kind <= PK_SELLB_D) PYN_TRY(sell_image(c, A, S, c->sell_shapes.size() != shapes));
@@ -1328,16 +1319,9 @@ int pyn_sell_spmv(pyn_ctx* c, const DMat& A, const ProductPlan& P, const double*
 }
 
 void pyn_sell_drop_structure(pyn_ctx* c) {
-  for (auto& q : c->sell_shapes) {
-    (void)hipFree(q.ptr);
-    (void)hipFree(q.w);
-    (void)hipFree(q.col);
-  }
   c->sell_shapes.clear();
-  (void)hipFree(c->sell_pid);
-  (void)hipFree(c->sell_tab);
-  c->sell_pid = nullptr;
-  c->sell_tab = nullptr;
+  c->sell_pid.reset();
+  c->sell_tab.reset();
   c->sell_npat = 0;
   c->sell_dict_built = false;
 }

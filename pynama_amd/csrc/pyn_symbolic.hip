@@ -35,14 +35,6 @@ __global__ void split_keys_kernel(const unsigned long long* __restrict__ keys, i
 static int pyn_symbolic_reset_dependents(pyn_ctx* c) {
   PYN_TRY(pyn_patch_plan_set_kind(c, 0, 0, nullptr, nullptr));
   PYN_TRY(pyn_patch_plan_set_kind(c, 1, 0, nullptr, nullptr));
-  for (auto& m : c->mats) {
-    (void)hipFree(m.val);
-    (void)hipFree(m.sell_val);
-    (void)hipFree(m.dinv);
-    m.release_lu();
-    m.release_mg();
-    pyn_rhs_release(m);
-  }
   c->mats.clear();
   c->esel_stamp = -1;
   pyn_sell_drop_structure(c);
@@ -81,12 +73,12 @@ extern "C" int pyn_csr_symbolic(pyn_ctx* c) {
   size_t tb = 0;
   PYN_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, k0, k1, total, 0, 64, s));
   PYN_HIP(tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.p, tb, k0, k1, total, 0, 64, s));
+  PYN_HIP(hipcub::DeviceRadixSort::SortKeys(tmp.get(), tb, k0, k1, total, 0, 64, s));
   tb = 0;
   PYN_HIP(hipcub::DeviceSelect::Unique(nullptr, tb, k1, k0, d_nuniq, total, s));
   PYN_HIP(hipStreamSynchronize(s));
   PYN_HIP(tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceSelect::Unique(tmp.p, tb, k1, k0, d_nuniq, total, s));
+  PYN_HIP(hipcub::DeviceSelect::Unique(tmp.get(), tb, k1, k0, d_nuniq, total, s));
   int64_t nuniq = 0;
   unsigned long long last = 0;
   PYN_HIP(hipMemcpyAsync(&nuniq, d_nuniq, sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -96,28 +88,26 @@ extern "C" int pyn_csr_symbolic(pyn_ctx* c) {
   if (last == ~0ull) --nuniq;  // the dropped (non-owned) rows
   PYN_CHECK(nuniq > 0 && nuniq < (int64_t)INT32_MAX, "pattern has %lld entries (int32 CSR limit)", (long long)nuniq);
 
-  (void)hipFree(c->d_rowptr);
-  (void)hipFree(c->d_colidx);
-  c->d_rowptr = nullptr;
-  c->d_colidx = nullptr;
-  c->nnzb = 0;
   PYN_HIP(tcnt.alloc((c->n_owned + 1) * sizeof(int32_t)));
   int32_t* rowcnt = tcnt.as<int32_t>();
-  PYN_HIP(hipMalloc((void**)&c->d_rowptr, (c->n_owned + 1) * sizeof(int32_t)));
-  PYN_HIP(hipMalloc((void**)&c->d_colidx, nuniq * sizeof(int32_t)));
+  DevBuf<int32_t> rowptr, colidx;   // the new graph: committed below, after the last step that can fail
+  PYN_HIP(rowptr.alloc(c->n_owned + 1));
+  PYN_HIP(colidx.alloc(nuniq));
   PYN_HIP(hipMemsetAsync(rowcnt, 0, (c->n_owned + 1) * sizeof(int32_t), s));
   grid = (int)std::min<int64_t>((nuniq + 255) / 256, 65536);
-  split_keys_kernel<<<grid, 256, 0, s>>>(k0, nuniq, c->d_colidx, rowcnt);
+  split_keys_kernel<<<grid, 256, 0, s>>>(k0, nuniq, colidx, rowcnt);
   tb = 0;
-  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rowcnt, c->d_rowptr, (int)(c->n_owned + 1), s));
+  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, rowcnt, rowptr.get(), (int)(c->n_owned + 1), s));
   PYN_HIP(hipStreamSynchronize(s));
   PYN_HIP(tmp.alloc(tb));
-  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, rowcnt, c->d_rowptr, (int)(c->n_owned + 1), s));
+  PYN_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.get(), tb, rowcnt, rowptr.get(), (int)(c->n_owned + 1), s));
   PYN_HIP(hipEventRecord(c->ev1, s));
   PYN_HIP(hipStreamSynchronize(s));
   float ms = 0;
   PYN_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
   c->timers[PYN_T_SYMBOLIC] = ms;
+  c->d_rowptr = std::move(rowptr);   // the stream is idle: no kernel still reads the old graph
+  c->d_colidx = std::move(colidx);
   c->nnzb = nuniq;
   return pyn_symbolic_reset_dependents(c);
 }

@@ -106,7 +106,7 @@ int stage_args(pyn_ctx* c, int x, int m, const int* ids, const char* what, Stage
   PYN_CHECK(m >= 0 && m <= PYN_TS_MAX_STAGES, "%s: %d stage vectors, at most %d", what, m, PYN_TS_MAX_STAGES);
   PYN_CHECK(m == 0 || ids, "%s: ids is NULL", what);
   const int bs = c->vecs[x].bs;
-  bool pairs = ((uintptr_t)c->vecs[x].d & 15) == 0;
+  bool pairs = ((uintptr_t)c->vecs[x].d.get() & 15) == 0;
   for (int j = 0; j < PYN_TS_MAX_STAGES; ++j) {
     a.v[j] = nullptr;
     a.w[j] = a.d[j] = 0.0;
@@ -131,7 +131,7 @@ extern "C" int pyn_vec_maxpy(pyn_ctx* c, int y, int x, int m, const int* ids, co
   PYN_TRY(pyn_check_vec(c, y, "pyn_vec_maxpy y"));
   PYN_CHECK(c->vecs[y].bs == c->vecs[x].bs, "pyn_vec_maxpy: block size mismatch (y %d, x %d)", c->vecs[y].bs, c->vecs[x].bs);
   PYN_CHECK(m == 0 || w, "pyn_vec_maxpy: w is NULL");
-  if (((uintptr_t)c->vecs[y].d & 15) != 0) nv = 0;
+  if (((uintptr_t)c->vecs[y].d.get() & 15) != 0) nv = 0;
   for (int j = 0; j < m; ++j) a.w[j] = w[j];
   double* yd = c->vecs[y].d;
   const double* xd = c->vecs[x].d;

@@ -30,6 +30,13 @@ def test_library_exports_every_declared_symbol():
     assert len(_lib.source_hash()) == 16 and _lib.source_hash() != "unknown"
 
 
+def test_alloc_live_needs_no_device():
+    """the live-allocation counter is process-wide state: readable before any context exists, two non-negative integers"""
+    from pynama_amd import _lib
+    n, b = _lib.alloc_live()
+    assert isinstance(n, int) and isinstance(b, int) and n >= 0 and b >= 0 and (n == 0) == (b == 0)
+
+
 def test_no_cpu_fallback():
     from pynama_amd import _lib
     if _lib.device_count() > 0:
