@@ -1108,7 +1108,7 @@ int table_id(int id, int last) { return id >= 1 && id <= last ? id : 0; }   // i
 // treats as that value: the default arm of a tile table, at least one workgroup)
 #define PYN_I(f, e, d) \
   if (const char* v = getenv(e)) k.f = d < 0 ? std::max(atoi(v), 0) : atoi(v);
-AsmKnobs asm_knobs() { AsmKnobs k; PYN_ASM_KNOBS(PYN_F, PYN_I) return k; }
+AsmKnobs asm_knobs() { AsmKnobs k; PYN_ASM_KNOBS(PYN_F, PYN_I) PYN_ASM_LAUNCH_KNOBS(PYN_F, PYN_I) return k; }
 AsmKnobs lat_fill_knobs() { AsmKnobs k; PYN_LAT_FILL_KNOBS(PYN_F, PYN_I) return k; }
 #undef PYN_F
 #undef PYN_I

@@ -132,6 +132,25 @@ __device__ __forceinline__ bool lat_tile_element(const LatArgs& T, int x0, int y
   return t < LT::NE && gx >= 0 && gx < T.nx - 1 && gy >= 0 && gy < T.ny - 1 && gl >= 0 && gl < T.npl - 1;
 }
 
+// add L_e of tile element (lx, ly, lz) to the rows the tile owns (27-point stencil slots)
+template <int TX, int TY, int TZ>
+__device__ __forceinline__ void lat_scatter_L(const LatArgs& T, int z0, double* acc, int lx, int ly, int lz, const double (&L)[36]) {
+  constexpr int CX[8] = {0, 0, 1, 1, 0, 1, 1, 0};
+  constexpr int CY[8] = {0, 1, 1, 0, 0, 0, 1, 1};
+  constexpr int CZ[8] = {0, 0, 0, 0, 1, 1, 1, 1};
+#pragma unroll
+  for (int a = 0; a < 8; ++a) {
+    const int rx = lx - 1 + CX[a], ry = ly - 1 + CY[a], rz = lz - 1 + CZ[a];
+    if (rx < 0 || rx >= TX || ry < 0 || ry >= TY || rz < 0 || rz >= TZ || z0 + rz >= T.n_own) continue;
+    double* row = acc + ((rz * TY + ry) * TX + rx) * 27;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int kk = (CZ[c] - CZ[a] + 1) * 9 + (CY[c] - CY[a] + 1) * 3 + (CX[c] - CX[a] + 1);
+      atomicAdd(&row[kk], L[tri(a, c)]);
+    }
+  }
+}
+
 // `pre`: the corners of the thread's FIRST element (t = t0) were requested by the caller before it cleared the accumulators (their
 // latency then overlaps the clearing and its barrier); later elements of the thread (tiles with more than nt elements) load here
 template <int TX, int TY, int TZ>
@@ -140,9 +159,6 @@ __device__ __forceinline__ void lat_integrate_affine(const LatArgs& T, int x0, i
   using LT = LatTile<TX, TY, TZ>;
   const int nx = T.nx, ny = T.ny;
   const double* __restrict__ S = T.q.aff + 248;
-  constexpr int CX[8] = {0, 0, 1, 1, 0, 1, 1, 0};
-  constexpr int CY[8] = {0, 1, 1, 0, 0, 0, 1, 1};
-  constexpr int CZ[8] = {0, 0, 0, 0, 1, 1, 1, 1};
   for (int t = t0; t < LT::NE; t += nt) {
     const int lx = t % LT::EX, ly = (t / LT::EX) % LT::EY, lz = t / (LT::EX * LT::EY);
     const int gx = x0 - 1 + lx, gy = y0 - 1 + ly, gl = T.p_own0 + z0 - 1 + lz;
@@ -156,17 +172,85 @@ __device__ __forceinline__ void lat_integrate_affine(const LatArgs& T, int x0, i
     } else {
       lat_affine_L(T, S, n00, gl, L);
     }
+    lat_scatter_L<TX, TY, TZ>(T, z0, acc, lx, ly, lz, L);
+  }
+}
+
+// ---- rectilinear lattices: the corners of an element are six numbers out of the three axis tables (LatArgs::axX / axY / axZ).
+// The BX + BY + BZ entries of a tile's node box are fetched with WAVE-UNIFORM addresses (tile origin from blockIdx, compile-time
+// offsets), i.e. through the scalar cache into SGPRs: no vector load stands in front of the tile's stores, and the scalar path
+// does not queue behind the stores of the other workgroups of the CU.  A lane picks its six values with select chains.
+template <int TX, int TY, int TZ>
+struct LatAxes {
+  using LT = LatTile<TX, TY, TZ>;
+  double x[LT::BX], y[LT::BY], z[LT::BZ];
+};
+
+// (compile-time recursion, not loops, here and in lat_pick: every index is a constant before any unrolling, so the entries are
+// scalars from the start -- with loops the compiler kept the arrays in scratch memory and indexed them per lane)
+template <int J, int N>
+__device__ __forceinline__ void lat_axis_copy(double (&d)[N], const double* __restrict__ src) {
+  if constexpr (J < N) {
+    d[J] = src[J];
+    lat_axis_copy<J + 1>(d, src);
+  }
+}
+
+template <int TX, int TY, int TZ>
+__device__ __forceinline__ void lat_axes_load(const LatArgs& T, int x0, int y0, int z0, LatAxes<TX, TY, TZ>& A) {
+  static_assert(TX <= LAT_AX_HI && TY <= LAT_AX_HI && TZ <= LAT_AX_HI, "the guard slots of the axis tables cover the last tile");
+  // slot of lattice index x0 - 1 + j is x0 + j (LAT_AX_LO == 1); planes by their position in the slab, ghosts included
+  static_assert(LAT_AX_LO == 1, "tile origin - 1 is slot `origin`");
+  const double* __restrict__ X = T.axX + __builtin_amdgcn_readfirstlane(x0);
+  const double* __restrict__ Y = T.axY + __builtin_amdgcn_readfirstlane(y0);
+  const double* __restrict__ Z = T.axZ + __builtin_amdgcn_readfirstlane(T.p_own0 + z0);
+  lat_axis_copy<0>(A.x, X);
+  lat_axis_copy<0>(A.y, Y);
+  lat_axis_copy<0>(A.z, Z);
+}
+
+// s[i], 0 <= i < N, s wave-uniform: a chain of selects over the scalars
+template <int J = 1, int N>
+__device__ __forceinline__ double lat_pick(const double (&s)[N], int i, double v) {
+  if constexpr (J < N)
+    return lat_pick<J + 1>(s, i, i >= J ? s[J] : v);
+  else
+    return v;
+}
+template <int N>
+__device__ __forceinline__ double lat_pick(const double (&s)[N], int i) {
+  return lat_pick<1>(s, i, s[0]);
+}
+
+// the four corners lat_affine_corners would load for element (lx, ly, lz) of the tile: the same doubles, so the same L
+template <int TX, int TY, int TZ>
+__device__ __forceinline__ void lat_axes_corners(const LatAxes<TX, TY, TZ>& A, int lx, int ly, int lz, double (&C4)[4][3]) {
+  const double xa = lat_pick(A.x, lx), xb = lat_pick(A.x, lx + 1);
+  const double ya = lat_pick(A.y, ly), yb = lat_pick(A.y, ly + 1);
+  const double za = lat_pick(A.z, lz), zb = lat_pick(A.z, lz + 1);
 #pragma unroll
-    for (int a = 0; a < 8; ++a) {
-      const int rx = lx - 1 + CX[a], ry = ly - 1 + CY[a], rz = lz - 1 + CZ[a];
-      if (rx < 0 || rx >= TX || ry < 0 || ry >= TY || rz < 0 || rz >= TZ || z0 + rz >= T.n_own) continue;
-      double* row = acc + ((rz * TY + ry) * TX + rx) * 27;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        const int kk = (CZ[c] - CZ[a] + 1) * 9 + (CY[c] - CY[a] + 1) * 3 + (CX[c] - CX[a] + 1);
-        atomicAdd(&row[kk], L[tri(a, c)]);
-      }
-    }
+  for (int d = 0; d < 4; ++d) {
+    C4[d][0] = d == 1 ? xb : xa;
+    C4[d][1] = d == 2 ? yb : ya;
+    C4[d][2] = d == 3 ? zb : za;
+  }
+}
+
+template <int TX, int TY, int TZ>
+__device__ __forceinline__ void lat_integrate_axes(const LatArgs& T, int x0, int y0, int z0, double* acc, int t0, int nt,
+                                                   const LatAxes<TX, TY, TZ>& A) {
+  using LT = LatTile<TX, TY, TZ>;
+  const int nx = T.nx, ny = T.ny;
+  const double* __restrict__ S = T.q.aff + 248;
+  for (int t = t0; t < LT::NE; t += nt) {
+    const int lx = t % LT::EX, ly = (t / LT::EX) % LT::EY, lz = t / (LT::EX * LT::EY);
+    const int gx = x0 - 1 + lx, gy = y0 - 1 + ly, gl = T.p_own0 + z0 - 1 + lz;
+    if (gx < 0 || gx >= nx - 1 || gy < 0 || gy >= ny - 1 || gl < 0 || gl >= T.npl - 1) continue;
+    double C4[4][3], Ji[3][3], L[36];
+    lat_axes_corners<TX, TY, TZ>(A, lx, ly, lz, C4);
+    const double det = lat_affine_geom_from(S, C4, Ji);
+    lat_affine_L_from(Ji, det, L);
+    lat_scatter_L<TX, TY, TZ>(T, z0, acc, lx, ly, lz, L);
   }
 }
 
@@ -179,9 +263,64 @@ __global__ void lattice_rowptr_check_kernel(LatArgs T, const int32_t* __restrict
 }
 
 
+// ---- once per mesh: is the lattice rectilinear, and what are its axes?  (pyn_lattice_axes_ensure)
+// candidate tables out of xyz: X from the first x-line, Y from the first node of every x-line of the first plane, Z from the first
+// node of every local plane (by position in the slab, ghost planes included); guard slots repeat the end values
+__global__ void lattice_axes_extract_kernel(LatArgs T, double* __restrict__ tab) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  const int sx = lat_axis_slots(T.nx), sy = lat_axis_slots(T.ny), sz = lat_axis_slots(T.npl);
+  if (s >= sx + sy + sz) return;
+  int64_t node;
+  int comp;
+  if (s < sx) {
+    node = (int64_t)T.P[0] + lat_axis_source(s, T.nx);
+    comp = 0;
+  } else if (s < sx + sy) {
+    node = (int64_t)T.P[0] + (int64_t)lat_axis_source(s - sx, T.ny) * T.nx;
+    comp = 1;
+  } else {
+    node = T.P[lat_axis_source(s - sx - sy, T.npl)];
+    comp = 2;
+  }
+  tab[s] = T.xyz[node * 3 + comp];
+}
+
+// every local node (ghost planes of a slab included) against (X[i], Y[j], Z[plane]) as raw 64-bit patterns: one ulp fails
+__global__ void lattice_axes_check_kernel(LatArgs T, const double* __restrict__ tab, int64_t n_node, int* flag) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_node) return;
+  const int x = (int)(i % T.nx), y = (int)((i / T.nx) % T.ny), j = (int)(i / ((int64_t)T.nx * T.ny));
+  const int sx = lat_axis_slots(T.nx), sy = lat_axis_slots(T.ny);
+  const double* q = T.xyz + ((int64_t)T.P[j] + (int64_t)y * T.nx + x) * 3;
+  const bool same = __double_as_longlong(q[0]) == __double_as_longlong(tab[LAT_AX_LO + x]) &&
+                    __double_as_longlong(q[1]) == __double_as_longlong(tab[sx + LAT_AX_LO + y]) &&
+                    __double_as_longlong(q[2]) == __double_as_longlong(tab[sx + sy + LAT_AX_LO + j]);
+  if (!same) *flag = 0;
+}
+
+
+// ---- once per Dirichlet set and tile shape: which tiles hold an imposed node in their node box?  (lattice_tilebc_ensure)
+// One wave per tile scans the flags of exactly the nodes lat_meta_load would load (the node box clipped to the local lattice, ghost
+// planes included) and sets the tile's bit; tiles without an imposed node issue no atomic.
+__global__ void __launch_bounds__(64) lattice_tilebc_kernel(LatArgs T, int TX, int TY, int TZ, uint32_t* __restrict__ map) {
+  const int b = blockIdx.x;
+  const int bx = b % T.ntx, by = (b / T.ntx) % T.nty, bz = b / (T.ntx * T.nty);
+  const int BX = TX + 2, BY = TY + 2, NB = BX * BY * (TZ + 2);
+  int any = 0;
+  for (int i = threadIdx.x; i < NB; i += 64) {
+    const int qx = i % BX, qy = (i / BX) % BY, qz = i / (BX * BY);
+    const int x = bx * TX - 1 + qx, y = by * TY - 1 + qy, pl = T.p_own0 + bz * TZ - 1 + qz;
+    if (x >= 0 && x < T.nx && y >= 0 && y < T.ny && pl >= 0 && pl < T.npl)
+      any |= T.bcmask[(int64_t)T.P[pl] + (int64_t)y * T.nx + x] != 0;
+  }
+  if (__any(any) && threadIdx.x == 0) atomicOr(&map[b >> 5], 1u << (b & 31));
+}
+
 // one tile per workgroup
-template <int TX, int TY, int TZ, bool AFF>
+// AX (with AFF): rectilinear lattice, element geometry from the axis tables -- no load from xyz at all
+template <int TX, int TY, int TZ, bool AFF, bool AX = false>
 __global__ void __launch_bounds__(TILE_THREADS, AFF ? 3 : 2) assemble_q1_hex_lattice_kernel(LatArgs T) {
+  static_assert(AFF || !AX, "the axis tables describe parallelepipeds");
   using LT = LatTile<TX, TY, TZ>;
   extern __shared__ __align__(16) double lds[];
   double* acc = lds;
@@ -195,17 +334,28 @@ __global__ void __launch_bounds__(TILE_THREADS, AFF ? 3 : 2) assemble_q1_hex_lat
   // parallelepipeds: the corner coordinates of this thread's element are requested FIRST; their latency (the largest single item of
   // a tile's lifetime: with PYNAMA_LATTICE_ABLATE=32, no coordinate loads, the kernel runs 12-16 % shorter) then overlaps the
   // clearing of the accumulators (-2 % in a same-process A/B)
+  // rectilinear: the scalar loads of the tile's table entries go out first of all (they share lgkmcnt with the LDS clear below:
+  // both are retired by the barrier's wait, nothing waits for them in between or in the element loop)
+  LatAxes<TX, TY, TZ> axs;
+  if (AX) lat_axes_load<TX, TY, TZ>(T, x0, y0, z0, axs);
   double C4[4][3];
-  if (AFF && T.ablate != 1) {
+  if (AFF && !AX && T.ablate != 1) {
     int n00, gl;
     if (lat_tile_element<TX, TY, TZ>(T, x0, y0, z0, tid, n00, gl)) lat_affine_corners(T, n00, gl, C4);
   }
+  // ... and with them the tile's bit of the Dirichlet map: clear = no imposed node in the node box, so no flag loads either, and no
+  // vector load at all stands in front of a plain tile's stores (the bit is needed only after the clear: one wait for both)
+  bool clean = false;
+  if (AX && T.tilebc) clean = !((T.tilebc[__builtin_amdgcn_readfirstlane(b) >> 5] >> (b & 31)) & 1u);
   LatMeta<TX, TY, TZ, TILE_THREADS> meta;
-  lat_meta_load<TX, TY, TZ, TILE_THREADS>(T, x0, y0, z0, tid, meta);   // in flight during the element phase
+  if (!AX) lat_meta_load<TX, TY, TZ, TILE_THREADS>(T, x0, y0, z0, tid, meta);   // in flight during the element phase
   for (int i = tid; i < LT::ACC; i += TILE_THREADS) acc[i] = 0.0;
+  if (AX) lat_meta_load<TX, TY, TZ, TILE_THREADS>(T, x0, y0, z0, tid, meta, clean);
   __syncthreads();
   if (T.ablate != 1) {
-    if (AFF)
+    if (AX)
+      lat_integrate_axes<TX, TY, TZ>(T, x0, y0, z0, acc, tid, TILE_THREADS, axs);
+    else if (AFF)
       lat_integrate_affine<TX, TY, TZ>(T, x0, y0, z0, acc, tid, TILE_THREADS, C4);
     else
       lat_integrate<TX, TY, TZ>(T, x0, y0, z0, acc, tid, TILE_THREADS);
@@ -1510,16 +1660,42 @@ int pyn_lattice_view(pyn_ctx* c) {
   return PYN_OK;
 }
 
+// The Dirichlet map of the tiles (LatArgs::tilebc) for the current Dirichlet set and this tile shape: cached on the lattice view under
+// the context's bc stamp, built into a local buffer and committed when the kernel has been enqueued.  T: ntx / nty filled.
+static int lattice_tilebc_ensure(pyn_ctx* c, const LatArgs& T, int TX, int TY, int TZ, int ntz) {
+  Lattice& L = c->lat;
+  const int shape = (TX << 16) | (TY << 8) | TZ;
+  if (L.d_tilebc && L.tilebc_stamp == c->bc_stamp && L.tilebc_shape == shape) return PYN_OK;
+  const int n_tiles = T.ntx * T.nty * ntz;
+  const size_t words = ((size_t)n_tiles + 31) / 32;
+  DevBuf<uint32_t> map;
+  PYN_HIP(map.alloc(words));
+  PYN_HIP(hipMemsetAsync(map, 0, words * sizeof(uint32_t), c->stream));
+  lattice_tilebc_kernel<<<n_tiles, 64, 0, c->stream>>>(T, TX, TY, TZ, map);
+  PYN_HIP(hipGetLastError());
+  L.d_tilebc = std::move(map);   // (freeing the old map waits for the device)
+  L.tilebc_stamp = c->bc_stamp;
+  L.tilebc_shape = shape;
+  return PYN_OK;
+}
+
 template <int TX, int TY, int TZ>
-static int launch_lattice(pyn_ctx* c, LatArgs& T, bool affine) {
+static int launch_lattice(pyn_ctx* c, LatArgs& T, bool affine, bool tilebc) {
   using LT = LatTile<TX, TY, TZ>;
   T.ntx = (T.nx + TX - 1) / TX;
   T.nty = (T.ny + TY - 1) / TY;
   const int ntz = (T.n_own + TZ - 1) / TZ;
   const int n_tiles = T.ntx * T.nty * ntz;
+  if (tilebc && affine && T.axX && T.bcmask) {   // the table variant reads the map
+    PYN_TRY(lattice_tilebc_ensure(c, T, TX, TY, TZ, ntz));
+    T.tilebc = c->lat.d_tilebc;
+  }
   PYN_TRY(pyn_kernel_lds(c, assemble_q1_hex_lattice_kernel<TX, TY, TZ, false>, LT::BYTES));
   PYN_TRY(pyn_kernel_lds(c, assemble_q1_hex_lattice_kernel<TX, TY, TZ, true>, LT::BYTES));
-  if (affine)
+  PYN_TRY(pyn_kernel_lds(c, assemble_q1_hex_lattice_kernel<TX, TY, TZ, true, true>, LT::BYTES));
+  if (affine && T.axX)   // rectilinear: geometry from the axis tables
+    assemble_q1_hex_lattice_kernel<TX, TY, TZ, true, true><<<n_tiles, TILE_THREADS, LT::BYTES, c->stream>>>(T);
+  else if (affine)
     assemble_q1_hex_lattice_kernel<TX, TY, TZ, true><<<n_tiles, TILE_THREADS, LT::BYTES, c->stream>>>(T);
   else
     assemble_q1_hex_lattice_kernel<TX, TY, TZ, false><<<n_tiles, TILE_THREADS, LT::BYTES, c->stream>>>(T);
@@ -1574,6 +1750,39 @@ int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k) {
       L.std_ok = h;
     }
   }
+  return PYN_OK;
+}
+
+// Rectilinear lattice?  Once per mesh (Lattice::rect, -1 not checked), and only for a mesh whose elements are all parallelepipeds:
+// the candidate axis tables are built into a local buffer, every local node is compared with them, and the tables are committed
+// to the context only when no node differs.  One read of xyz.
+static int pyn_lattice_axes_ensure(pyn_ctx* c, const AsmKnobs& k) {
+  Lattice& L = c->lat;
+  if (L.rect >= 0) return PYN_OK;
+  if (!L.valid || c->mesh_affine != 1) return PYN_OK;   // (mesh_affine not checked yet: ask again later)
+  const BoxLattice& B = c->box;
+  const int ns = lat_axis_slots(B.NX) + lat_axis_slots(B.NY) + lat_axis_slots(B.npl);
+  const int64_t n_node = (int64_t)B.npl * B.NX * B.NY;
+  if (n_node != c->n_node) {   // nodes outside the lattice's planes: not this variant's mesh
+    L.rect = 0;
+    return PYN_OK;
+  }
+  DevBuf<double> tab;
+  DevTmp flag;
+  PYN_HIP(tab.alloc(ns));
+  PYN_HIP(flag.alloc(sizeof(int)));
+  const int one = 1;
+  PYN_HIP(hipMemcpyAsync(flag.get(), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  LatArgs Tc;
+  lat_fill(c, k, Tc);
+  lattice_axes_extract_kernel<<<(ns + 255) / 256, 256, 0, c->stream>>>(Tc, tab);
+  lattice_axes_check_kernel<<<(int)((n_node + 255) / 256), 256, 0, c->stream>>>(Tc, tab, n_node, flag.as<int>());
+  PYN_HIP(hipGetLastError());
+  int h = 0;
+  PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  PYN_HIP(hipStreamSynchronize(c->stream));
+  if (h) L.d_axes = std::move(tab);
+  L.rect = h ? 1 : 0;
   return PYN_OK;
 }
 
@@ -1657,19 +1866,35 @@ int pyn_assemble_lattice(pyn_ctx* c, AsmRequest& rq, const AsmKnobs& k, const As
   T.rcrow = rq.rcrow;
   T.dinv = P.dinv ? rq.dinv : nullptr;   // the store phases see whole rows: 1 / diagonal leaves with them (no diag_kernel pass)
   rq.dinv_written = T.dinv != nullptr;
+  // The table variant of the parallelepiped tile kernel, decided here as the closed form is: a rectilinear mesh, unless switched off
+  // (PYNAMA_LATTICE_ABLATE=32 keeps its meaning: the kernel that loads coordinates, with the loads cut out).
+  const bool tiles_closed = P.kind == AK_LATTICE && P.k_closed;
+  if (tiles_closed && !k.no_lattice_axes && k.lattice_ablate != 32) {
+    PYN_TRY(pyn_lattice_axes_ensure(c, k));
+    if (c->lat.rect == 1) {
+      T.axX = c->lat.d_axes;
+      T.axY = T.axX + lat_axis_slots(T.nx);
+      T.axZ = T.axY + lat_axis_slots(T.ny);
+    }
+  }
+  PYN_CHECK(!k.lattice_axes_require || T.axX,
+            "PYNAMA_LATTICE_AXES_REQUIRE: the axis-table variant of the lattice tile kernel does not apply (%s)",
+            !tiles_closed ? "not the parallelepiped tile kernel" : k.no_lattice_axes || k.lattice_ablate == 32 ? "switched off"
+                                                                                                              : "mesh not rectilinear");
+  if (k.lattice_ablate == 64) T.bcmask = nullptr;   // diagnostics: no Dirichlet flag loads (timing only: imposed rows come out wrong)
   if (P.kind == AK_MARCH) return pyn_assemble_lattice_march(c, k, &T, P.shape);
-  const bool affine = P.k_closed;
+  const bool affine = P.k_closed, tilebc = !k.no_lattice_tilebc;
   switch (P.shape) {
-    case 1: return launch_lattice<7, 7, 7>(c, T, affine);
-    case 2: return launch_lattice<6, 6, 6>(c, T, affine);
-    case 3: return launch_lattice<8, 6, 6>(c, T, affine);
-    case 4: return launch_lattice<7, 6, 6>(c, T, affine);
-    case 5: return launch_lattice<6, 6, 4>(c, T, affine);
-    case 6: return launch_lattice<6, 5, 5>(c, T, affine);
-    case 7: return launch_lattice<7, 4, 4>(c, T, affine);
-    case 8: return launch_lattice<14, 3, 3>(c, T, affine);
-    case 9: return launch_lattice<7, 5, 5>(c, T, affine);
-    default: return launch_lattice<7, 5, 4>(c, T, affine);
+    case 1: return launch_lattice<7, 7, 7>(c, T, affine, tilebc);
+    case 2: return launch_lattice<6, 6, 6>(c, T, affine, tilebc);
+    case 3: return launch_lattice<8, 6, 6>(c, T, affine, tilebc);
+    case 4: return launch_lattice<7, 6, 6>(c, T, affine, tilebc);
+    case 5: return launch_lattice<6, 6, 4>(c, T, affine, tilebc);
+    case 6: return launch_lattice<6, 5, 5>(c, T, affine, tilebc);
+    case 7: return launch_lattice<7, 4, 4>(c, T, affine, tilebc);
+    case 8: return launch_lattice<14, 3, 3>(c, T, affine, tilebc);
+    case 9: return launch_lattice<7, 5, 5>(c, T, affine, tilebc);
+    default: return launch_lattice<7, 5, 4>(c, T, affine, tilebc);
   }
 }
 

@@ -541,6 +541,10 @@ __global__ void box_xyz_kernel(BoxArgs B, double* __restrict__ xyz) {
 static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
   // first drop what belonged to the old mesh, so that a refusal below leaves nothing of it behind:
   c->mesh_affine = -1;
+  c->lat.rect = -1;               // the axis tables of a rectilinear lattice belong to the old coordinates
+  c->lat.d_axes.reset();
+  c->lat.d_tilebc.reset();        // ... and the Dirichlet map of its tiles to the old lattice
+  c->lat.tilebc_stamp = -1;
   for (int k = 0; k < PYN_MATFREE_SLOTS; ++k) {   // the matrix-free operators
     c->mf_mask[k].reset();
     c->mf_set[k] = false;

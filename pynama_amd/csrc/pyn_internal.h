@@ -241,6 +241,11 @@ struct Lattice {
   bool std_shape = false;      // ids follow the slab numbering: owned planes, ghost planes below, ghost planes above (one rank, or a rank's slab)
   int std_ok = -1;             // closed-form row offsets verified against the graph (-1: not checked yet)
   DevBuf<int32_t> d_zord;      // [npl]: count | (dz+1) codes of the z-neighbour planes sorted by node id
+  int rect = -1;               // rectilinear: node (i, j, plane k) at (X[i], Y[j], Z[k]) bit for bit (-1: not checked yet; reset with the mesh)
+  DevBuf<double> d_axes;       // ... its axis tables X | Y | Z, each with guard slots (lat_axis_slots, pyn_lattice.h); set iff rect == 1
+  DevBuf<uint32_t> d_tilebc;   // one bit per tile of the scalar tile kernel: its node box holds an imposed node ...
+  int64_t tilebc_stamp = -1;   // ... for this Dirichlet set (pyn_ctx::bc_stamp)
+  int tilebc_shape = -1;       // ... and this tile shape (TX << 16 | TY << 8 | TZ)
 };
 
 // View of orders ngl 2 and 3 (pyn_assemble_ho3.hip: row-run assembly; ngl 3, the order all of the reference's cases run,
@@ -572,10 +577,15 @@ constexpr int PYN_HO3_MAX_TERMS = 32;   // operator terms the row-run kernels ca
   I(kle_lattice_tile, "PYNAMA_KLE_LATTICE_TILE", -1) I(march_zlen, "PYNAMA_MARCH_ZLEN", -1) I(ho3_run, "PYNAMA_HO3_RUN", 0)     \
   I(ho3_wgs_per_cu, "PYNAMA_HO3_WGS_PER_CU", -1) I(ho3_grid, "PYNAMA_HO3_GRID", -1) I(kle_ablate, "PYNAMA_KLE_ABLATE", 0)       \
   I(tiled_ablate, "PYNAMA_TILED_ABLATE", 0) I(ho3_ablate, "PYNAMA_HO3_ABLATE", 0)
+// PYN_ASM_LAUNCH_KNOBS: switches of a launcher that asm_choose never sees (the variant is decided inside the launcher, as AFF is), so
+// they are read with the others but are no part of the exported chooser's knob array (pyn_assemble_choose_layout).
+#define PYN_ASM_LAUNCH_KNOBS(F, I) F(no_lattice_axes, "PYNAMA_NO_LATTICE_AXES") F(lattice_axes_require, "PYNAMA_LATTICE_AXES_REQUIRE") \
+  F(no_lattice_tilebc, "PYNAMA_NO_LATTICE_TILEBC")
 struct AsmKnobs {
 #define PYN_F(f, e) bool f = false;
 #define PYN_I(f, e, d) int f = d;
   PYN_ASM_KNOBS(PYN_F, PYN_I)
+  PYN_ASM_LAUNCH_KNOBS(PYN_F, PYN_I)
 #undef PYN_F
 #undef PYN_I
 };

@@ -4,6 +4,7 @@
 #pragma once
 #include "pyn_internal.h"
 #include "pyn_q1_hex.h"
+#include "pyn_lattice_axes.h"
 
 namespace {
 
@@ -31,7 +32,8 @@ struct LatArgs {
                            // come from arithmetic (no index loads at all)
   int lean;                // the uploaded tables are the standard 2x2x2 Gauss tables: closed-form element routine (q1_laplace_lean)
   int ablate;              // diagnostics (PYNAMA_LATTICE_ABLATE): 1 no element phase, 4 no plain-tile store path, 16 boundary columns of the march through the CSR-slot decode,
-                           // 6 round-robin instead of XCD-contiguous tile order
+                           // 6 round-robin instead of XCD-contiguous tile order, 32 no coordinate loads (a fixed cube), 64 no Dirichlet flag loads
+                           // (timing only, like 32: the launcher hands the tile kernels a null mask)
   TileArgs q;              // quadrature tables (w, hrs, hcoo, aff) -- only those fields are used
   double* A;
   double* Arhs;
@@ -41,6 +43,13 @@ struct LatArgs {
   const int32_t* rcrow = nullptr;      // Arhs is a COMPACT imposed-column matrix: first block of every owned node row in it, -1 = not stored
                                        // (honoured by the KLE lattice kernels; the scalar kernels are never handed a compact target)
   unsigned long long* dbg = nullptr;   // diagnostics (PYNAMA_MARCH_STAMPS): per-phase s_memtime stamps of the marching kernels
+  // RECTILINEAR lattice (node (i, j, plane k) sits at (X[i], Y[j], Z[k]), checked bit for bit once per mesh): the three axis
+  // tables, each pointing at its first guard slot -- ax[i + LAT_AX_LO] is the coordinate of lattice index i.  Null: not rectilinear
+  // (or PYNAMA_NO_LATTICE_AXES); only the scalar tile kernel's table variant reads them.
+  const double *axX = nullptr, *axY = nullptr, *axZ = nullptr;
+  // ... and, for the current Dirichlet set and THIS launch's tile shape, one bit per tile (index bx + ntx (by + nty bz)): the tile's node
+  // box holds an imposed node.  A clear bit: the tile loads no flag bytes.  Null: no map (every tile loads its flags, as ever).
+  const uint32_t* tilebc = nullptr;
 };
 
 template <int TX, int TY, int TZ>
@@ -101,8 +110,10 @@ struct LatMeta {
   int r[NRW];
 };
 
+// no_flags (wave-uniform): the caller knows that no node of the box is imposed (LatArgs::tilebc) -- no flag loads, f = 0
 template <int TX, int TY, int TZ, int NT, int NDOF = 1>
-__device__ __forceinline__ void lat_meta_load(const LatArgs& T, int x0, int y0, int z0, int t, LatMeta<TX, TY, TZ, NT>& M) {
+__device__ __forceinline__ void lat_meta_load(const LatArgs& T, int x0, int y0, int z0, int t, LatMeta<TX, TY, TZ, NT>& M,
+                                              bool no_flags = false) {
   using L = LatTile<TX, TY, TZ>;
   const int nx = T.nx, ny = T.ny;
 #pragma unroll
@@ -110,7 +121,7 @@ __device__ __forceinline__ void lat_meta_load(const LatArgs& T, int x0, int y0, 
     const int i = t + j * NT;
     const int qx = i % L::BX, qy = (i / L::BX) % L::BY, qz = i / (L::BX * L::BY);
     const int x = x0 - 1 + qx, y = y0 - 1 + qy, pl = T.p_own0 + z0 - 1 + qz;
-    const bool ok = T.bcmask && i < L::NB && x >= 0 && x < nx && y >= 0 && y < ny && pl >= 0 && pl < T.npl;
+    const bool ok = !no_flags && T.bcmask && i < L::NB && x >= 0 && x < nx && y >= 0 && y < ny && pl >= 0 && pl < T.npl;
     unsigned char f = 0;   // bit q: DOF q of the node imposed
     if (ok) {
       const int64_t node = lat_plane(T, pl) + y * nx + x;
