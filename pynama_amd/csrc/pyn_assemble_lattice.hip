@@ -298,6 +298,30 @@ __global__ void lattice_axes_check_kernel(LatArgs T, const double* __restrict__ 
   if (!same) *flag = 0;
 }
 
+// ... and the 1-D P1 stiffness / mass tables of the three axes out of the candidate axis tables (pyn_lattice_rows.h: six doubles per
+// node and axis, x | y | z behind the axis tables): coordinates only, committed with them
+__global__ void lattice_rows_tables_kernel(LatArgs T, double* __restrict__ tab) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= T.nx + T.ny + T.npl) return;
+  const int sx = lat_axis_slots(T.nx), sy = lat_axis_slots(T.ny);
+  const double* c = tab + LAT_AX_LO;
+  int i = s, n = T.nx;
+  if (s >= T.nx + T.ny) {
+    c += sx + sy;
+    i = s - T.nx - T.ny;
+    n = T.npl;
+  } else if (s >= T.nx) {
+    c += sx;
+    i = s - T.nx;
+    n = T.ny;
+  }
+  double km[6];
+  lat_rows_km(c, i, n, km);
+  double* out = tab + lat_rows_tab_base(T.nx, T.ny, T.npl) + 6 * (int64_t)s;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) out[j] = km[j];
+}
+
 
 // ---- once per Dirichlet set and tile shape: which tiles hold an imposed node in their node box?  (lattice_tilebc_ensure)
 // One wave per tile scans the flags of exactly the nodes lat_meta_load would load (the node box clipped to the local lattice, ghost
@@ -366,6 +390,143 @@ __global__ void __launch_bounds__(TILE_THREADS, AFF ? 3 : 2) assemble_q1_hex_lat
     lat_store_plain<TX, TY, TZ>(T, acc, rlo, tid, TILE_THREADS);
   else
     lat_store<TX, TY, TZ>(T, x0, y0, acc, rlo, zrd, nbc, tid, TILE_THREADS);
+}
+
+// ---- rectilinear lattice: CSR rows straight from the 1-D tables
+// On a rectilinear lattice the 2x2x2 rule is exact and A = Kx (x) My (x) Mz + Mx (x) Ky (x) Mz + Mx (x) My (x) Kz, so entry
+// (row (x, y, pl), column (x + dx, y + dy, pl + dz)) is Kx[x][dx] a + Mx[x][dx] b with a = My Mz, b = Ky Mz + My Kz of the
+// neighbouring line (dy, dz): no element work, no LDS accumulators, no atomics.  One workgroup per x-line (y, owned plane): its nx
+// rows are ONE contiguous run of cy cz (3 nx - 2) values, written front to back, one double per lane and instruction.
+// The store loop is VALU-bound before it is store-bound (a wave64 instruction takes four cycles), so nothing in it divides,
+// multiplies integers or loads from global memory (on this part a load's wait also waits for the stores in front of it): every
+// lane-varying operand comes out of LDS, staged once per line in the order of the line's slot groups t = kz cy + ky
+// (pyn_lattice_rows.h) -- (a, b)[t], the x axis' (K1, M1) pairs, and the Dirichlet flags of the cc neighbouring x-lines, clipped at
+// the lattice faces (fl[t][x + 1], one zero byte at either end) -- and a lane walks its entries by additions (lat_rows_step).
+// A wave whose 64 entries meet no flag stores v as it is; the others route as lat_store_rows does.  km: the (K1, M1) tables, x | y | z.
+// Everything a workgroup reads is requested up front: all loads in flight together, one wait, one barrier.  NL consecutive lines of
+// one plane per workgroup share that phase and the x axis' pairs; measured, one line per 256 threads is the fastest shape
+// (PYNAMA_LATTICE_ROWS_LINES / _THREADS keep the others for tools/lattice_rows_ab.py).
+static size_t lat_rows_lds(int nx, int NL) {   // (a, b)[NL][9] | the x axis' pairs [nx][3] | flag bytes [NL][9][nx + 2]
+  return (size_t)NL * 144 + (size_t)nx * 48 + (((size_t)NL * 9 * (nx + 2) + 15) & ~(size_t)15);
+}
+
+template <int NL, int NT>
+__global__ void __launch_bounds__(NT) assemble_q1_lattice_rows_kernel(LatArgs T, const double* __restrict__ km) {
+  extern __shared__ __align__(16) double lds[];
+  double2* ab = reinterpret_cast<double2*>(lds);
+  double2* skx = ab + NL * 9;                                       // [nx][3]: (K1, M1) of (x, dx + 1)
+  unsigned char* fl = reinterpret_cast<unsigned char*>(skx + 3 * T.nx);
+  const int tid = threadIdx.x, nx = T.nx, ny = T.ny, W = nx + 2;
+  const int b = xcd_contiguous_tile(blockIdx.x, gridDim.x);   // neighbouring lines (shared flags, the partial 128-B lines at run ends) in one L2
+  const int ngy = (ny + NL - 1) / NL;
+  const int y0 = (b % ngy) * NL, zo = b / ngy, pl = T.p_own0 + zo;
+  const int nl = min(NL, ny - y0);
+  const int zcode = lat_zcode(T, pl), cz = zcode & 3;
+  const double2* __restrict__ kmx = reinterpret_cast<const double2*>(km);
+  const double2* __restrict__ kmy = kmx + 3 * nx;
+  const double2* __restrict__ kmz = kmy + 3 * ny;
+  // ---- staging: every load of a pass is unconditional (clamped addresses, the result masked afterwards), so that all of them are
+  // in flight before the first wait.  A pass covers 1024 of the x axis' pairs and 256 bytes of every flag row: one pass up to 254 nodes
+  // first node of flag row (l, s), computed by lane l 9 + s of every wave and handed round as a scalar (a slot group or a line
+  // that does not exist: a neighbouring one again, masked when the line is written)
+  int rowoff;
+  {
+    const int q = min(tid & 63, NL * 9 - 1), l = q / 9, s = q - l * 9;
+    const int y = min(y0 + l, ny - 1), cy = 3 - (y == 0) - (y == ny - 1);
+    int dy, dz;
+    lat_rows_group(min(s, cy * cz - 1), cy, y != 0, zcode, dy, dz);
+    rowoff = lat_plane(T, pl + dz) + (y + dy) * nx;
+  }
+  const int npass = max((3 * nx + 4 * NT - 1) / (4 * NT), (W + NT - 1) / NT);
+  for (int pass = 0; pass < npass; ++pass) {
+    double2 r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = kmx[min((pass * 4 + j) * NT + tid, 3 * nx - 1)];
+    const int i = pass * NT + tid;
+    unsigned char f[NL][9];
+    if (T.bcmask) {   // (wave-uniform)
+      const int xi = min(max(i - 1, 0), nx - 1);
+#pragma unroll
+      for (int l = 0; l < NL; ++l)
+#pragma unroll
+        for (int s = 0; s < 9; ++s) f[l][s] = T.bcmask[(int64_t)__builtin_amdgcn_readlane(rowoff, l * 9 + s) + xi];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int q = (pass * 4 + j) * NT + tid;
+      if (q < 3 * nx) skx[q] = r[j];
+    }
+    if (i < W) {
+      const bool inx = T.bcmask && i >= 1 && i <= nx;
+#pragma unroll
+      for (int l = 0; l < NL; ++l)
+#pragma unroll
+        for (int s = 0; s < 9; ++s) fl[(l * 9 + s) * W + i] = (inx && f[l][s] != 0) ? 1 : 0;
+    }
+  }
+  if (tid < NL * 9) {
+    const int l = tid / 9, t = tid - l * 9, y = y0 + l;
+    const int cy = 3 - (y == 0) - (y == ny - 1);
+    if (l < nl && t < cy * cz) {
+      int dy, dz;
+      lat_rows_group(t, cy, y != 0, zcode, dy, dz);
+      const double2 fy = kmy[y * 3 + dy + 1], fz = kmz[pl * 3 + dz + 1];
+      ab[tid] = make_double2(fy.y * fz.y, fma(fy.x, fz.y, fy.y * fz.x));
+    }
+  }
+  __syncthreads();
+  // ---- the lines, one after the other
+  for (int l = 0; l < nl; ++l) {
+    const int y = y0 + l, cy = 3 - (y == 0) - (y == ny - 1), cc = cy * cz;
+    const int tself = ((zcode >> 2) & 3) == 1 ? (y != 0) : cy + (y != 0);   // the line's own slot group: dz = 0 is kz = 0 or 1
+    const double2* abl = ab + l * 9;
+    const unsigned char* fll = fl + l * 9 * W;
+    const int64_t base = T.std_lat ? lat_rowptr_std(T, 0, y, zo) : T.rowptr[(int64_t)T.P[pl] + (int64_t)y * nx];
+    double* __restrict__ outA = T.A + base;
+    double* __restrict__ outR = T.Arhs ? T.Arhs + base : nullptr;
+    const bool zeros = outR && !T.rhs_clean;   // Arhs zeros have to be written (a clean target holds them already)
+    const int len = lat_rows_line_len(nx, cy, cz), nint = lat_rows_interior_len(nx, cc);
+    const unsigned char* fself = fll + tself * W + 1;
+    // the rows x = 1 .. nx - 2
+    if (tid < nint) {
+      const LatRowsStride st = lat_rows_stride(NT, cc);
+      LatRowsPos p = lat_rows_interior(tid, cc, lat_rows_magic(cc));
+      double* __restrict__ pA = outA + 2 * cc;
+      double* __restrict__ pR = outR ? outR + 2 * cc : nullptr;
+      for (int m = tid; m < nint; m += NT) {
+        const double2 k = skx[__mul24(p.x, 3) + p.kx], c = abl[p.t];
+        const unsigned fr = fself[p.x], fc = fll[__mul24(p.t, W) + p.x + p.kx];   // (24-bit products: full rate)
+        const double v = fma(k.x, c.x, k.y * c.y);
+        if (!__any(fr | fc)) {
+          pA[m] = v;
+          if (zeros) pR[m] = 0.0;
+        } else {
+          const double idv = (p.t == tself && p.kx == 1) ? 1.0 : 0.0;
+          pA[m] = fr ? idv : (fc ? 0.0 : v);
+          if (pR) pR[m] = fr ? idv : (fc ? -v : 0.0);
+        }
+        lat_rows_step(p, st, cc);
+      }
+    }
+    // the rows x = 0 and x = nx - 1 (two columns per neighbouring line)
+    if (tid < 4 * cc) {
+      const LatRowsEnd r = lat_rows_end(tid, nx, cc, len);
+      const double2 k = skx[3 * r.x + r.dx + 1], c = abl[r.t];
+      const unsigned fr = fself[r.x], fc = fll[r.t * W + r.x + r.dx + 1];
+      const double v = fma(k.x, c.x, k.y * c.y);
+      const double idv = (r.t == tself && r.dx == 0) ? 1.0 : 0.0;
+      outA[r.e] = fr ? idv : (fc ? 0.0 : v);
+      if (outR && (zeros || fr || fc)) outR[r.e] = fr ? idv : (fc ? -v : 0.0);
+    }
+    if (T.dinv) {   // 1 / diagonal of the line's rows, one lane per row: the diagonal entry is recomputed (the same two products)
+      const double2 c = abl[tself];
+      double* __restrict__ dv = T.dinv + ((int64_t)zo * ny + y) * nx;
+      for (int x = tid; x < nx; x += NT) {
+        const double2 k = skx[x * 3 + 1];
+        dv[x] = fself[x] ? 1.0 : 1.0 / fma(k.x, c.x, k.y * c.y);
+      }
+    }
+  }
 }
 
 // y_e = L_e x_e for a parallelepiped WITHOUT forming L_e: in the Haar basis of each axis ((v0, v1) -> (s, d) = (v0 + v1,
@@ -1755,7 +1916,8 @@ int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k) {
 
 // Rectilinear lattice?  Once per mesh (Lattice::rect, -1 not checked), and only for a mesh whose elements are all parallelepipeds:
 // the candidate axis tables are built into a local buffer, every local node is compared with them, and the tables are committed
-// to the context only when no node differs.  One read of xyz.
+// to the context only when no node differs.  One read of xyz.  The 1-D stiffness / mass tables of the rows kernel are built behind
+// them in the same buffer (coordinates only: same lifetime, reset by pyn_mesh_set).
 static int pyn_lattice_axes_ensure(pyn_ctx* c, const AsmKnobs& k) {
   Lattice& L = c->lat;
   if (L.rect >= 0) return PYN_OK;
@@ -1769,7 +1931,7 @@ static int pyn_lattice_axes_ensure(pyn_ctx* c, const AsmKnobs& k) {
   }
   DevBuf<double> tab;
   DevTmp flag;
-  PYN_HIP(tab.alloc(ns));
+  PYN_HIP(tab.alloc((size_t)lat_rows_tab_base(B.NX, B.NY, B.npl) + lat_rows_tab_doubles(B.NX, B.NY, B.npl)));   // + the (K1, M1) tables of the rows kernel
   PYN_HIP(flag.alloc(sizeof(int)));
   const int one = 1;
   PYN_HIP(hipMemcpyAsync(flag.get(), &one, sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -1777,12 +1939,25 @@ static int pyn_lattice_axes_ensure(pyn_ctx* c, const AsmKnobs& k) {
   lat_fill(c, k, Tc);
   lattice_axes_extract_kernel<<<(ns + 255) / 256, 256, 0, c->stream>>>(Tc, tab);
   lattice_axes_check_kernel<<<(int)((n_node + 255) / 256), 256, 0, c->stream>>>(Tc, tab, n_node, flag.as<int>());
+  lattice_rows_tables_kernel<<<(B.NX + B.NY + B.npl + 255) / 256, 256, 0, c->stream>>>(Tc, tab);
   PYN_HIP(hipGetLastError());
   int h = 0;
   PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
   PYN_HIP(hipStreamSynchronize(c->stream));
   if (h) L.d_axes = std::move(tab);
   L.rect = h ? 1 : 0;
+  return PYN_OK;
+}
+
+// rows kernel of a rectilinear lattice (c->lat.rect == 1): one workgroup per NL consecutive x-lines of an owned plane
+template <int NL, int NT>
+static int launch_lattice_rows(pyn_ctx* c, LatArgs& T) {
+  const size_t lds = lat_rows_lds(T.nx, NL);
+  const int64_t n_groups = (int64_t)((T.ny + NL - 1) / NL) * T.n_own;
+  PYN_CHECK(n_groups > 0 && n_groups < (int64_t)INT32_MAX, "lattice rows kernel: %lld workgroups", (long long)n_groups);
+  const double* km = c->lat.d_axes.get() + lat_rows_tab_base(T.nx, T.ny, T.npl);
+  assemble_q1_lattice_rows_kernel<NL, NT><<<(int)n_groups, NT, lds, c->stream>>>(T, km);
+  PYN_HIP(hipGetLastError());
   return PYN_OK;
 }
 
@@ -1881,6 +2056,29 @@ int pyn_assemble_lattice(pyn_ctx* c, AsmRequest& rq, const AsmKnobs& k, const As
             "PYNAMA_LATTICE_AXES_REQUIRE: the axis-table variant of the lattice tile kernel does not apply (%s)",
             !tiles_closed ? "not the parallelepiped tile kernel" : k.no_lattice_axes || k.lattice_ablate == 32 ? "switched off"
                                                                                                               : "mesh not rectilinear");
+  // The rows kernel, decided here too (the plan record stays AK_LATTICE, shape 0, closed form): a rectilinear mesh and no request
+  // for a tile shape, an ablation or one of the tile kernel's own variants.
+  int rows_nl = k.lattice_rows_lines == 2 ? 2 : 1;                                 // x-lines per workgroup ...
+  while (rows_nl > 1 && lat_rows_lds(T.nx, rows_nl) > 64 * 1024) rows_nl /= 2;                       // ... that fit the LDS
+  const char* no_rows = !tiles_closed                                                                ? "not the parallelepiped tile kernel"
+                        : k.no_lattice_rows                                                          ? "switched off"
+                        : k.lattice_tile >= 0                                                        ? "PYNAMA_LATTICE_TILE asks for a tile shape"
+                        : k.lattice_ablate != 0                                                      ? "PYNAMA_LATTICE_ABLATE is set"
+                        : k.no_lattice_axes || k.lattice_axes_require || k.no_lattice_tilebc         ? "a switch of the tile kernel's variants is set"
+                        : rq.rcrow                                                                   ? "compact Arhs"
+                        : c->lat.rect != 1                                                           ? "mesh not rectilinear"
+                        : lat_rows_lds(T.nx, rows_nl) > 64 * 1024                                            ? "x-lines too long for the LDS staging"
+                                                                                                     : nullptr;
+  PYN_CHECK(!k.lattice_rows_require || !no_rows, "PYNAMA_LATTICE_ROWS_REQUIRE: the rows kernel of rectilinear lattices does not apply (%s)",
+            no_rows);
+  if (!no_rows) {
+    if (rows_nl == 2) return launch_lattice_rows<2, 256>(c, T);
+    switch (k.lattice_rows_threads) {
+      case 128: return launch_lattice_rows<1, 128>(c, T);
+      case 512: return launch_lattice_rows<1, 512>(c, T);
+      default: return launch_lattice_rows<1, 256>(c, T);
+    }
+  }
   if (k.lattice_ablate == 64) T.bcmask = nullptr;   // diagnostics: no Dirichlet flag loads (timing only: imposed rows come out wrong)
   if (P.kind == AK_MARCH) return pyn_assemble_lattice_march(c, k, &T, P.shape);
   const bool affine = P.k_closed, tilebc = !k.no_lattice_tilebc;

@@ -580,7 +580,9 @@ constexpr int PYN_HO3_MAX_TERMS = 32;   // operator terms the row-run kernels ca
 // PYN_ASM_LAUNCH_KNOBS: switches of a launcher that asm_choose never sees (the variant is decided inside the launcher, as AFF is), so
 // they are read with the others but are no part of the exported chooser's knob array (pyn_assemble_choose_layout).
 #define PYN_ASM_LAUNCH_KNOBS(F, I) F(no_lattice_axes, "PYNAMA_NO_LATTICE_AXES") F(lattice_axes_require, "PYNAMA_LATTICE_AXES_REQUIRE") \
-  F(no_lattice_tilebc, "PYNAMA_NO_LATTICE_TILEBC")
+  F(no_lattice_tilebc, "PYNAMA_NO_LATTICE_TILEBC") F(no_lattice_rows, "PYNAMA_NO_LATTICE_ROWS")                                      \
+  F(lattice_rows_require, "PYNAMA_LATTICE_ROWS_REQUIRE") I(lattice_rows_lines, "PYNAMA_LATTICE_ROWS_LINES", 0)               \
+  I(lattice_rows_threads, "PYNAMA_LATTICE_ROWS_THREADS", 0)
 struct AsmKnobs {
 #define PYN_F(f, e) bool f = false;
 #define PYN_I(f, e, d) int f = d;

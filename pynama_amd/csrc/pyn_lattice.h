@@ -5,6 +5,7 @@
 #include "pyn_internal.h"
 #include "pyn_q1_hex.h"
 #include "pyn_lattice_axes.h"
+#include "pyn_lattice_rows.h"
 
 namespace {
 
@@ -67,20 +68,14 @@ struct LatTile {
 template <bool STD = false>   // STD: the caller has checked T.std_lat (no index loads compiled in)
 __device__ __forceinline__ int lat_plane(const LatArgs& T, int j) {
   if (!STD && !T.std_lat) return T.P[j];
-  const int pp = T.nx * T.ny, lo = T.p_own0, hi = T.p_own0 + T.n_own;
-  if (j < lo) return (T.n_own + j) * pp;
-  if (j >= hi) return (T.n_own + lo + (j - hi)) * pp;
-  return (j - lo) * pp;
+  return lat_rows_plane(T.nx, T.ny, T.p_own0, T.n_own, j);   // (pyn_lattice_rows.h: shared with the host check)
 }
 
 // CSR offset of the row of owned node (x, y, owned plane zo): rows in id order, len = cx cy cz with c = 3 minus
 // the domain faces the node sits on (a slab interface is not a face: its ghost plane supplies the columns);
 // sum_{x' < x} cx(x') = 3x - (x > 0), sum over a whole line = 3 nx - 2.  Verified against the graph's rowptr.
 __device__ __forceinline__ int lat_rowptr_std(const LatArgs& T, int x, int y, int zo) {
-  const int sx = 3 * T.nx - 2, sy = 3 * T.ny - 2;
-  const bool bot = T.p_own0 == 0, top = T.p_own0 + T.n_own == T.npl;   // does the slab hold the domain's end planes?
-  const int cy = 3 - (y == 0) - (y == T.ny - 1), cz = 3 - (bot && zo == 0) - (top && zo == T.n_own - 1);
-  return (3 * zo - (bot && zo > 0)) * sy * sx + cz * ((3 * y - (y > 0)) * sx + cy * (3 * x - (x > 0)));
+  return lat_rows_rowptr(T.nx, T.ny, T.npl, T.p_own0, T.n_own, x, y, zo);
 }
 
 // z-order code of OWNED plane pl: the existing z-neighbours sorted by node id -- owned planes first (ascending),
@@ -88,16 +83,7 @@ __device__ __forceinline__ int lat_rowptr_std(const LatArgs& T, int x, int y, in
 template <bool STD = false>
 __device__ __forceinline__ int lat_zcode(const LatArgs& T, int pl) {
   if (!STD && !T.std_lat) return T.zord[pl];
-  const int lo = T.p_own0, hi = T.p_own0 + T.n_own;
-  const bool has_dn = pl > 0, has_up = pl < T.npl - 1;
-  const bool dn_ghost = has_dn && pl - 1 < lo, up_ghost = has_up && pl + 1 >= hi;
-  int code = 0, n = 0;
-  if (has_dn && !dn_ghost) code |= 0 << (2 + 2 * n++);
-  code |= 1 << (2 + 2 * n++);
-  if (has_up && !up_ghost) code |= 2 << (2 + 2 * n++);
-  if (dn_ghost) code |= 0 << (2 + 2 * n++);
-  if (up_ghost) code |= 2 << (2 + 2 * n++);
-  return code | n;
+  return lat_rows_zcode(T.npl, T.p_own0, T.n_own, pl);
 }
 
 // Row offsets and Dirichlet flags of a tile, in two steps so that their HBM latency hides behind the element
