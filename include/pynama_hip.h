@@ -403,15 +403,30 @@ int pyn_assemble_choose_layout(char* buf, int len);
  *                                                          or ghost nodes, n_elem * nn >= 2^31, tables that are not those rules or
  *                                                          whose geometry tables are not the multilinear corner basis, a cell with
  *                                                          det J <= 0 at a point of either rule ("non-positive Jacobian")
+ *   ANY quadrilateral / hexahedral mesh of order ngl 3      PYN_MATFREE_KLE_NGL3_GENERAL only: second-order lattices with bent cells and
+ *                                                          imported Gmsh meshes lifted to ngl 3 (any node numbering, cell order,
+ *                                                          orientation-preserving cell orientation and vertex valence), ONE rank (lane
+ *                                                          per tensor position = point of the Gauss(3) full rule, both rules by
+ *                                                          interpolation with the Jacobian formed at every point from the cell's
+ *                                                          corners, the gather pass of the general operator;
+ *                                                          pyn_matfree_ho3_general.hip).  Refused with a message: an order other than
+ *                                                          ngl 3 (ngl >= 4: PYN_MATFREE_KLE_GENERAL), several ranks or ghost nodes,
+ *                                                          n_elem * nn >= 2^31, tables that are not the Gauss(3) / Gauss(2) rules on the
+ *                                                          Lobatto(3) nodes or whose geometry tables are not the multilinear corner
+ *                                                          basis, a cell with det J <= 0 at a point of either rule ("non-positive
+ *                                                          Jacobian"), PYN_PC_MG in pyn_solve (the V-cycle keeps the assembled product)
  *   PYN_MATFREE_LAPLACE  the scalar Laplacian pyn_assemble_scalar(PYN_FORM_LAPLACE) builds (1 DOF per node)
  *   PYN_MATFREE_KLE      the K of pyn_assemble_kle (dim DOFs per node: 3 on Q1 hexahedra, 2 / 3 on second- and higher-order meshes);
  *                        alpha_d / alpha_w are that call's penalty weights (1e3 / 1e2 in the reference, spectral.py:152-153)
  *   PYN_MATFREE_KLE_GENERAL  the same K; its own operator id with its own snapshot (mask, alpha_d, alpha_w): on a box lattice of
  *                        affine cells both ids may be set on one context and stay independent
+ *   PYN_MATFREE_KLE_NGL3_GENERAL  the same K at order ngl 3; again an id and a snapshot of its own, next to PYN_MATFREE_KLE on a
+ *                        second-order lattice of affine cells.  The backend is chosen by the id, not by the mesh
  * pyn_matfree_set defines the operator from the mesh, the element tables and a SNAPSHOT of the current Dirichlet mask
  * (imposed rows identity, imposed columns eliminated, base_problem.py:531-549): call it next to the assembly it mirrors;
  * later pyn_bc_set calls do not change it. */
-enum { PYN_MATFREE_OFF = 0, PYN_MATFREE_LAPLACE = 1, PYN_MATFREE_KLE = 2, PYN_MATFREE_KLE_GENERAL = 3 };
+enum { PYN_MATFREE_OFF = 0, PYN_MATFREE_LAPLACE = 1, PYN_MATFREE_KLE = 2, PYN_MATFREE_KLE_GENERAL = 3,
+       PYN_MATFREE_KLE_NGL3_GENERAL = 4 };
 int pyn_matfree_set(pyn_ctx* ctx, int op, double alpha_d, double alpha_w);
 int pyn_matfree_apply(pyn_ctx* ctx, int op, int x_vec, int y_vec);
 typedef struct pyn_solve_opts {

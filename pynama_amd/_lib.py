@@ -20,7 +20,7 @@ CSRC = os.path.join(_HERE, "csrc")
 Q_FULL, Q_RED, Q_NODAL = 0, 1, 2
 FORM_LAPLACE, FORM_MASS_NODAL, FORM_MASS_FULL, FORM_KLE, FORM_OPERATOR = 0, 1, 2, 3, 4
 KSP_CG, KSP_GMRES = 0, 1
-MATFREE_OFF, MATFREE_LAPLACE, MATFREE_KLE, MATFREE_KLE_GENERAL = 0, 1, 2, 3
+MATFREE_OFF, MATFREE_LAPLACE, MATFREE_KLE, MATFREE_KLE_GENERAL, MATFREE_KLE_NGL3_GENERAL = 0, 1, 2, 3, 4
 PC_NONE, PC_JACOBI, PC_MG = 0, 1, 2
 MG_MAX_LEVELS = 16
 TS_MAX_STAGES = 8
@@ -711,11 +711,14 @@ class Context:
     def matfree_apply(self, x, y, op=1):
         """y = A x without an assembled matrix (op: MATFREE_LAPLACE scalar, structured Q1 hex meshes; MATFREE_KLE dim DOFs per
         node: structured Q1 hex meshes, second-order lattices of affine cells, box lattices of affine cells of order ngl 4..12
-        in 2-D / 4..8 in 3-D; MATFREE_KLE_GENERAL the same K on any quadrilateral / hexahedral mesh of those orders, one rank)"""
+        in 2-D / 4..8 in 3-D; MATFREE_KLE_GENERAL the same K on any quadrilateral / hexahedral mesh of those orders, one rank;
+        MATFREE_KLE_NGL3_GENERAL the same K on any quadrilateral / hexahedral mesh of order ngl 3 -- bent cells, imported meshes --
+        on one rank)"""
         _check(self.lib.pyn_matfree_apply(self.h, op, x, y))
 
     def matfree_set(self, op=1, alpha_d=0.0, alpha_w=0.0):
-        """define the matrix-free operator from the mesh, the tables and a snapshot of the CURRENT Dirichlet mask"""
+        """define the matrix-free operator (a MATFREE_* id; each id keeps its own snapshot) from the mesh, the tables and a snapshot
+        of the CURRENT Dirichlet mask"""
         _check(self.lib.pyn_matfree_set(self.h, op, alpha_d, alpha_w))
 
     def matfree_kle_set(self, alpha_d, alpha_w):

@@ -1,5 +1,6 @@
-// What the matrix-free KLE kernels of orders ngl >= 4 share (pyn_matfree_ho.hip: box lattices of affine cells; pyn_matfree_ho_general.hip:
-// any quadrilateral / hexahedral mesh): the 1-D rules and tables of an order, the workgroup shape of the cell pass, the table upload.
+// What the matrix-free KLE kernels with a lane per node / point share (pyn_matfree_ho.hip: box lattices of affine cells at ngl >= 4;
+// pyn_matfree_ho_general.hip: any quadrilateral / hexahedral mesh at ngl >= 4; pyn_matfree_ho3_general.hip: any such mesh at ngl 3): the
+// 1-D rules and tables of an order, the workgroup shape of the cell pass, the table upload, the Jacobian of a multilinear cell at a point.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -130,6 +131,56 @@ struct HoCfg {
   static_assert(BLOCK <= 1024, "workgroup size");
 };
 
+// J[r][x] at the point xi of the cell with corners Xc[b][x], b = lattice bits (x the lowest); returns det J and Ji[x][r] = d xi_r / d x
+template <int DIM, class XP>
+__device__ __forceinline__ double hog_jac_inv(XP Xc, const double* xi, double (*Ji)[DIM]) {
+  double fm[DIM], fp[DIM], J[DIM][DIM];
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    fm[d] = 0.5 * (1.0 - xi[d]);
+    fp[d] = 0.5 * (1.0 + xi[d]);
+  }
+#pragma unroll
+  for (int r = 0; r < DIM; ++r)
+#pragma unroll
+    for (int x = 0; x < DIM; ++x) J[r][x] = 0.0;
+#pragma unroll
+  for (int b = 0; b < (1 << DIM); ++b)
+#pragma unroll
+    for (int r = 0; r < DIM; ++r) {
+      double dn = ((b >> r) & 1) ? 0.5 : -0.5;
+#pragma unroll
+      for (int e = 0; e < DIM; ++e)
+        if (e != r) dn *= ((b >> e) & 1) ? fp[e] : fm[e];
+#pragma unroll
+      for (int x = 0; x < DIM; ++x) J[r][x] = fma(dn, Xc[b * DIM + x], J[r][x]);
+    }
+  double det;
+  if constexpr (DIM == 2) {
+    det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
+    const double rr = 1.0 / det;
+    Ji[0][0] = J[1][1] * rr;
+    Ji[0][1] = -J[0][1] * rr;
+    Ji[1][0] = -J[1][0] * rr;
+    Ji[1][1] = J[0][0] * rr;
+  } else {
+    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1], c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
+    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+    det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
+    const double rr = 1.0 / det;
+    Ji[0][0] = c00 * rr;
+    Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * rr;
+    Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * rr;
+    Ji[1][0] = c01 * rr;
+    Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * rr;
+    Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * rr;
+    Ji[2][0] = c02 * rr;
+    Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * rr;
+    Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * rr;
+  }
+  return det;
+}
+
 }  // namespace pyn_ho
 
 // what pyn_matfree_set does for both operators of these orders (pyn_matfree_ho.hip): the uploaded rules against the tensor products of
@@ -140,3 +191,16 @@ int pyn_ho_tab_upload(pyn_ctx* c, const pyn_ho::HoTab1D& T);
 int pyn_hog_set(pyn_ctx* c);
 int pyn_hog_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);
 void pyn_hog_release(pyn_ctx* c);
+// what the two general operators share (pyn_matfree_ho_general.hip; `what` names the operator in the messages): a_of_t, the geometry
+// tables against the multilinear corner basis at the 1-D points of both rules, the device check of det J > 0 at the points
+// d_tab[tab_pts ...] (full rule [ngl], reduced rule [ngl - 1]), the node -> (cell, t) incidence list, the gather pass
+void pyn_hog_aoft(int ngl, int dim, std::vector<int32_t>& aoft);
+int pyn_hog_check_geometry_tables(pyn_ctx* c, const std::vector<double>& pts_full, const std::vector<double>& pts_red, const char* what);
+int pyn_hog_check_det(pyn_ctx* c, const int32_t* d_aoft, const double* d_tab, int tab_pts, const char* what, const char* where);
+int64_t pyn_hog_incidence_host(const int32_t* conn, int64_t n_elem, int nn, int64_t n_node, const int32_t* aoft, std::vector<int32_t>& ptr,
+                               std::vector<int32_t>& inc);
+int pyn_hog_incidence(pyn_ctx* c, const std::vector<int32_t>& aoft, const char* what, DevBuf<int32_t>& d_inc_ptr, DevBuf<int32_t>& d_inc);
+int pyn_hog_gather(pyn_ctx* c, const int32_t* inc_ptr, const int32_t* inc, const double* ye, const uint8_t* mask, const double* x, double* y,
+                   bool dot, int* grid_out);
+// the general operator of order ngl 3 (pyn_matfree_ho3_general.hip), its own backend (chosen by the id, pyn_krylov.hip)
+void pyn_h3g_release(pyn_ctx* c);

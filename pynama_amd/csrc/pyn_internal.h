@@ -273,7 +273,7 @@ struct Ho3MfBasis {
   int diag = 0;                // every cell's J^-1 is diagonal (axis-aligned boxes)
 };
 
-constexpr int PYN_MATFREE_SLOTS = PYN_MATFREE_KLE_GENERAL + 1;   // operator ids of include/pynama_hip.h
+constexpr int PYN_MATFREE_SLOTS = PYN_MATFREE_KLE_NGL3_GENERAL + 1;   // operator ids of include/pynama_hip.h
 constexpr int PYN_HO_MAX_NGL_2D = 12, PYN_HO_MAX_NGL_3D = 8;   // orders the matrix-free kernels are instantiated for
 
 struct SellShape {
@@ -391,6 +391,10 @@ struct pyn_ctx {
   DevBuf<int32_t> d_hog_aoft;         // [nn] local node at tensor position t (the inverse of mesh_local_lattice)
   DevBuf<int32_t> d_hog_inc_ptr;      // [n_node + 1] node -> (cell, t) incidence list in CSR form ...
   DevBuf<int32_t> d_hog_inc;          // ... [n_elem * nn] entries cell * nn + t, ascending within a row
+  // PYN_MATFREE_KLE_NGL3_GENERAL (pyn_matfree_ho3_general.hip), any quadrilateral / hexahedral mesh of order ngl 3: buffers of its own
+  DevBuf<double> d_h3g_tab;           // the 1-D tables of both rules: wf Bf Gf wr Br Gr xf xr
+  DevBuf<double> d_h3g_ye;            // the per-cell results between the two passes [n_elem][dim][nn]
+  DevBuf<int32_t> d_h3g_aoft, d_h3g_inc_ptr, d_h3g_inc;   // as d_hog_aoft, d_hog_inc_ptr, d_hog_inc
   // reference matrices of the ngl = 3 element in tensor (lattice) order, from the uploaded tables (pyn_elem_tables_set):
   // Tf / Tr[r][s][a][b] = sum_g w Hrs_r[a] Hrs_s[b] (full / reduced rule), Uf / Ur[r][a][b] = sum_g w H[a] Hrs_r[b]
   DevBuf<double> d_ho3_tabs;
@@ -514,6 +518,8 @@ int pyn_dense_lu_solve(pyn_ctx* c, const double* D, const int* piv, int64_t n, c
 // A matrix-free backend: the mesh family whose kernels apply the shell operators (PYN_MATFREE_*).  One static record per family, next
 // to its kernels: second-order lattices (pyn_matfree_ho3.hip), meshes of order ngl >= 4 (pyn_matfree_ho.hip: box lattices of affine
 // cells, and PYN_MATFREE_KLE_GENERAL on any mesh through pyn_matfree_ho_general.hip), Q1 lattices (pyn_assemble_lattice.hip).
+// PYN_MATFREE_KLE_NGL3_GENERAL has a backend of its own (pyn_matfree_ho3_general.hip) that is chosen by the operator id, not by the
+// mesh: a bent second-order lattice is owned by the ngl 3 backend, an imported ngl 3 mesh by none.
 struct MfBackend {
   bool (*owns)(const pyn_ctx* c);
   int (*set)(pyn_ctx* c, int op);        // the checks and tables of pyn_matfree_set
@@ -525,6 +531,7 @@ struct MfBackend {
 const MfBackend* pyn_mf_ho3();
 const MfBackend* pyn_mf_ho();
 const MfBackend* pyn_mf_q1();
+const MfBackend* pyn_mf_h3g();
 inline const MfBackend* pyn_matfree_backend(const pyn_ctx* c) { return pyn_mf_ho3()->owns(c) ? pyn_mf_ho3() : pyn_mf_ho()->owns(c) ? pyn_mf_ho() : pyn_mf_q1(); }
 
 // "apply A" of one solve (pyn_krylov.hip): the matrix-free shell or the matrix's product plan, resolved once by init.  No halo

@@ -678,9 +678,14 @@ extern "C" int pyn_spmv(pyn_ctx* c, int mat_id, int xv, int yv) {
 }
 
 // -----------------------------------------------------------------------------------------------
-// the backend of `op` on this mesh; only the backend of the orders ngl >= 4 knows PYN_MATFREE_KLE_GENERAL
+// the backend of `op` on this mesh; only the backend of the orders ngl >= 4 knows PYN_MATFREE_KLE_GENERAL, and
+// PYN_MATFREE_KLE_NGL3_GENERAL has the backend of pyn_matfree_ho3_general.hip on every mesh
 static int mf_backend_of(const pyn_ctx* c, int op, const MfBackend** mf) {
-  PYN_CHECK(op >= PYN_MATFREE_LAPLACE && op <= PYN_MATFREE_KLE_GENERAL, "unknown matrix-free operator %d", op);
+  PYN_CHECK(op >= PYN_MATFREE_LAPLACE && op <= PYN_MATFREE_KLE_NGL3_GENERAL, "unknown matrix-free operator %d", op);
+  if (op == PYN_MATFREE_KLE_NGL3_GENERAL) {   // by the id: its set says what it serves
+    *mf = pyn_mf_h3g();
+    return PYN_OK;
+  }
   *mf = pyn_matfree_backend(c);
   PYN_CHECK(op != PYN_MATFREE_KLE_GENERAL || *mf == pyn_mf_ho(),
             "general matrix-free KLE operator (PYN_MATFREE_KLE_GENERAL): serves quadrilateral / hexahedral meshes of order ngl 4..%d "
@@ -1383,7 +1388,10 @@ extern "C" int pyn_solve(pyn_ctx* c, int mat_id, int bv, int xv, const pyn_solve
   PYN_CHECK(opts->pc != PYN_PC_MG || opts->method == PYN_KSP_CG, "the multigrid preconditioner (PYN_PC_MG) runs with CG only, not GMRES");
   PYN_CHECK(opts->maxit > 0 || opts->fixed_iters > 0, "maxit must be positive");
   PYN_CHECK(!(c->nranks > 1 && c->detached), "detached communicator: the Krylov solve needs collectives");
-  PYN_CHECK(opts->matfree >= PYN_MATFREE_OFF && opts->matfree <= PYN_MATFREE_KLE_GENERAL, "unknown matrix-free operator %d", opts->matfree);
+  PYN_CHECK(opts->matfree >= PYN_MATFREE_OFF && opts->matfree <= PYN_MATFREE_KLE_NGL3_GENERAL, "unknown matrix-free operator %d", opts->matfree);
+  PYN_CHECK(!(opts->pc == PYN_PC_MG && opts->matfree == PYN_MATFREE_KLE_NGL3_GENERAL),
+            "the multigrid preconditioner (PYN_PC_MG) does not multiply with PYN_MATFREE_KLE_NGL3_GENERAL: solve with matfree = 0 "
+            "(the V-cycle keeps the assembled product) or with the Jacobi preconditioner");
   PYN_HIP(hipSetDevice(c->device));
   double* b = c->vecs[bv].d;
   double* x = c->vecs[xv].d;

@@ -560,6 +560,7 @@ void pyn_ho_view(pyn_ctx* c) {
   c->d_ho_tab.reset();   // the operator's tables and scratch belong to the mesh
   c->d_ho_ye.reset();
   pyn_hog_release(c);
+  pyn_h3g_release(c);
   const BoxLattice& B = c->box;
   c->ho_valid = B.valid && B.ngl >= 4 && B.ngl <= pyn_ho_matfree_max_ngl(B.dim) && B.plane() <= INT32_MAX / 4 && B.n_own >= 1 &&
                 c->n_elem < INT32_MAX && !getenv("PYNAMA_NO_HO_LATTICE");

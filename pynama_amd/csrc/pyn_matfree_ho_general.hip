@@ -35,56 +35,6 @@ struct HogArgs {
   double alpha_d, alpha_w;
 };
 
-// J[r][x] at the point xi of the cell with corners Xc[b][x], b = lattice bits (x the lowest); returns det J and Ji[x][r] = d xi_r / d x
-template <int DIM, class XP>
-__device__ __forceinline__ double hog_jac_inv(XP Xc, const double* xi, double (*Ji)[DIM]) {
-  double fm[DIM], fp[DIM], J[DIM][DIM];
-#pragma unroll
-  for (int d = 0; d < DIM; ++d) {
-    fm[d] = 0.5 * (1.0 - xi[d]);
-    fp[d] = 0.5 * (1.0 + xi[d]);
-  }
-#pragma unroll
-  for (int r = 0; r < DIM; ++r)
-#pragma unroll
-    for (int x = 0; x < DIM; ++x) J[r][x] = 0.0;
-#pragma unroll
-  for (int b = 0; b < (1 << DIM); ++b)
-#pragma unroll
-    for (int r = 0; r < DIM; ++r) {
-      double dn = ((b >> r) & 1) ? 0.5 : -0.5;
-#pragma unroll
-      for (int e = 0; e < DIM; ++e)
-        if (e != r) dn *= ((b >> e) & 1) ? fp[e] : fm[e];
-#pragma unroll
-      for (int x = 0; x < DIM; ++x) J[r][x] = fma(dn, Xc[b * DIM + x], J[r][x]);
-    }
-  double det;
-  if constexpr (DIM == 2) {
-    det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    const double rr = 1.0 / det;
-    Ji[0][0] = J[1][1] * rr;
-    Ji[0][1] = -J[0][1] * rr;
-    Ji[1][0] = -J[1][0] * rr;
-    Ji[1][1] = J[0][0] * rr;
-  } else {
-    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1], c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-    det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-    const double rr = 1.0 / det;
-    Ji[0][0] = c00 * rr;
-    Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * rr;
-    Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * rr;
-    Ji[1][0] = c01 * rr;
-    Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * rr;
-    Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * rr;
-    Ji[2][0] = c02 * rr;
-    Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * rr;
-    Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * rr;
-  }
-  return det;
-}
-
 // the workgroup shape of HoCfg plus what the pointwise geometry stages in LDS: the corners of every cell, the points of both rules
 template <int DIM, int N>
 struct HogCfg : HoCfg<DIM, N> {
@@ -518,16 +468,18 @@ HogArgs hog_args(const pyn_ctx* c) {
 
 constexpr const char* WHAT = "general matrix-free KLE operator";
 
+}  // namespace
+
 // the uploaded geometry tables (HrsCoo [point][axis][corner], reference order of points and corners) against the multilinear basis of
-// the closed form, at the points of both rules
-int hog_check_geometry_tables(pyn_ctx* c, const HoTab1D& T) {
+// the closed form, at the points of both rules (1-D points pts_full [ngl], pts_red [ngl - 1])
+int pyn_hog_check_geometry_tables(pyn_ctx* c, const std::vector<double>& pts_full, const std::vector<double>& pts_red, const char* WHAT) {
   const int dim = c->dim, ngl = c->ngl, nc = c->nc;
   std::vector<int> ln;
   ref_local_lattice(ngl, dim, ln);
   double worst = 0.0;
   for (int q = 0; q < 2; ++q) {
     const int n = q ? ngl - 1 : ngl, ngp = c->quad[q].ngp;
-    const std::vector<double>& pts = q ? T.xr : T.xl;
+    const std::vector<double>& pts = q ? pts_red : pts_full;
     PYN_CHECK(c->quad[q].HrsCoo, "%s (ngl %d): no geometry tables (pyn_elem_tables_set)", WHAT, ngl);
     std::vector<int> lp;
     ref_local_lattice(n, dim, lp);
@@ -547,12 +499,80 @@ int hog_check_geometry_tables(pyn_ctx* c, const HoTab1D& T) {
   return PYN_OK;
 }
 
-}  // namespace
-
 void pyn_hog_release(pyn_ctx* c) {
   c->d_hog_aoft.reset();
   c->d_hog_inc_ptr.reset();
   c->d_hog_inc.reset();
+}
+
+// a_of_t: the local node at tensor position i + ngl (j + ngl k), the inverse of mesh_local_lattice
+void pyn_hog_aoft(int ngl, int dim, std::vector<int32_t>& aoft) {
+  std::vector<int> loc;
+  mesh_local_lattice(ngl, dim, loc);
+  int nn = 1;
+  for (int d = 0; d < dim; ++d) nn *= ngl;
+  aoft.assign((size_t)nn, -1);
+  for (int a = 0; a < nn; ++a) {
+    int t = 0;
+    for (int d = dim - 1; d >= 0; --d) t = t * ngl + loc[a * dim + d];
+    aoft[t] = a;
+  }
+}
+
+// det J > 0 at every point of both rules of every cell, before anything else touches the cells.  d_tab + tab_pts: the 1-D points of
+// the full rule [ngl], then those of the reduced rule [ngl - 1]; `where` names the points in the message.
+int pyn_hog_check_det(pyn_ctx* c, const int32_t* d_aoft, const double* d_tab, int tab_pts, const char* what, const char* where) {
+  HogArgs A = hog_args(c);
+  A.aoft = d_aoft;
+  A.tab = d_tab;
+  DevTmp flag;
+  int h = 0;
+  PYN_HIP(flag.alloc(sizeof(int)));
+  PYN_HIP(hipMemsetAsync(flag.get(), 0, sizeof(int), c->stream));
+  const int ge = (A.n_cells + 63) / 64;
+  if (c->dim == 3)
+    hog_det_kernel<3><<<ge, 64, 0, c->stream>>>(A, c->ngl, tab_pts, flag.as<int>());
+  else
+    hog_det_kernel<2><<<ge, 64, 0, c->stream>>>(A, c->ngl, tab_pts, flag.as<int>());
+  PYN_HIP(hipGetLastError());
+  PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  PYN_HIP(hipStreamSynchronize(c->stream));
+  PYN_CHECK(!h, "%s (ngl %d): non-positive Jacobian: a cell has det J <= 0 at %s (inverted or "
+                "degenerate cell, or a connectivity that does not follow the reference's local node order)", what, c->ngl, where);
+  return PYN_OK;
+}
+
+// node -> (cell, t) incidence list: a counting sort over the connectivity conn [n_elem][nn] in ascending cell * nn + t
+// (ptr [n_node + 1], inc [n_elem * nn]); returns the index of the first connectivity entry out of range, -1 when there is none
+int64_t pyn_hog_incidence_host(const int32_t* conn, int64_t n_elem, int nn, int64_t n_node, const int32_t* aoft, std::vector<int32_t>& ptr,
+                               std::vector<int32_t>& inc) {
+  const int64_t n_ent = n_elem * nn;
+  ptr.assign((size_t)n_node + 1, 0);
+  inc.assign((size_t)n_ent, 0);
+  for (int64_t i = 0; i < n_ent; ++i) {
+    if (conn[i] < 0 || conn[i] >= n_node) return i;
+    ++ptr[conn[i] + 1];
+  }
+  std::partial_sum(ptr.begin(), ptr.end(), ptr.begin());
+  std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+  for (int64_t e = 0; e < n_elem; ++e)
+    for (int t = 0; t < nn; ++t) inc[fill[conn[e * nn + aoft[t]]]++] = (int32_t)(e * nn + t);
+  return -1;
+}
+
+// ... of the context's mesh, on the device
+int pyn_hog_incidence(pyn_ctx* c, const std::vector<int32_t>& aoft, const char* what, DevBuf<int32_t>& d_inc_ptr, DevBuf<int32_t>& d_inc) {
+  const int nn = c->nn;
+  const int64_t n_node = c->n_node, n_ent = c->n_elem * nn;
+  std::vector<int32_t> conn((size_t)n_ent), ptr, inc;
+  PYN_HIP(hipMemcpy(conn.data(), c->d_conn, (size_t)n_ent * sizeof(int32_t), hipMemcpyDeviceToHost));
+  const int64_t bad = pyn_hog_incidence_host(conn.data(), c->n_elem, nn, n_node, aoft.data(), ptr, inc);
+  PYN_CHECK(bad < 0, "%s: conn[%lld] = %d out of range", what, (long long)bad, conn[bad]);
+  PYN_HIP(d_inc_ptr.alloc((size_t)n_node + 1));
+  PYN_HIP(d_inc.alloc(std::max<size_t>(1, (size_t)n_ent)));
+  PYN_HIP(hipMemcpy(d_inc_ptr, ptr.data(), ((size_t)n_node + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+  PYN_HIP(hipMemcpy(d_inc, inc.data(), (size_t)n_ent * sizeof(int32_t), hipMemcpyHostToDevice));
+  return PYN_OK;
 }
 
 // pyn_matfree_set(PYN_MATFREE_KLE_GENERAL): the refusals, the tables, a_of_t, the sign of det J everywhere, the incidence list
@@ -571,62 +591,45 @@ int pyn_hog_set(pyn_ctx* c) {
   PYN_HIP(hipSetDevice(c->device));
   const HoTab1D T(ngl);
   PYN_TRY(pyn_ho_check_rules(c, T, WHAT));
-  PYN_TRY(hog_check_geometry_tables(c, T));
+  PYN_TRY(pyn_hog_check_geometry_tables(c, T.xl, T.xr, WHAT));
   PYN_TRY(pyn_ho_tab_upload(c, T));
   pyn_hog_release(c);
   c->mf_set[PYN_MATFREE_KLE_GENERAL] = false;
-  // a_of_t: the local node at tensor position i + ngl (j + ngl k)
-  std::vector<int> loc;
-  mesh_local_lattice(ngl, dim, loc);
-  std::vector<int32_t> aoft((size_t)nn, -1), t_of_a((size_t)nn);
-  for (int a = 0; a < nn; ++a) {
-    int t = 0;
-    for (int d = dim - 1; d >= 0; --d) t = t * ngl + loc[a * dim + d];
-    aoft[t] = a;
-    t_of_a[a] = t;
-  }
+  std::vector<int32_t> aoft;
+  pyn_hog_aoft(ngl, dim, aoft);
   DevBuf<int32_t> d_aoft, d_inc_ptr, d_inc;   // committed together at the end: a refused set leaves no lists behind
   PYN_HIP(d_aoft.alloc((size_t)nn));
   PYN_HIP(hipMemcpy(d_aoft, aoft.data(), (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice));
-  {   // det J > 0 everywhere, before anything else touches the cells
-    HogArgs A = hog_args(c);
-    A.aoft = d_aoft;
-    DevTmp flag;
-    int h = 0;
-    PYN_HIP(flag.alloc(sizeof(int)));
-    PYN_HIP(hipMemsetAsync(flag.get(), 0, sizeof(int), c->stream));
-    const int ge = (A.n_cells + 63) / 64, tab_pts = (int)(T.packed().size() - T.xl.size() - T.xr.size());
-    if (dim == 3)
-      hog_det_kernel<3><<<ge, 64, 0, c->stream>>>(A, ngl, tab_pts, flag.as<int>());
-    else
-      hog_det_kernel<2><<<ge, 64, 0, c->stream>>>(A, ngl, tab_pts, flag.as<int>());
-    PYN_HIP(hipGetLastError());
-    PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    PYN_HIP(hipStreamSynchronize(c->stream));
-    PYN_CHECK(!h, "%s (ngl %d): non-positive Jacobian: a cell has det J <= 0 at a Lobatto node or a Gauss point (inverted or "
-                  "degenerate cell, or a connectivity that does not follow the reference's local node order)", WHAT, ngl);
-  }
-  // node -> (cell, t) incidence list: a counting sort over the connectivity in ascending cell * nn + t
-  const int64_t n_node = c->n_node, n_ent = c->n_elem * nn;
-  std::vector<int32_t> conn((size_t)n_ent), ptr((size_t)n_node + 1, 0), inc((size_t)n_ent);
-  PYN_HIP(hipMemcpy(conn.data(), c->d_conn, (size_t)n_ent * sizeof(int32_t), hipMemcpyDeviceToHost));
-  for (int64_t i = 0; i < n_ent; ++i) {
-    PYN_CHECK(conn[i] >= 0 && conn[i] < n_node, "%s: conn[%lld] = %d out of range", WHAT, (long long)i, conn[i]);
-    ++ptr[conn[i] + 1];
-  }
-  std::partial_sum(ptr.begin(), ptr.end(), ptr.begin());
-  {
-    std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-    for (int64_t e = 0; e < c->n_elem; ++e)
-      for (int t = 0; t < nn; ++t) inc[fill[conn[e * nn + aoft[t]]]++] = (int32_t)(e * nn + t);
-  }
-  PYN_HIP(d_inc_ptr.alloc((size_t)n_node + 1));
-  PYN_HIP(d_inc.alloc(std::max<size_t>(1, (size_t)n_ent)));
-  PYN_HIP(hipMemcpy(d_inc_ptr, ptr.data(), ((size_t)n_node + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-  PYN_HIP(hipMemcpy(d_inc, inc.data(), (size_t)n_ent * sizeof(int32_t), hipMemcpyHostToDevice));
+  const int tab_pts = (int)(T.packed().size() - T.xl.size() - T.xr.size());
+  PYN_TRY(pyn_hog_check_det(c, d_aoft, c->d_ho_tab, tab_pts, WHAT, "a Lobatto node or a Gauss point"));
+  PYN_TRY(pyn_hog_incidence(c, aoft, WHAT, d_inc_ptr, d_inc));
   c->d_hog_aoft = std::move(d_aoft);
   c->d_hog_inc_ptr = std::move(d_inc_ptr);
   c->d_hog_inc = std::move(d_inc);
+  return PYN_OK;
+}
+
+// pass 2 of both general operators: every row = the sum of its incidence entries in ascending order, under `mask`.  dot: fused p.Ap
+// partials into c->d_part (one per workgroup, *grid_out of them).
+int pyn_hog_gather(pyn_ctx* c, const int32_t* inc_ptr, const int32_t* inc, const double* ye, const uint8_t* mask, const double* x, double* y,
+                   bool dot, int* grid_out) {
+  const int* flag = dot ? c->d_flag : nullptr;
+  const int64_t rows = c->n_node;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, PYN_MAX_PARTIALS));
+  if (grid_out) *grid_out = grid;
+  double* part = dot ? c->d_part : nullptr;
+  if (c->dim == 3) {
+    if (dot)
+      hog_gather_kernel<3, true><<<grid, 256, 0, c->stream>>>(inc_ptr, inc, ye, mask, c->nn, rows, x, y, flag, part);
+    else
+      hog_gather_kernel<3, false><<<grid, 256, 0, c->stream>>>(inc_ptr, inc, ye, mask, c->nn, rows, x, y, flag, part);
+  } else {
+    if (dot)
+      hog_gather_kernel<2, true><<<grid, 256, 0, c->stream>>>(inc_ptr, inc, ye, mask, c->nn, rows, x, y, flag, part);
+    else
+      hog_gather_kernel<2, false><<<grid, 256, 0, c->stream>>>(inc_ptr, inc, ye, mask, c->nn, rows, x, y, flag, part);
+  }
+  PYN_HIP(hipGetLastError());
   return PYN_OK;
 }
 
@@ -636,23 +639,6 @@ int pyn_hog_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out
   PYN_CHECK(c->mf_set[PYN_MATFREE_KLE_GENERAL] && c->d_ho_tab && c->d_ho_ye && c->d_hog_aoft && c->d_hog_inc_ptr && c->d_hog_inc,
             "%s: pyn_matfree_set first", WHAT);
   const HogArgs A = hog_args(c);
-  const int* flag = dot ? c->d_flag : nullptr;
-  PYN_TRY(launch_hog_cells_any(c, c->dim, c->ngl, A, x, flag));
-  const int64_t rows = c->n_node;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, PYN_MAX_PARTIALS));
-  if (grid_out) *grid_out = grid;
-  double* part = dot ? c->d_part : nullptr;
-  if (c->dim == 3) {
-    if (dot)
-      hog_gather_kernel<3, true><<<grid, 256, 0, c->stream>>>(c->d_hog_inc_ptr, c->d_hog_inc, A.ye, A.mask, c->nn, rows, x, y, flag, part);
-    else
-      hog_gather_kernel<3, false><<<grid, 256, 0, c->stream>>>(c->d_hog_inc_ptr, c->d_hog_inc, A.ye, A.mask, c->nn, rows, x, y, flag, part);
-  } else {
-    if (dot)
-      hog_gather_kernel<2, true><<<grid, 256, 0, c->stream>>>(c->d_hog_inc_ptr, c->d_hog_inc, A.ye, A.mask, c->nn, rows, x, y, flag, part);
-    else
-      hog_gather_kernel<2, false><<<grid, 256, 0, c->stream>>>(c->d_hog_inc_ptr, c->d_hog_inc, A.ye, A.mask, c->nn, rows, x, y, flag, part);
-  }
-  PYN_HIP(hipGetLastError());
-  return PYN_OK;
+  PYN_TRY(launch_hog_cells_any(c, c->dim, c->ngl, A, x, dot ? c->d_flag : nullptr));
+  return pyn_hog_gather(c, c->d_hog_inc_ptr, c->d_hog_inc, A.ye, A.mask, x, y, dot, grid_out);
 }

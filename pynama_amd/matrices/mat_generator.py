@@ -200,18 +200,24 @@ class Mat:
                               self.Rd.id if with_rd else -1, variant)
         # K also exists in matrix-free form on structured Q1 hex meshes (KspSolver -pynama_mat_free), and, opt-in, on structured
         # meshes of affine cells of second order (-pynama_mat_free_ngl3) and of orders ngl >= 4 (-pynama_mat_free_ho), and on any
-        # quadrilateral / hexahedral mesh of orders ngl >= 4, bent and imported ones included (-pynama_mat_free_ho_general)
+        # quadrilateral / hexahedral mesh of orders ngl >= 4, bent and imported ones included (-pynama_mat_free_ho_general), or of
+        # order ngl 3 (-pynama_mat_free_ngl3_general)
         self.K.matfree = None
         topo = self.ctx.mesh_topology()[0]
         if self.dim == 3 and elem.nnode == 8 and topo == "lattice":
             self.ctx.matfree_set(_lib.MATFREE_KLE, alpha_d, alpha_w)      # snapshot of THIS assembly's Dirichlet mask
             self.K.matfree = _lib.MATFREE_KLE
-        elif topo == "lattice-ngl3" and _flag_set(Options(), 'pynama_mat_free_ngl3'):
-            try:
-                self.ctx.matfree_set(_lib.MATFREE_KLE, alpha_d, alpha_w)
-                self.K.matfree = _lib.MATFREE_KLE
-            except _lib.PynamaHipError as e:                              # e.g. a cell that is not affine
-                logging.getLogger("Mat").info(f"-pynama_mat_free_ngl3: K stays assembled only ({e})")
+        elif topo == "lattice-ngl3" or (topo == "general" and getattr(elem, 'ngl', 0) == 3):
+            # second order: the affine lattice shell first, exactly as before; the general ngl 3 one (bent cells, imported meshes)
+            # where that is refused, was not asked for or does not apply
+            for flag, op in (('pynama_mat_free_ngl3', _lib.MATFREE_KLE), ('pynama_mat_free_ngl3_general', _lib.MATFREE_KLE_NGL3_GENERAL)):
+                if self.K.matfree is not None or not _flag_set(Options(), flag) or (op == _lib.MATFREE_KLE and topo != "lattice-ngl3"):
+                    continue
+                try:
+                    self.ctx.matfree_set(op, alpha_d, alpha_w)
+                    self.K.matfree = op
+                except _lib.PynamaHipError as e:                          # e.g. a cell that is not affine
+                    logging.getLogger("Mat").info(f"-{flag}: K stays assembled only ({e})")
         elif topo == "general" and getattr(elem, 'ngl', 0) >= 4:
             # the affine box-lattice shell first, exactly as before; the general one where that is refused or was not asked for
             for flag, op in (('pynama_mat_free_ho', _lib.MATFREE_KLE), ('pynama_mat_free_ho_general', _lib.MATFREE_KLE_GENERAL)):

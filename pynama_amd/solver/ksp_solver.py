@@ -18,7 +18,11 @@ On second-order (ngl 3) structured meshes of affine cells ``Mat.K`` carries the 
 the same rules apply.  ``-pynama_mat_free_ho_general`` (opt-in, one rank) gives ``Mat.K`` of any quadrilateral / hexahedral mesh of
 those orders a shell -- bent cells, imported (Gmsh) meshes, any numbering and vertex valence: the Jacobian is formed at every
 quadrature point from the cell's corners.  With both options the affine shell is taken where it applies (it is the faster one) and
-the general one elsewhere.  ``-pc_type mg`` stays refused on meshes that are no lattice, with or without a shell.
+the general one elsewhere.  ``-pynama_mat_free_ngl3_general`` (opt-in, one rank) does the same at the reference's own order: a
+second-order lattice with a cell that is not affine, or an imported quadrilateral / hexahedral mesh lifted to ngl 3, gets a shell
+that interpolates to the points of both Gauss rules and forms the Jacobian there; with ``-pynama_mat_free_ngl3`` as well, the
+affine shell is tried first.  ``-pc_type mg`` stays refused on meshes that are no lattice, with or without a shell, and does not
+multiply with the general ngl 3 shell (the V-cycle keeps the assembled product).
 
 The reference's hard-wired default is ``preonly`` + ``lu`` (:13-16).  Systems of up to ``-pynama_direct_max_rows`` rows
 (default 8192 = the library's limit; one rank) ARE solved directly: ``pyn_solve_direct`` factors the matrix densely with partial pivoting once
@@ -171,7 +175,8 @@ class KspSolver(object):
                 raise ValueError("-pynama_mat_free: this operator has no matrix-free form (structured Q1 hex meshes; "
                                  "second-order structured meshes of affine cells with -pynama_mat_free_ngl3; box meshes "
                                  "of affine cells of order ngl 4..12 in 2-D / 4..8 in 3-D with -pynama_mat_free_ho; any "
-                                 "quadrilateral / hexahedral mesh of those orders on one rank with -pynama_mat_free_ho_general)")
+                                 "quadrilateral / hexahedral mesh of those orders on one rank with -pynama_mat_free_ho_general, "
+                                 "of order ngl 3 with -pynama_mat_free_ngl3_general)")
             mf = tag
         elif self.mat_free is None and tag is not None and self.ksp_type in ('cg', 'preonly'):
             try:                                       # automatic: the shell, unless the library finds it differs from A
