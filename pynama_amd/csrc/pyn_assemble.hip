@@ -117,6 +117,22 @@ __device__ inline int curl_term(int dim, int p, int k, int* m) {
 // v[m] for a runtime m without dynamic register-array indexing (which would put the array in scratch memory)
 __device__ __forceinline__ double pick3(const double (&v)[3], int m) { return m == 0 ? v[0] : (m == 1 ? v[1] : v[2]); }
 
+// G_a . G_b over the first `dim` axes, and one reduced-rule point's term of entry (p, q) of a node pair's K block,
+// alpha_d G_pa G_qb + alpha_w (d_pq G_a.G_b - G_qa G_pb), with every rounding spelled out.  The per-pair and the staged KLE paths
+// both sum their K entries through these two functions and fma(c, term, acc), so that they round alike: with the same sums written
+// as plain expressions and fused as the compiler saw fit at each site, the two paths differed in the last bit of a few per cent of
+// the diagonal-component entries of a one-cell mesh (tests/test_gpu_generic_forms.py keeps them bit-identical).
+__device__ __forceinline__ double gdot(const double (&ga)[3], const double (&gb)[3], int dim) {
+  double s = ga[0] * gb[0];
+  if (dim > 1) s = fma(ga[1], gb[1], s);
+  if (dim > 2) s = fma(ga[2], gb[2], s);
+  return s;
+}
+__device__ __forceinline__ double kle_pen(double ad, double aw, double gap, double gbq, double gaq, double gbp, double s, bool diag) {
+  const double pen = fma(ad * gap, gbq, -(aw * gaq * gbp));
+  return diag ? fma(aw, s, pen) : pen;
+}
+
 template <int BLOCK, bool PT_LDS, bool DENSE>
 __global__ void __launch_bounds__(BLOCK) assemble_generic_kernel(AsmArgs A) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -293,24 +309,19 @@ __global__ void __launch_bounds__(BLOCK) assemble_generic_kernel(AsmArgs A) {
                 for (int ub = 0; ub < 2; ++ub) {
                   const int pr = ua * 2 + ub;
                   if (pass == 0) {
-                    double sdot = 0.0;
-#pragma unroll
-                    for (int d = 0; d < 3; ++d)
-                      if (d < dim) sdot += ga[ua][d] * gb[ub][d];
+                    const double sdot = gdot(ga[ua], gb[ub], dim);
                     if (full) {
 #pragma unroll
                       for (int p = 0; p < 3; ++p)
-                        if (p < dim) acc[pr][p][p] += cg * sdot;
+                        if (p < dim) acc[pr][p][p] = fma(cg, sdot, acc[pr][p][p]);
                     } else {
 #pragma unroll
                       for (int p = 0; p < 3; ++p)
 #pragma unroll
                         for (int q = 0; q < 3; ++q)
-                          if (p < dim && q < dim) {
-                            double pen = A.alpha_d * ga[ua][p] * gb[ub][q] - A.alpha_w * ga[ua][q] * gb[ub][p];
-                            if (p == q) pen += A.alpha_w * sdot;
-                            acc[pr][p][q] += cg * pen;
-                          }
+                          if (p < dim && q < dim)
+                            acc[pr][p][q] = fma(cg, kle_pen(A.alpha_d, A.alpha_w, ga[ua][p], gb[ub][q], ga[ua][q], gb[ub][p], sdot, p == q),
+                                                acc[pr][p][q]);
                     }
                   } else if (full) {
 #pragma unroll
@@ -458,9 +469,15 @@ __global__ void __launch_bounds__(BLOCK) assemble_generic_kernel(AsmArgs A) {
         double vfull = 0.0;
         for (int g = 0; g < nga; ++g) {
           const double* P = pt + (int64_t)g * pt_stride;
-          double s = 0.0;
-          for (int d = 0; d < dim; ++d) s += P[dd + 1 + d * nn + a] * P[dd + 1 + d * nn + b];
-          vfull += P[dd] * s;
+          const double* G = P + dd + 1;
+          double ga[3] = {0.0, 0.0, 0.0}, gb[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+          for (int d = 0; d < 3; ++d)
+            if (d < dim) {
+              ga[d] = G[d * nn + a];
+              gb[d] = G[d * nn + b];
+            }
+          vfull = fma(P[dd], gdot(ga, gb, dim), vfull);
         }
         double v[3][3];
 #pragma unroll
@@ -470,24 +487,20 @@ __global__ void __launch_bounds__(BLOCK) assemble_generic_kernel(AsmArgs A) {
         for (int g = nga; g < ngt; ++g) {
           const double* P = pt + (int64_t)g * pt_stride;
           const double* G = P + dd + 1;
-          double ga[3] = {0.0, 0.0, 0.0}, gb[3] = {0.0, 0.0, 0.0}, s = 0.0;
+          double ga[3] = {0.0, 0.0, 0.0}, gb[3] = {0.0, 0.0, 0.0};
 #pragma unroll
           for (int d = 0; d < 3; ++d)
             if (d < dim) {
               ga[d] = G[d * nn + a];
               gb[d] = G[d * nn + b];
-              s += ga[d] * gb[d];
             }
+          const double s = gdot(ga, gb, dim);
           const double cg = P[dd];
 #pragma unroll
           for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int q = 0; q < 3; ++q)
-              if (p < dim && q < dim) {
-                double pen = A.alpha_d * ga[p] * gb[q] - A.alpha_w * ga[q] * gb[p];
-                if (p == q) pen += A.alpha_w * s;
-                v[p][q] += cg * pen;
-              }
+              if (p < dim && q < dim) v[p][q] = fma(cg, kle_pen(A.alpha_d, A.alpha_w, ga[p], gb[q], ga[q], gb[p], s, p == q), v[p][q]);
         }
         if (!DENSE) {
           locate(ab, a, b);

@@ -41,6 +41,24 @@ def bent_lattice(dim, nelem, ngl, bend=0.2, seed=0):
     return mesh
 
 
+def warped_lattice(dim, nelem, ngl, warp=0.15, seed=0):
+    """the box lattice of fo.box_mesh with EVERY corner node, those on the boundary included, moved by at most warp * h along every
+    axis and every high-order node recomputed as the multilinear image of its cell's corners: a single cell is already bilinear /
+    trilinear (bent_lattice moves interior corners only, and a [2, 1, 2] box has none).  `boundary` and `borders` stay the node
+    sets of the box: valid Dirichlet and wall sets of a domain whose shape alone has changed."""
+    mesh = fo.box_mesh(nelem, [0.0] * dim, UPPER[:dim], ngl)
+    nc = 2 ** dim
+    h = min(u / n for u, n in zip(UPPER[:dim], nelem))
+    corner_ids = np.unique(mesh.conn[:, :nc])
+    cxyz = mesh.xyz.copy()
+    cxyz[corner_ids] += warp * h * np.random.default_rng(seed).uniform(-1.0, 1.0, (len(corner_ids), dim))
+    xyz = cxyz.copy()
+    xyz[mesh.conn.ravel()] = _corner_image(ngl, dim, cxyz[mesh.conn[:, :nc]]).reshape(-1, dim)
+    xyz[corner_ids] = cxyz[corner_ids]
+    mesh.xyz = xyz
+    return mesh
+
+
 def _rotations(dim):
     from tests.test_highorder_import_host import _rotations as rot
     return rot(dim)

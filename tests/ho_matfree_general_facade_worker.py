@@ -2,7 +2,8 @@
 case gmsh2d / gmsh3d: UniformFlow on a Gmsh file of a jittered box in random node numbering and random cell order (the recipe of
 tests/test_gpu_api.py: _write_permuted_box), 2-D [5, 4] at ngl 5 / 3-D [3, 3, 2] at ngl 4; mode on carries
 -pynama_mat_free_ho_general, mode off does not.  case tg, mode both: the Taylor-Green box of tests/ho_matfree_facade_worker.py with
--pynama_mat_free_ho and -pynama_mat_free_ho_general.  Every run solves with -ksp_type cg -pc_type jacobi -ksp_rtol 1e-12."""
+-pynama_mat_free_ho and -pynama_mat_free_ho_general.  Every run solves with -ksp_type cg -pc_type jacobi, -ksp_rtol 1e-12 (tg) or
+1e-13 (gmsh2d / gmsh3d)."""
 import os
 import sys
 
@@ -30,7 +31,9 @@ def main():
     (case, mode), out, tmp = sys.argv[1].split(":"), sys.argv[2], sys.argv[3]
     from common.options import Options
     flags = {"on": ["-pynama_mat_free_ho_general"], "off": [], "both": ["-pynama_mat_free_ho", "-pynama_mat_free_ho_general"]}[mode]
-    Options(flags + ["-ksp_type", "cg", "-pc_type", "jacobi", "-ksp_rtol", "1e-12"])
+    # (the Gmsh cases to 1e-13: with 1e-12 the error of the assembled solve ends between 0.5e-10 and 1.2e-10 from run to run, as the
+    # order of the assembly's atomic adds moves the iteration CG stops at, and the test bounds it by 1e-10)
+    Options(flags + ["-ksp_type", "cg", "-pc_type", "jacobi", "-ksp_rtol", "1e-12" if case == "tg" else "1e-13"])
     if case == "tg":
         from cases.custom_func import CustomFuncCase
         with open(os.path.join(CASES, "taylor-green.yaml")) as f:

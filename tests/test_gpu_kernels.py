@@ -101,6 +101,8 @@ def test_csr_symbolic_permuted_elements(lib):
     # point data beyond the LDS: Gauss points staged in chunks; nn >= 48 takes the FP64 matrix-core kernel
     ([3, 2], 8, 0.0, 0), ([2, 2], 11, 0.0, 0), ([2, 2, 2], 4, 0.0, 0), ([2, 1, 2], 5, 0.0, 0)])
 def test_assemble_kle_vs_oracle(lib, nelem, ngl, jitter, variant):
+    # the launch form of the generic kernel every variant-0 row is meant to reach: 1 = 64 threads, 2 = point data in LDS, 5 = matrix cores
+    form = {(2, 2): 1, (3, 2): 1, (2, 3): 2, (3, 3): 2, (2, 6): 2, (2, 8): 5, (2, 11): 5, (3, 4): 5, (3, 5): 5}[(len(nelem), ngl)]
     dim = len(nelem)
     dw = 1 if dim == 2 else 3
     mesh = fo.box_mesh(nelem, [0.0] * dim, [1.0, 0.8, 1.2][:dim], ngl, jitter=jitter)
@@ -112,8 +114,10 @@ def test_assemble_kle_vs_oracle(lib, nelem, ngl, jitter, variant):
         ctx.patch_plan_set(*tile_plan(mesh, (4, 3, 3)), kind=1)
         ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, -1, variant=1)
         ctx.assemble_kle(1e3, 1e2, -1, -1, -1, Rd, variant=0)
+        assert_assembled(ctx, lib.AK_GENERIC, generic=form)
     else:
         ctx.assemble_kle(1e3, 1e2, K, Krhs, Rw, Rd, variant=variant)
+        assert_assembled(ctx, lib.AK_GENERIC, generic=form)
     ref = fo.assemble_kle_freeslip(mesh, fo.Tables(ngl, dim), with_rd=True)
     assert sp_rel_err(mat_to_scipy(ctx, K, dim, dim), ref["K"]) < FP_TOL
     assert sp_rel_err(mat_to_scipy(ctx, Krhs, dim, dim), ref["Krhs"]) < FP_TOL

@@ -75,7 +75,10 @@ def test_two_rule_model_equals_the_oracle_on_every_cell(lib, name, make):
     assert worst <= CELL_TOL
 
 
-@pytest.mark.parametrize("name,make", [m for m in MESHES if m[0] in ("bent2d[7, 4]", "imported3d[3, 2, 3]", "star5", "star5x2")], ids=str)
+INCIDENCE_MESHES = [m for m in MESHES if m[0] in ("bent2d[7, 4]", "imported3d[3, 2, 3]", "star5", "star5x2")]
+
+
+@pytest.mark.parametrize("name,make", INCIDENCE_MESHES, ids=[m[0] for m in INCIDENCE_MESHES])   # (ids=str would print the builder's address)
 def test_incidence_list(lib, name, make):
     """the node -> (cell, t) list: every entry once, ascending within a row, every entry of a row names that node, rows as long as
     the node's valence; on a lexicographic lattice an interior vertex has 2^dim entries"""
