@@ -547,6 +547,31 @@ int pyn_ibm_info(pyn_ctx* ctx, int64_t* info);
 /* drops the marker set (pyn_mesh_set / pyn_mesh_box and pyn_ctx_destroy do the same) */
 int pyn_ibm_clear(pyn_ctx* ctx);
 
+/* ---- point probes (pyn_probe.hip) ------------------------------------------------------------
+ * The finite-element interpolant of a nodal vector at arbitrary points of any quadrilateral / hexahedral mesh of order
+ * ngl <= pyn_ho_matfree_max_ngl(dim), on one rank.  Several probe sets live side by side (ids as for node sets, never reused);
+ * pyn_mesh_set / pyn_mesh_box end every set, and a dead id is PYN_EINVAL with a message.
+ * A point's cell e and reference position xi solve x(xi) = sum_c N_c(xi) X_c over the 2^dim corners (the first 2^dim entries of the
+ * connectivity row; corner c sits at reference position pyn_ho_local_lattice's unflipped table of order 2).  The sampled value is
+ * sum_a phi_a(xi) u[conn[e][a]], phi_a the tensor product of the Lagrange functions of the ascending Lobatto(ngl) nodes at the
+ * reference position of local node a.  No floating-point atomics: two calls on the same state give identical bits. */
+/* Uploads X[n*dim] and locates every point on the device, once.  Path 0, a box lattice whose nodes are the tensor product of
+ * per-axis lines bit for bit (checked on the device): binary search over the cell edges per axis, xi in closed form, a point on an
+ * interior cell face goes to the lower cell.  Path 1, every other mesh: a uniform bin grid of the cells' corner bounding boxes, Newton
+ * from xi = 0 on each candidate (at most 16 steps, until |d xi|_inf < 1e-13), accepted at |xi|_inf <= 1 + 1e-10 (then clipped to
+ * [-1, 1]); the lowest accepting cell index wins; a cell with det J <= 0 at an iterate is skipped.  A point in no cell is not an
+ * error: cell -1, NaN samples.  Refused with a message: simplices; several ranks or ghost nodes; ngl above
+ * pyn_ho_matfree_max_ngl(dim); nn that is not ngl^dim; n < 1; a coordinate that is NaN or infinite. */
+int pyn_probe_create(pyn_ctx* ctx, int64_t n, const double* X, int* probe_id);
+/* info[5]: points, points found, path (0 rectilinear, 1 search), most Newton steps of an accepted cell, most candidates of a point */
+int pyn_probe_info(pyn_ctx* ctx, int probe_id, int64_t* info);
+/* cell[n] (-1: not found) and xi[n*dim] (NaN where not found); either pointer may be NULL */
+int pyn_probe_get(pyn_ctx* ctx, int probe_id, int32_t* cell, double* xi);
+/* out[n*bs]: all bs components of the vector at every point in one pass (bs 1 .. 6), NaN where the point was not found.  Refused:
+ * a vector whose node count is not the mesh's */
+int pyn_probe_sample(pyn_ctx* ctx, int probe_id, int vec_id, double* out);
+int pyn_probe_destroy(pyn_ctx* ctx, int probe_id);
+
 /* ---- timers -------------------------------------------------------------------------------
  * Device time (HIP events on the context stream) of the last call of each phase, in ms.
  * Replaces the tic/toc log of src/run_case.py:156-162. */

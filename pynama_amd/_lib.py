@@ -152,6 +152,11 @@ SIGNATURES = {
     "pyn_ibm_matrix_get": [_P, _pf64],
     "pyn_ibm_info": [_P, _pi64],
     "pyn_ibm_clear": [_P],
+    "pyn_probe_create": [_P, _L, _pf64, C.POINTER(_I)],
+    "pyn_probe_info": [_P, _I, _pi64],
+    "pyn_probe_get": [_P, _I, _pi32, _pf64],
+    "pyn_probe_sample": [_P, _I, _I, _pf64],
+    "pyn_probe_destroy": [_P, _I],
     "pyn_timers_get": [_P, _pf64, _I],
 }
 
@@ -331,6 +336,7 @@ class Context:
         self.rank, self.nranks = 0, 1
         self.dim = self.nn = 0
         self.n_owned = self.n_ghost = 0
+        self._vec_bs = {}               # block size of every vector made by vec_create (probe_sample sizes its result by it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -544,6 +550,7 @@ class Context:
     def vec_create(self, bs) -> int:
         i = _I(-1)
         _check(self.lib.pyn_vec_create(self.h, bs, C.byref(i)))
+        self._vec_bs[i.value] = int(bs)
         return i.value
 
     def vec_destroy(self, vid):
@@ -837,6 +844,49 @@ class Context:
 
     def ibm_clear(self):
         _check(self.lib.pyn_ibm_clear(self.h))
+
+    # -- point probes
+    def probe_create(self, X) -> int:
+        """locates the points X [n, dim] in the mesh on the device (pyn_probe_create); the id dies with the mesh"""
+        X = _f64(X)
+        dim = self.dim
+        if X.ndim == 1 and dim:
+            X = X.reshape(-1, dim)
+        if X.ndim != 2 or (X.shape[0] and X.shape[1] != dim):
+            raise PynamaHipError(f"probe_create: points {X.shape} are not [n, {dim}]")
+        i = _I(-1)
+        _check(self.lib.pyn_probe_create(self.h, X.shape[0], X if X.size else np.zeros(1), C.byref(i)))
+        return i.value
+
+    def probe_info(self, pid):
+        """{'n', 'found', 'path' (0 rectilinear, 1 search), 'max_newton', 'max_candidates'}"""
+        info = np.zeros(5, np.int64)
+        _check(self.lib.pyn_probe_info(self.h, int(pid), info))
+        return dict(zip(("n", "found", "path", "max_newton", "max_candidates"), (int(v) for v in info)))
+
+    def probe_get(self, pid):
+        """(cell [n] int32, -1 where the point is in no cell; xi [n, dim], NaN there)"""
+        n = self.probe_info(pid)["n"]
+        cell, xi = np.empty(n, np.int32), np.empty((n, self.dim))
+        _check(self.lib.pyn_probe_get(self.h, int(pid), cell, xi))
+        return cell, xi
+
+    def probe_sample(self, pid, vid, bs=None):
+        """the vector's interpolant at the points, [n, bs] (NaN where a point was not found); bs: the vector's block size (known for
+        vectors of vec_create)"""
+        if bs is None:
+            bs = self._vec_bs.get(vid)
+            if bs is None:
+                raise PynamaHipError(f"probe_sample: the block size of vector {vid} is not known here, pass bs")
+        elif self._vec_bs.get(vid, bs) != bs:
+            raise PynamaHipError(f"probe_sample: vector {vid} has block size {self._vec_bs[vid]}, not {bs}")
+        out = np.empty((self.probe_info(pid)["n"], int(bs)))
+        _check(self.lib.pyn_probe_sample(self.h, int(pid), int(vid), out))
+        return out
+
+    def probe_destroy(self, pid):
+        if self.h:
+            _check(self.lib.pyn_probe_destroy(self.h, int(pid)))
 
     def timers(self):
         t = np.zeros(8)

@@ -206,6 +206,39 @@ class BaseProblem(object):
             self.logger.info(f"Converged: Step {step:4} | Time {time:.4e} | Increment Time: {ts.getTimeStep():.2e}")
         if self.config.get("save-output", False) and step % max(1, getattr(self, "_saveEvery", 1)) == 0:
             self.saveStep(step, time)
+        probe = self.getProbe()
+        if probe is not None:
+            self._probeSeries.append((time, probe.sample(self.vel), probe.sample(self.vort)))
+
+    def probePoints(self):
+        """the points of the optional `probes` block of the yaml: `points: [[x, y], ...]` and / or
+        `line: {from: [x, y], to: [x, y], n: 65}` (the listed points first); None without the block"""
+        block = self.config.get("probes")
+        if not block:
+            return None
+        from pynama_amd.domain.probe import line_points
+        parts = []
+        if block.get("points") is not None:
+            parts.append(np.asarray(block["points"], dtype=np.float64).reshape(-1, self.dim))
+        if block.get("line") is not None:
+            line = block["line"]
+            parts.append(line_points(line["from"], line["to"], line["n"]).reshape(-1, self.dim))
+        if not parts:
+            raise ValueError("probes: the block has neither `points` nor `line`")
+        return np.concatenate(parts)
+
+    def getProbe(self):
+        """the probe set of the `probes` block, located in the mesh on first use; None (and nothing created) without the block"""
+        if getattr(self, "_probe", None) is None:
+            points = self.probePoints()
+            if points is None:
+                return None
+            self._probe, self._probeSeries = self.dom.createProbe(points), []
+        return self._probe
+
+    def getProbeSeries(self):
+        """[(t, vel [n, dim], vort [n, dim_w])] of every accepted step so far (empty without a `probes` block)"""
+        return list(getattr(self, "_probeSeries", []))
 
     def solveKLE(self, time, vort):
         pass

@@ -62,3 +62,21 @@ class Cavity(NoSlipFreeSlip):
     def applyBoundaryConditionsFS(self):
         self._setWallValues(self.velFS, self.nsWalls.getWallsWithVelocity(), static=False)
         self._setWallValues(self.velFS, self.nsWalls.getStaticWalls(), static=True)
+
+    def centerlines(self, n=65):
+        """the velocity profiles of the two centre lines (the Ghia comparison): (y, u(xc, y)) and (x, v(x, yc)) at n points each,
+        from two probe sets built on first use"""
+        xc, yc = (0.5 * (lo + up) for lo, up in zip(self.lower[:2], self.upper[:2]))
+        if self.dim != 2:
+            raise ValueError("centerlines: the cavity's centre lines are those of a 2-D case")
+        cached = getattr(self, "_centerProbes", None)
+        if cached is None or cached[0] != int(n):
+            for probe in (cached[3:] if cached else ()):
+                probe.destroy()
+            y = np.linspace(self.lower[1], self.upper[1], int(n))
+            x = np.linspace(self.lower[0], self.upper[0], int(n))
+            cached = (int(n), y, x, self.dom.createProbe(np.column_stack([np.full(int(n), xc), y])),
+                      self.dom.createProbe(np.column_stack([x, np.full(int(n), yc)])))
+            self._centerProbes = cached
+        _, y, x, vertical, horizontal = cached
+        return (y, vertical.sample(self.vel)[:, 0]), (x, horizontal.sample(self.vel)[:, 1])

@@ -551,6 +551,10 @@ static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
   }
   c->ibm.reset();                 // ... the immersed-boundary marker set
   for (auto& s : c->nodesets) s = DNodeSet();   // ... every node set (ids are not reused: the slots stay, dead)
+  for (auto& p : c->probes) p = DProbe();       // ... and every probe set, the same way, with the tables of their order
+  c->d_probe_loc.reset();
+  c->d_probe_tab.reset();
+  c->probe_tab_ngl = c->probe_tab_dim = 0;
   c->d_rowptr.reset();            // ... and the graph (the matrices go with the next pyn_csr_symbolic)
   c->d_colidx.reset();
   c->nnzb = 0;

@@ -298,6 +298,17 @@ struct DNodeSet {
   bool live = false;
 };
 
+// a set of sample points located in the mesh (pyn_probe.hip): the cell and reference position of every point, found once at creation
+struct DProbe {
+  DevBuf<int32_t> cell;    // [n] cell of the point, -1: in no cell
+  DevBuf<double> xi;       // [n][dim] reference position in that cell (NaN where not found)
+  DevBuf<double> out;      // [n][bs] staging of pyn_probe_sample (grown on demand)
+  int64_t n = 0, found = 0;
+  int path = 0;            // 0 rectilinear box lattice (binary search per axis), 1 bin grid + Newton
+  int max_newton = 0, max_cand = 0;
+  bool live = false;
+};
+
 static_assert(!std::is_copy_constructible<DMat>::value && !std::is_copy_constructible<DVec>::value &&
                   !std::is_copy_constructible<SellShape>::value && !std::is_copy_constructible<DevBuf<double>>::value,
               "a struct that owns device memory must not be copyable");
@@ -416,6 +427,10 @@ struct pyn_ctx {
   std::vector<DMat> mats;
   std::vector<DVec> vecs;
   std::vector<DNodeSet> nodesets;   // ids are never reused: a released set stays dead (pyn_fields.hip)
+  std::vector<DProbe> probes;       // point probes (pyn_probe.hip); ids are never reused either, and a new mesh kills every set
+  DevBuf<int32_t> d_probe_loc;      // ... their local-order table ref_local_lattice(ngl, dim) [nn][dim] ...
+  DevBuf<double> d_probe_tab;       // ... and the 1-D Lobatto nodes x[ngl] with the Lagrange denominators den[ngl], uploaded once for
+  int probe_tab_ngl = 0, probe_tab_dim = 0;   // ... this order and dimension
 
   // reduction / solver scratch
   DevBuf<double> d_part;       // [8][PYN_MAX_PARTIALS]

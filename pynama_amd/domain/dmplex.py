@@ -858,6 +858,11 @@ class DMPlexDom(object):
         from pynama_amd.vectors import Vec
         return Vec(self.ctx, bs or self.dim)
 
+    def createProbe(self, points):
+        """Probe over the points [n, dim], located in the mesh on the device (pynama_amd/domain/probe.py); one rank"""
+        from pynama_amd.domain.probe import Probe
+        return Probe(self, points)
+
     def nodeSet(self, nodes):
         """NodeSet of the owned nodes among `nodes` (global ids: a set, a list, a range); every owned node -> the set -1"""
         if isinstance(nodes, NodeSet):
