@@ -375,6 +375,10 @@ int pyn_product_choose(int br, int bc, int npat, int maxw, int64_t nnzb, int64_t
  *   [6] 1 when 1 / diagonal was written with the rows
  *   [7] assemblies of this context so far */
 int pyn_assemble_last(pyn_ctx* ctx, int64_t* info);
+/* ... and, when that assembly ran the rows kernel of rectilinear Q1 lattices (AK_LATTICE, shape 0, closed form), which form of it:
+ * info[2]: [0] 0: another kernel, 1: one workgroup per x-line (PYNAMA_LATTICE_ROWS_ONESHOT), 2: the persistent form;
+ *          [1] the workgroups it launched */
+int pyn_assemble_last_rows(pyn_ctx* ctx, int64_t* info);
 /* The rule that picks the family (host only: no context, no device, no environment) -- what every assembly applies, once, to its
  * request, the facts of the context and the PYNAMA_* switches of the moment.  The three arrays hold plain integers in the order
  * pyn_assemble_choose_layout writes into buf ("request:a,b,..;facts:..;knobs:.."): request = form, variant, which of K / Krhs / Rw /

@@ -13,7 +13,9 @@ import sys
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("PYNAMA_LIB_PATH") or os.path.join(_HERE, "libpynama_hip.so")   # (the override: A/B of two builds, tools/)
+_DEFAULT_LIB_PATH = os.path.join(_HERE, "libpynama_hip.so")
+LIB_PATH = os.environ.get("PYNAMA_LIB_PATH") or _DEFAULT_LIB_PATH   # (the override: A/B of two builds, tools/)
+_NEWER_SYMBOLS = ("pyn_assemble_last_rows",)   # diagnostics an older build under PYNAMA_LIB_PATH may lack (never the in-tree library)
 CSRC = os.path.join(_HERE, "csrc")
 
 # enums of include/pynama_hip.h
@@ -132,6 +134,7 @@ SIGNATURES = {
     "pyn_product_last": [_P, _pi64],
     "pyn_product_choose": [_I] * 4 + [_L, _L] + [_I] * 7 + [_D, _I, _I] + [C.POINTER(_I)] * 4,
     "pyn_assemble_last": [_P, _pi64],
+    "pyn_assemble_last_rows": [_P, _pi64],
     "pyn_assemble_choose": [_pi64, _pi64, _pi64, _pi64],
     "pyn_assemble_choose_layout": [C.c_char_p, _I],
     "pyn_matfree_apply": [_P, _I, _I, _I],
@@ -182,6 +185,8 @@ def load_library():
             "(or `make -C pynama_amd/csrc`). pynama_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name, args in SIGNATURES.items():
+        if name in _NEWER_SYMBOLS and LIB_PATH != _DEFAULT_LIB_PATH and not hasattr(lib, name):
+            continue                     # an older build loaded for an A/B: the diagnostics it predates report "unknown"
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.argtypes = args
         fn.restype = C.c_int
@@ -703,10 +708,16 @@ class Context:
 
     def assemble_last(self):
         """what the most recent numeric assembly of this context launched: {'kind' (index into ASSEMBLY_KINDS), 'shape' (tile id, or
-        rows per run), 'k_closed', 'rw_closed', 'generic' (sub-variant), 'krhs_completed', 'dinv', 'count' (running count)}"""
-        info = np.zeros(8, np.int64)
+        rows per run), 'k_closed', 'rw_closed', 'generic' (sub-variant), 'krhs_completed', 'dinv', 'count' (running count),
+        'rows_form' (the rows kernel of rectilinear Q1 lattices: 0 did not run, 1 one workgroup per x-line, 2 persistent),
+        'rows_grid' (its workgroups); both -1 from an older build under PYNAMA_LIB_PATH that does not record them}"""
+        info, rows = np.zeros(8, np.int64), np.zeros(2, np.int64)
         _check(self.lib.pyn_assemble_last(self.h, info))
-        return {k: int(v) for k, v in zip(_ASM_LAST_KEYS, info)}
+        if hasattr(self.lib, "pyn_assemble_last_rows"):
+            _check(self.lib.pyn_assemble_last_rows(self.h, rows))
+        else:                                # (an older build under PYNAMA_LIB_PATH)
+            rows[:] = -1
+        return dict({k: int(v) for k, v in zip(_ASM_LAST_KEYS, info)}, rows_form=int(rows[0]), rows_grid=int(rows[1]))
 
     def mesh_ho_lattice(self):
         """(ngl, nx, ny, nz) when the mesh is a box lattice of order ngl >= 4 that the matrix-free KLE operator accepts

@@ -1083,6 +1083,8 @@ int asm_finish(pyn_ctx* c, const AsmPlan& P, const AsmRequest& rq) {
   const int64_t r[7] = {P.kind, P.shape, P.k_closed, P.rw_closed, P.kind == AK_GENERIC ? rq.generic : 0, rq.krhs_completed, rq.dinv_written};
   std::copy(r, r + 7, c->asm_last);
   c->asm_last[7] += 1;
+  c->asm_last_rows[0] = rq.rows_form;
+  c->asm_last_rows[1] = rq.rows_grid;
   return PYN_OK;
 }
 
@@ -1419,6 +1421,12 @@ extern "C" int pyn_assemble_scalar(pyn_ctx* c, int form, int Aid, int Arhs, int 
 extern "C" int pyn_assemble_last(pyn_ctx* c, int64_t* info) {
   PYN_CHECK(c && info, "NULL argument");
   std::copy(c->asm_last, c->asm_last + 8, info);
+  return PYN_OK;
+}
+
+extern "C" int pyn_assemble_last_rows(pyn_ctx* c, int64_t* info) {
+  PYN_CHECK(c && info, "NULL argument");
+  std::copy(c->asm_last_rows, c->asm_last_rows + 2, info);
   return PYN_OK;
 }
 

@@ -529,6 +529,206 @@ __global__ void __launch_bounds__(NT) assemble_q1_lattice_rows_kernel(LatArgs T,
   }
 }
 
+// ---- once per Dirichlet set: the word of every x-line (pyn_lattice_rows.h: class + what its neighbouring lines impose at x = 0 and
+// x = nx - 1), one wave per line, cached under the bc stamp like the tiles' map (lattice_rows_map_ensure)
+__global__ void __launch_bounds__(64) lattice_rows_map_kernel(LatArgs T, uint32_t* __restrict__ map) {
+  __shared__ uint32_t bits;
+  const int line = blockIdx.x, y = line % T.ny, pl = T.p_own0 + line / T.ny;
+  if (threadIdx.x == 0) bits = 0;
+  __syncthreads();
+  const uint32_t mine = lat_rows_line_bits(T.nx, T.ny, y, lat_zcode(T, pl), (int)threadIdx.x, 64, [&](int dy, int dz, int x) {
+    return T.bcmask[(int64_t)lat_plane(T, pl + dz) + (int64_t)(y + dy) * T.nx + x] != 0;
+  });
+  if (mine) atomicOr(&bits, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) map[line] = lat_rows_word(bits);
+}
+
+// The walking form of the rows kernel: `grid` workgroups walk the x-lines by lat_rows_sched (one contiguous range of lines per XCD,
+// dealt round-robin inside it).  By default there is a workgroup per line -- every persistent shape measured slower, DESIGN.md 8 --
+// and PYNAMA_LATTICE_ROWS_MAX_GRID makes the loop turn.  What differs from the one-shot kernel above:
+//  - lmap (lattice_rows_map_kernel): a line of class 0 or 1 loads no flag byte; its rows x = 2 .. nx - 3 are stored with no flag
+//    read, no vote and no branch, and the four other rows take their flags out of the line's word.  Class 2 (and every line when
+//    lmap is null under a Dirichlet set) stages its flag rows and runs the one-shot kernel's loop;
+//  - the line's word and its y / z pairs sit at wave-uniform addresses: scalar loads, requested first of all;
+//  - the x axis' pairs are staged once per workgroup, not once per line.
+// STD: T.std_lat, plane bases, z codes and row offsets by arithmetic -- no vector load is compiled in outside the staging (a register
+// such a load may still own costs every store phase a wait for the stores before it).
+// Every entry keeps the one-shot kernel's formula and routing: the two forms write the same bits.
+static size_t lat_rows_walk_lds(int nx) {   // the x axis' pairs [nx][3] | (a, b)[9] | flag bytes [9][nx + 2]
+  return (size_t)nx * 48 + 144 + (((size_t)9 * (nx + 2) + 15) & ~(size_t)15);
+}
+
+struct LatRowsLine {   // wave-uniform: what the store phase of a line reads besides LDS
+  int y, zo, zcode;
+  uint32_t word;
+  int64_t base;
+};
+
+// (8 workgroups of 256 threads per CU need at most 64 VGPRs and 80 SGPRs: the arguments alone would take more)
+template <int NT, bool STD>
+__global__ void __launch_bounds__(NT, 2048 / NT) __attribute__((amdgpu_num_sgpr(80)))
+assemble_q1_lattice_rows_walk_kernel(LatArgs T, const double* __restrict__ km, const uint32_t* __restrict__ lmap, int n_lines) {
+  extern __shared__ __align__(16) double lds[];
+  const int tid = threadIdx.x, nx = T.nx, ny = T.ny, W = nx + 2;
+  double2* skx = reinterpret_cast<double2*>(lds);                          // [nx][3]: (K1, M1) of (x, dx + 1)
+  double2* abl = skx + 3 * nx;                                             // [9]
+  unsigned char* fll = reinterpret_cast<unsigned char*>(abl + 9);          // [9][W]
+  const double2* __restrict__ kmx = reinterpret_cast<const double2*>(km);
+  const double2* __restrict__ kmy = kmx + 3 * nx;
+  const double2* __restrict__ kmz = kmy + 3 * ny;
+  const uint32_t no_map = T.bcmask ? 2u : 0u;   // no map: every line class 2 under a Dirichlet set, class 0 without one
+
+  // everything of a line that sits at a wave-uniform address
+  auto fetch = [&](int line) {
+    LatRowsLine L;
+    L.y = line % ny;
+    L.zo = line / ny;
+    L.zcode = lat_zcode<STD>(T, T.p_own0 + L.zo);
+    L.word = lmap ? lmap[line] : no_map;
+    L.base = STD ? lat_rowptr_std(T, 0, L.y, L.zo) : T.rowptr[(int64_t)T.P[T.p_own0 + L.zo] + (int64_t)L.y * nx];
+    return L;
+  };
+  // (a, b) of the line's slot groups and, class 2, the flag rows of its neighbouring lines -> LDS
+  auto stage = [&](const LatRowsLine& L) {
+    const int y = L.y, pl = T.p_own0 + L.zo, cy = 3 - (y == 0) - (y == ny - 1), cc = cy * (L.zcode & 3);
+    if (lat_rows_class(L.word) == 2) {   // (wave-uniform)
+      int rowoff;   // first node of flag row s, computed by lane s of every wave and handed round as a scalar
+      {
+        int dy, dz;
+        lat_rows_group(min(min(tid & 63, 8), cc - 1), cy, y != 0, L.zcode, dy, dz);
+        rowoff = lat_plane<STD>(T, pl + dz) + (y + dy) * nx;
+      }
+      for (int i0 = 0; i0 < W; i0 += NT) {
+        const int i = i0 + tid, xi = min(max(i - 1, 0), nx - 1);
+        unsigned char f[9];
+#pragma unroll
+        for (int s = 0; s < 9; ++s) f[s] = T.bcmask[(int64_t)__builtin_amdgcn_readlane(rowoff, s) + xi];
+        if (i < W) {
+          const bool inx = i >= 1 && i <= nx;
+#pragma unroll
+          for (int s = 0; s < 9; ++s) fll[s * W + i] = (inx && f[s] != 0) ? 1 : 0;
+        }
+      }
+    }
+    const double2 y0 = kmy[y * 3], y1 = kmy[y * 3 + 1], y2 = kmy[y * 3 + 2];        // (uniform addresses: scalar loads)
+    const double2 z0 = kmz[pl * 3], z1 = kmz[pl * 3 + 1], z2 = kmz[pl * 3 + 2];
+    if (tid < cc) {
+      int dy, dz;
+      lat_rows_group(tid, cy, y != 0, L.zcode, dy, dz);
+      const double2 fy = dy < 0 ? y0 : dy == 0 ? y1 : y2, fz = dz < 0 ? z0 : dz == 0 ? z1 : z2;
+      abl[tid] = make_double2(fy.y * fz.y, fma(fy.x, fz.y, fy.y * fz.x));
+    }
+  };
+
+  // one line out of LDS
+  auto store = [&](const LatRowsLine& L) {
+    const int y = L.y, zo = L.zo, zcode = L.zcode, cy = 3 - (y == 0) - (y == ny - 1), cz = zcode & 3, cc = cy * cz;
+    const int tself = ((zcode >> 2) & 3) == 1 ? (y != 0) : cy + (y != 0);   // the line's own slot group: dz = 0 is kz = 0 or 1
+    double* __restrict__ outA = T.A + L.base;
+    double* __restrict__ outR = T.Arhs ? T.Arhs + L.base : nullptr;
+    const bool zeros = outR && !T.rhs_clean;   // Arhs zeros have to be written (a clean target holds them already)
+    const int len = lat_rows_line_len(nx, cy, cz), nint = lat_rows_interior_len(nx, cc);
+    const uint32_t magic = lat_rows_magic(cc);
+    double* __restrict__ dv = T.dinv ? T.dinv + ((int64_t)zo * ny + y) * nx : nullptr;
+    if (lat_rows_class(L.word) == 2) {   // (wave-uniform) the one-shot kernel's loop
+      const unsigned char* fself = fll + tself * W + 1;
+      if (tid < nint) {
+        const LatRowsStride st = lat_rows_stride(NT, cc);
+        LatRowsPos p = lat_rows_interior(tid, cc, magic);
+        double* __restrict__ pA = outA + 2 * cc;
+        double* __restrict__ pR = outR ? outR + 2 * cc : nullptr;
+        for (int m = tid; m < nint; m += NT) {
+          const double2 k = skx[__mul24(p.x, 3) + p.kx], c = abl[p.t];
+          const unsigned fr = fself[p.x], fc = fll[__mul24(p.t, W) + p.x + p.kx];
+          const double v = fma(k.x, c.x, k.y * c.y);
+          if (!__any(fr | fc)) {
+            pA[m] = v;
+            if (zeros) pR[m] = 0.0;
+          } else {
+            const double idv = (p.t == tself && p.kx == 1) ? 1.0 : 0.0;
+            pA[m] = fr ? idv : (fc ? 0.0 : v);
+            if (pR) pR[m] = fr ? idv : (fc ? -v : 0.0);
+          }
+          lat_rows_step(p, st, cc);
+        }
+      }
+      if (tid < 4 * cc) {
+        const LatRowsEnd r = lat_rows_end(tid, nx, cc, len);
+        const double2 k = skx[3 * r.x + r.dx + 1], c = abl[r.t];
+        const unsigned fr = fself[r.x], fc = fll[r.t * W + r.x + r.dx + 1];
+        const double v = fma(k.x, c.x, k.y * c.y);
+        const double idv = (r.t == tself && r.dx == 0) ? 1.0 : 0.0;
+        outA[r.e] = fr ? idv : (fc ? 0.0 : v);
+        if (outR && (zeros || fr || fc)) outR[r.e] = fr ? idv : (fc ? -v : 0.0);
+      }
+      if (dv) {
+        const double2 c = abl[tself];
+        for (int x = tid; x < nx; x += NT) {
+          const double2 k = skx[x * 3 + 1];
+          dv[x] = fself[x] ? 1.0 : 1.0 / fma(k.x, c.x, k.y * c.y);
+        }
+      }
+      return;
+    }
+    // classes 0 and 1.  The rows x = 2 .. nx - 3: entries [3 cc, nint - 3 cc) of the interior, no flag anywhere near them
+    const int nfree = nint - 6 * cc;
+    if (tid < nfree) {
+      const LatRowsStride st = lat_rows_stride(NT, cc);
+      LatRowsPos p = lat_rows_interior(3 * cc + tid, cc, magic);
+      double* __restrict__ pA = outA + 5 * cc;
+      double* __restrict__ pR = outR ? outR + 5 * cc : nullptr;
+      for (int m = tid; m < nfree; m += NT) {
+        const double2 k = skx[__mul24(p.x, 3) + p.kx], c = abl[p.t];
+        pA[m] = fma(k.x, c.x, k.y * c.y);
+        if (zeros) pR[m] = 0.0;
+        lat_rows_step(p, st, cc);
+      }
+    }
+    // one entry of the four other rows: its flags are bits of the word
+    auto edge = [&](int e, int x, int t, int dx) {
+      const double2 k = skx[3 * x + dx + 1], c = abl[t];
+      const unsigned fr = lat_rows_word_flag(L.word, tself, x, nx), fc = lat_rows_word_flag(L.word, t, x + dx, nx);
+      const double v = fma(k.x, c.x, k.y * c.y);
+      const double idv = (t == tself && dx == 0) ? 1.0 : 0.0;
+      outA[e] = fr ? idv : (fc ? 0.0 : v);
+      if (outR && (zeros || fr || fc)) outR[e] = fr ? idv : (fc ? -v : 0.0);
+    };
+    const int nedge = min(nint, 6 * cc);   // the rows x = 1 and x = nx - 2 (one row when nx = 3, none when nx = 2)
+    if (tid < nedge) {
+      const int m = tid < 3 * cc ? tid : nint - 6 * cc + tid;
+      const LatRowsPos p = lat_rows_interior(m, cc, magic);
+      edge(2 * cc + m, p.x, p.t, p.kx - 1);
+    }
+    if (tid < 4 * cc) {   // the rows x = 0 and x = nx - 1
+      const LatRowsEnd r = lat_rows_end(tid, nx, cc, len);
+      edge(r.e, r.x, r.t, r.dx);
+    }
+    if (dv) {
+      const double2 c = abl[tself];
+      for (int x = tid; x < nx; x += NT) {
+        const double2 k = skx[x * 3 + 1];
+        dv[x] = lat_rows_word_flag(L.word, tself, x, nx) ? 1.0 : 1.0 / fma(k.x, c.x, k.y * c.y);
+      }
+    }
+  };
+
+  int line = lat_rows_sched(blockIdx.x, gridDim.x, n_lines, 0);
+  if (line < 0) return;   // (more workgroups than lines in this XCD's range)
+  LatRowsLine L = fetch(line);   // (the first line's scalar loads go out in front of the x axis' pairs)
+  for (int q = tid; q < 3 * nx; q += NT) skx[q] = kmx[q];
+  stage(L);
+  for (int trip = 1;; ++trip) {
+    __syncthreads();
+    store(L);
+    line = lat_rows_sched(blockIdx.x, gridDim.x, n_lines, trip);
+    if (line < 0) break;
+    L = fetch(line);
+    __syncthreads();   // every wave has read the last line's (a, b) and flags
+    stage(L);
+  }
+}
+
 // y_e = L_e x_e for a parallelepiped WITHOUT forming L_e: in the Haar basis of each axis ((v0, v1) -> (s, d) = (v0 + v1,
 // v1 - v0)) the 1-D factors of the trilinear element are monomial -- mass 2/3 [[1, 1/2], [1/2, 1]] -> diag(3, 1)/3... i.e.
 // int N N -> (s, d) |-> (3 s, d)/3, int N' N' -> (0, d), int N' N -> s |-> d', its transpose d |-> s' -- so
@@ -1951,13 +2151,57 @@ static int pyn_lattice_axes_ensure(pyn_ctx* c, const AsmKnobs& k) {
 
 // rows kernel of a rectilinear lattice (c->lat.rect == 1): one workgroup per NL consecutive x-lines of an owned plane
 template <int NL, int NT>
-static int launch_lattice_rows(pyn_ctx* c, LatArgs& T) {
+static int launch_lattice_rows(pyn_ctx* c, LatArgs& T, AsmRequest& rq) {
   const size_t lds = lat_rows_lds(T.nx, NL);
   const int64_t n_groups = (int64_t)((T.ny + NL - 1) / NL) * T.n_own;
   PYN_CHECK(n_groups > 0 && n_groups < (int64_t)INT32_MAX, "lattice rows kernel: %lld workgroups", (long long)n_groups);
   const double* km = c->lat.d_axes.get() + lat_rows_tab_base(T.nx, T.ny, T.npl);
   assemble_q1_lattice_rows_kernel<NL, NT><<<(int)n_groups, NT, lds, c->stream>>>(T, km);
   PYN_HIP(hipGetLastError());
+  rq.rows_form = 1;
+  rq.rows_grid = (int)n_groups;
+  return PYN_OK;
+}
+
+// The words of the x-lines (lattice_rows_map_kernel) for the current Dirichlet set: cached on the lattice view under the context's bc
+// stamp, built into a local buffer and committed when the kernel has been enqueued (as lattice_tilebc_ensure does)
+static int lattice_rows_map_ensure(pyn_ctx* c, const LatArgs& T, int n_lines) {
+  Lattice& L = c->lat;
+  if (L.d_rowsmap && L.rowsmap_stamp == c->bc_stamp) return PYN_OK;
+  DevBuf<uint32_t> map;
+  PYN_HIP(map.alloc((size_t)n_lines));
+  lattice_rows_map_kernel<<<n_lines, 64, 0, c->stream>>>(T, map);
+  PYN_HIP(hipGetLastError());
+  L.d_rowsmap = std::move(map);   // (freeing the old map waits for the device)
+  L.rowsmap_stamp = c->bc_stamp;
+  return PYN_OK;
+}
+
+// ... its walking form: a workgroup per line (PYNAMA_LATTICE_ROWS_MAX_GRID: at most so many workgroups, each walking lines by
+// lat_rows_sched -- tests: the loop turns on small meshes; with the workgroups the device holds at once, pyn_kernel_occupancy x CUs,
+// this is the persistent launch DESIGN.md 8 measured)
+template <bool STD>
+static int launch_lattice_rows_walk(pyn_ctx* c, const AsmKnobs& k, LatArgs& T, AsmRequest& rq) {
+  const size_t lds = lat_rows_walk_lds(T.nx);
+  const int64_t n_lines = (int64_t)T.ny * T.n_own;
+  PYN_CHECK(n_lines > 0 && n_lines < (int64_t)INT32_MAX, "lattice rows kernel: %lld x-lines", (long long)n_lines);
+  const uint32_t* lmap = nullptr;
+  if (T.bcmask && !k.lattice_rows_no_classes) {
+    PYN_TRY(lattice_rows_map_ensure(c, T, (int)n_lines));
+    lmap = c->lat.d_rowsmap;
+  }
+  int64_t grid = n_lines;
+  if (k.lattice_rows_max_grid > 0) grid = std::min<int64_t>(grid, k.lattice_rows_max_grid);
+  if (k.lattice_rows_max_grid < 0) {   // "what the device holds at once"
+    int per_cu = 0;
+    PYN_TRY(pyn_kernel_occupancy(c, reinterpret_cast<const void*>(assemble_q1_lattice_rows_walk_kernel<256, STD>), 256, lds, &per_cu));
+    grid = std::min<int64_t>(grid, (int64_t)std::max(1, per_cu) * 256);   // 256 CUs (gfx950)
+  }
+  const double* km = c->lat.d_axes.get() + lat_rows_tab_base(T.nx, T.ny, T.npl);
+  assemble_q1_lattice_rows_walk_kernel<256, STD><<<(int)grid, 256, lds, c->stream>>>(T, km, lmap, (int)n_lines);
+  PYN_HIP(hipGetLastError());
+  rq.rows_form = 2;
+  rq.rows_grid = (int)grid;
   return PYN_OK;
 }
 
@@ -2072,11 +2316,14 @@ int pyn_assemble_lattice(pyn_ctx* c, AsmRequest& rq, const AsmKnobs& k, const As
   PYN_CHECK(!k.lattice_rows_require || !no_rows, "PYNAMA_LATTICE_ROWS_REQUIRE: the rows kernel of rectilinear lattices does not apply (%s)",
             no_rows);
   if (!no_rows) {
-    if (rows_nl == 2) return launch_lattice_rows<2, 256>(c, T);
+    // the walking form unless the one-shot form or one of its shapes is asked for
+    if (!k.lattice_rows_oneshot && rows_nl == 1 && k.lattice_rows_threads == 0 && lat_rows_walk_lds(T.nx) <= 64 * 1024)
+      return T.std_lat ? launch_lattice_rows_walk<true>(c, k, T, rq) : launch_lattice_rows_walk<false>(c, k, T, rq);
+    if (rows_nl == 2) return launch_lattice_rows<2, 256>(c, T, rq);
     switch (k.lattice_rows_threads) {
-      case 128: return launch_lattice_rows<1, 128>(c, T);
-      case 512: return launch_lattice_rows<1, 512>(c, T);
-      default: return launch_lattice_rows<1, 256>(c, T);
+      case 128: return launch_lattice_rows<1, 128>(c, T, rq);
+      case 512: return launch_lattice_rows<1, 512>(c, T, rq);
+      default: return launch_lattice_rows<1, 256>(c, T, rq);
     }
   }
   if (k.lattice_ablate == 64) T.bcmask = nullptr;   // diagnostics: no Dirichlet flag loads (timing only: imposed rows come out wrong)

@@ -545,6 +545,8 @@ static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
   c->lat.d_axes.reset();
   c->lat.d_tilebc.reset();        // ... and the Dirichlet map of its tiles to the old lattice
   c->lat.tilebc_stamp = -1;
+  c->lat.d_rowsmap.reset();       // ... and the words of its x-lines
+  c->lat.rowsmap_stamp = -1;
   for (int k = 0; k < PYN_MATFREE_SLOTS; ++k) {   // the matrix-free operators
     c->mf_mask[k].reset();
     c->mf_set[k] = false;

@@ -246,6 +246,8 @@ struct Lattice {
   DevBuf<uint32_t> d_tilebc;   // one bit per tile of the scalar tile kernel: its node box holds an imposed node ...
   int64_t tilebc_stamp = -1;   // ... for this Dirichlet set (pyn_ctx::bc_stamp)
   int tilebc_shape = -1;       // ... and this tile shape (TX << 16 | TY << 8 | TZ)
+  DevBuf<uint32_t> d_rowsmap;  // one word per owned x-line of the rows kernel's walking form: class + end flags (pyn_lattice_rows.h) ...
+  int64_t rowsmap_stamp = -1;  // ... for this Dirichlet set
 };
 
 // View of orders ngl 2 and 3 (pyn_assemble_ho3.hip: row-run assembly; ngl 3, the order all of the reference's cases run,
@@ -442,6 +444,7 @@ struct pyn_ctx {
   DevBuf<double> d_work;
   std::vector<hipEvent_t> prof_ev;  // event pool for per-kernel timing
   int64_t asm_last[8] = {0};     // pyn_assemble_last: what the most recent numeric assembly launched (pyn_assemble.hip)
+  int64_t asm_last_rows[2] = {0};   // pyn_assemble_last_rows: ... form and grid of the lattice rows kernel, if that is what ran
   // per-context kernel attributes (pyn_kernel_lds / pyn_kernel_occupancy): a second context on another device sets its own
   std::map<const void*, size_t> kern_lds;                      // dynamic-LDS limit this context has raised the kernel to
   std::map<std::pair<const void*, size_t>, int> kern_occ;      // workgroups per CU of (kernel, dynamic LDS)
@@ -604,7 +607,8 @@ constexpr int PYN_HO3_MAX_TERMS = 32;   // operator terms the row-run kernels ca
 #define PYN_ASM_LAUNCH_KNOBS(F, I) F(no_lattice_axes, "PYNAMA_NO_LATTICE_AXES") F(lattice_axes_require, "PYNAMA_LATTICE_AXES_REQUIRE") \
   F(no_lattice_tilebc, "PYNAMA_NO_LATTICE_TILEBC") F(no_lattice_rows, "PYNAMA_NO_LATTICE_ROWS")                                      \
   F(lattice_rows_require, "PYNAMA_LATTICE_ROWS_REQUIRE") I(lattice_rows_lines, "PYNAMA_LATTICE_ROWS_LINES", 0)               \
-  I(lattice_rows_threads, "PYNAMA_LATTICE_ROWS_THREADS", 0)
+  I(lattice_rows_threads, "PYNAMA_LATTICE_ROWS_THREADS", 0) F(lattice_rows_oneshot, "PYNAMA_LATTICE_ROWS_ONESHOT")                      \
+  I(lattice_rows_max_grid, "PYNAMA_LATTICE_ROWS_MAX_GRID", 0) F(lattice_rows_no_classes, "PYNAMA_LATTICE_ROWS_NO_CLASSES")
 struct AsmKnobs {
 #define PYN_F(f, e) bool f = false;
 #define PYN_I(f, e, d) int f = d;
@@ -646,6 +650,7 @@ struct AsmRequest {
   bool dinv_written = false;        // a kernel filled dinv
   bool krhs_completed = false;      // the compact Krhs was left to the completion pass (generic kernel over the imposed elements)
   int generic = 0;                  // sub-variant of the last generic launch
+  int rows_form = 0, rows_grid = 0; // the lattice rows kernel ran: 1 the one-shot form, 2 the walking form (a class per line); its workgroups
 };
 
 struct AsmPlan {

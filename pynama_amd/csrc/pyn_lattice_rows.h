@@ -111,6 +111,48 @@ PYN_AX_HD inline LatRowsEnd lat_rows_end(int j, int nx, int cc, int len) {
   return r;
 }
 
+// ---- the persistent form: `grid` workgroups walk the n x-lines (line = zo ny + y).  Workgroups are dealt round-robin to the 8 XCDs,
+// so the workgroups wg = j (mod 8) form group j and share one L2; group j owns ONE contiguous range of lines -- the range
+// xcd_contiguous_tile (pyn_lattice.h) gives it when there is a workgroup per line -- and inside it workgroup w of the group's g takes
+// the lines w, w + g, w + 2 g, ..: the group's store front stays a narrow moving window.  Fewer than 8 workgroups: as many groups.
+// Returns the line of workgroup wg's trip, -1 when it has none left.
+PYN_AX_HD inline int lat_rows_sched(int wg, int grid, int n, int trip) {
+  const int ng = grid < 8 ? grid : 8, j = wg % ng, w = wg / ng;
+  const int g = (grid - j + ng - 1) / ng;                       // workgroups of group j
+  const int q = n / ng, r = n % ng, cnt = q + (j < r);          // its lines: [lo, lo + cnt)
+  const int64_t i = w + (int64_t)trip * g;
+  return i < cnt ? j * q + (j < r ? j : r) + (int)i : -1;
+}
+
+// ---- a word per line for the current Dirichlet set (lattice_rows_map_kernel): what the <= 9 neighbouring x-lines, the line itself
+// included, impose.  An imposed node at x of the line behind slot group t sets bit 2 + t (x = 0), bit 11 + t (x = nx - 1) or bit 31
+// (any other x); the word is these bits with the class in bits 0-1 (bit 31 dropped):
+//   0: no imposed node -- 1: imposed nodes at x = 0 and x = nx - 1 only -- 2: anything else.
+// In classes 0 and 1 the rows x = 2 .. nx - 3 meet no flag (their columns lie in 1 .. nx - 2), and every flag the other four rows
+// meet is a bit of the word: such a line loads no flag byte at all.
+PYN_AX_HD inline uint32_t lat_rows_node_bits(int x, int nx, int t, bool imposed) {
+  return !imposed ? 0u : x == 0 ? 1u << (2 + t) : x == nx - 1 ? 1u << (11 + t) : 1u << 31;
+}
+// the bits of the nodes x = x0, x0 + xstep, .. of every neighbouring line of line y in a plane with z code zcode;
+// imposed(dy, dz, x): is node x of the line (y + dy, plane + dz) imposed?  (partial results of several callers are OR-ed)
+template <class F>
+PYN_AX_HD inline uint32_t lat_rows_line_bits(int nx, int ny, int y, int zcode, int x0, int xstep, F imposed) {
+  const int cy = 3 - (y == 0) - (y == ny - 1), cc = cy * (zcode & 3);
+  uint32_t bits = 0;
+  for (int t = 0; t < cc; ++t) {
+    int dy, dz;
+    lat_rows_group(t, cy, y != 0, zcode, dy, dz);
+    for (int x = x0; x < nx; x += xstep) bits |= lat_rows_node_bits(x, nx, t, imposed(dy, dz, x));
+  }
+  return bits;
+}
+PYN_AX_HD inline uint32_t lat_rows_word(uint32_t bits) { return (bits & 0x7ffffffcu) | ((bits >> 31) ? 2u : bits ? 1u : 0u); }
+PYN_AX_HD inline int lat_rows_class(uint32_t word) { return (int)(word & 3u); }
+// class 0 / 1: is node xx of the line behind slot group t imposed?
+PYN_AX_HD inline unsigned lat_rows_word_flag(uint32_t word, int t, int xx, int nx) {
+  return xx == 0 ? (word >> (2 + t)) & 1u : xx == nx - 1 ? (word >> (11 + t)) & 1u : 0u;
+}
+
 // ---- the 1-D P1 tables behind the values: per axis and node i six doubles, (K1[i][d], M1[i][d]) for the neighbour d - 1 = -1, 0, +1,
 //   K1[i] = (-1/h[i-1], 1/h[i-1] + 1/h[i], -1/h[i]),  M1[i] = (h[i-1]/6, (h[i-1] + h[i])/3, h[i]/6),  h[i] = |c[i+1] - c[i]|,
 // the terms of a missing neighbour dropped.  They follow the three axis tables in one buffer, x | y | z (z by plane position in the
