@@ -576,10 +576,37 @@ int pyn_probe_get(pyn_ctx* ctx, int probe_id, int32_t* cell, double* xi);
 int pyn_probe_sample(pyn_ctx* ctx, int probe_id, int vec_id, double* out);
 int pyn_probe_destroy(pyn_ctx* ctx, int probe_id);
 
+/* ---- mesh integrals (pyn_integrals.hip) -------------------------------------------------------
+ * The moments of a nodal field over any quadrilateral / hexahedral mesh of order 2 <= ngl <= pyn_ho_matfree_max_ngl(dim), on one
+ * rank, in one pass over the cells: u = a, or u = a - b when vec_b >= 0 (the difference is formed per node, with one rounding,
+ * before anything else).  The field of a cell is its tensor Lagrange interpolant on the Lobatto(ngl) nodes; the geometry is the
+ * multilinear image of the cell's 2^dim corners (the first 2^dim entries of the connectivity row, as for the probes), its Jacobian
+ * formed at every quadrature point.
+ * rule: PYN_RULE_NODAL, the Lobatto(ngl) nodes themselves (collocation: the reference's lumped nodal weights); PYN_RULE_GAUSS,
+ * Gauss-Legendre with ngl + 1 points per axis: volume, value and square are exact on every multilinear cell, the gradient moments
+ * on affine cells.
+ * out, with bs the block size of the vector (1 .. 6) and dim_w = 1 (2-D) / 3 (3-D):
+ *   volume          int 1
+ *   value[bs]       int u_c
+ *   square[bs]      int u_c^2
+ *   grad2[bs]       int |grad u_c|^2              with_grad
+ *   div2            int (div u)^2                 with_grad and bs == dim
+ *   curl2[dim_w]    int (curl u)_k^2              with_grad and bs == dim; 2-D: d u_1 / dx - d u_0 / dy, 3-D: the usual three
+ * n_out = pyn_integrate_len(dim, bs, with_grad) entries (0 for a dim or bs that has none).
+ * No floating-point atomics: a cell's sums depend on the cell alone, a fixed number of consecutive cells is accumulated in cell
+ * order into one partial, a one-workgroup kernel sums the partials in a fixed order.  The result is a function of the mesh, the
+ * vectors and the source constants; PYNAMA_INTEGRATE_MAX_GRID (read at every call) caps the grid and does not change a bit of it.
+ * A NaN in the field gives NaN moments (volume stays), not an error.  Refused with a message: simplices; several ranks or ghost
+ * nodes; nn that is not ngl^dim; ngl above the limit; a vector whose node count is not the mesh's; vec_b of another block size; an
+ * unknown rule; det J <= 0 at a quadrature point (the message names the lowest such cell).  pyn_timers_get: PYN_T_INTEGRATE. */
+enum { PYN_RULE_NODAL = 0, PYN_RULE_GAUSS = 1 };
+int pyn_integrate(pyn_ctx* ctx, int rule, int with_grad, int vec_a, int vec_b /* -1: none */, double* out, int* n_out);
+int pyn_integrate_len(int dim, int bs, int with_grad);
+
 /* ---- timers -------------------------------------------------------------------------------
  * Device time (HIP events on the context stream) of the last call of each phase, in ms.
  * Replaces the tic/toc log of src/run_case.py:156-162. */
-enum { PYN_T_SYMBOLIC = 0, PYN_T_ASSEMBLE = 1, PYN_T_SPMV = 2, PYN_T_SOLVE = 3, PYN_T_COUNT = 8 };
+enum { PYN_T_SYMBOLIC = 0, PYN_T_ASSEMBLE = 1, PYN_T_SPMV = 2, PYN_T_SOLVE = 3, PYN_T_INTEGRATE = 4, PYN_T_COUNT = 8 };
 int pyn_timers_get(pyn_ctx* ctx, double* ms, int n);
 
 #ifdef __cplusplus

@@ -27,7 +27,8 @@ PC_NONE, PC_JACOBI, PC_MG = 0, 1, 2
 MG_MAX_LEVELS = 16
 TS_MAX_STAGES = 8
 NORM_PRECONDITIONED, NORM_UNPRECONDITIONED, NORM_NATURAL = 0, 1, 2
-T_SYMBOLIC, T_ASSEMBLE, T_SPMV, T_SOLVE = 0, 1, 2, 3
+T_SYMBOLIC, T_ASSEMBLE, T_SPMV, T_SOLVE, T_INTEGRATE = 0, 1, 2, 3, 4
+RULE_NODAL, RULE_GAUSS = 0, 1
 # PYN_FIELD_*: the closed-form fields of cases/custom_func.py that pyn_field_eval evaluates on the device
 (FIELD_TG2D_VEL, FIELD_TG2D_VORT, FIELD_TG3D_VEL, FIELD_TG3D_VORT, FIELD_TG3D_CONV, FIELD_TG3D_DIFF,
  FIELD_SEN2D_VEL, FIELD_SEN2D_VORT, FIELD_SEN2D_CONV, FIELD_SEN2D_DIFF) = range(10)
@@ -160,6 +161,8 @@ SIGNATURES = {
     "pyn_probe_get": [_P, _I, _pi32, _pf64],
     "pyn_probe_sample": [_P, _I, _I, _pf64],
     "pyn_probe_destroy": [_P, _I],
+    "pyn_integrate": [_P, _I, _I, _I, _I, _pf64, C.POINTER(_I)],
+    "pyn_integrate_len": [_I, _I, _I],
     "pyn_timers_get": [_P, _pf64, _I],
 }
 
@@ -224,6 +227,11 @@ def device_count() -> int:
 def ho_matfree_max_ngl(dim) -> int:
     """largest order (ngl) the matrix-free KLE operator of high-order box lattices has a kernel for"""
     return load_library().pyn_ho_matfree_max_ngl(int(dim))
+
+
+def integrate_len(dim, bs, grad=False) -> int:
+    """entries of Context.integrate for a vector of block size bs on a dim-D mesh (pyn_integrate_len; 0: no such dim or bs)"""
+    return load_library().pyn_integrate_len(int(dim), int(bs), 1 if grad else 0)
 
 
 def ho_tables_1d(ngl):
@@ -899,7 +907,15 @@ class Context:
         if self.h:
             _check(self.lib.pyn_probe_destroy(self.h, int(pid)))
 
+    # -- mesh integrals
+    def integrate(self, vec_a, vec_b=None, rule=RULE_GAUSS, grad=False):
+        """the moments of u = vec_a (- vec_b) over the mesh (pyn_integrate), flat: volume, value[bs], square[bs] and, with grad,
+        grad2[bs] and, for bs == dim, div2, curl2[dim_w]; pynama_amd.domain.integrals.Moments names them"""
+        out, n = np.zeros(24), _I(0)
+        _check(self.lib.pyn_integrate(self.h, int(rule), 1 if grad else 0, int(vec_a), -1 if vec_b is None else int(vec_b), out, C.byref(n)))
+        return out[:n.value].copy()
+
     def timers(self):
         t = np.zeros(8)
         _check(self.lib.pyn_timers_get(self.h, t, 8))
-        return {"symbolic_ms": t[0], "assemble_ms": t[1], "spmv_ms": t[2], "solve_ms": t[3]}
+        return {"symbolic_ms": t[0], "assemble_ms": t[1], "spmv_ms": t[2], "solve_ms": t[3], "integrate_ms": t[4]}

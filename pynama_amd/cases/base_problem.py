@@ -209,6 +209,40 @@ class BaseProblem(object):
         probe = self.getProbe()
         if probe is not None:
             self._probeSeries.append((time, probe.sample(self.vel), probe.sample(self.vort)))
+        every = self.diagnosticsEvery()
+        if every and step % every == 0:
+            self._diagnosticsSeries = getattr(self, "_diagnosticsSeries", [])
+            self._diagnosticsSeries.append(self.computeDiagnostics(time))
+
+    def diagnosticsEvery(self):
+        """`every` of the optional `diagnostics: {every: 1, rule: gauss}` block of the yaml (1 when the block has no `every`); 0
+        without the block: nothing is created and no integral is taken"""
+        if "diagnostics" not in self.config or self.config["diagnostics"] is False:
+            return 0
+        return max(1, int((self.config["diagnostics"] or {}).get("every", 1)))    # a bare `diagnostics:` takes the defaults
+
+    def computeDiagnostics(self, time):
+        """One record of integral diagnostics of the current fields (DMPlexDom.integrate): two passes over the mesh, velocity with
+        gradients and vorticity without, and two more for the errors when the case has exact fields"""
+        rule = (self.config.get("diagnostics") or {}).get("rule", "gauss")
+        mv = self.dom.integrate(self.vel, rule=rule, grad=True)
+        mw = self.dom.integrate(self.vort, rule=rule)
+        rec = {"t": float(time),
+               "kinetic_energy": 0.5 * self.rho * float(np.sum(mv.square)),
+               "enstrophy": 0.5 * float(np.sum(mw.square)),
+               "circulation": mw.value.copy(),
+               "div_l2": float(np.sqrt(mv.div2)),
+               "curl_l2": float(np.sqrt(np.sum(mv.curl2)))}
+        exact = getattr(self, "generateExactVecs", None)          # the no-slip cases (the cavity) have no exact fields at all
+        exactVel, exactVort = exact(time) if exact is not None else (None, None)
+        if hasattr(exactVel, "id") and hasattr(exactVort, "id"):
+            rec["vel_error_l2"] = self.dom.normL2(self.vel, minus=exactVel, rule=rule)
+            rec["vort_error_l2"] = self.dom.normL2(self.vort, minus=exactVort, rule=rule)
+        return rec
+
+    def getDiagnosticsSeries(self):
+        """the records of computeDiagnostics of every `every`-th accepted step so far (empty without a `diagnostics` block)"""
+        return list(getattr(self, "_diagnosticsSeries", []))
 
     def probePoints(self):
         """the points of the optional `probes` block of the yaml: `points: [[x, y], ...]` and / or
@@ -337,15 +371,25 @@ class FreeSlip(BaseProblem):
         self.applyBoundaryConditions(time)
         self.solver(self.mat.Rw * vort + self.mat.Krhs * self.vel, self.vel)     # base_problem.py:481
 
-    def getKLEError(self, viscousTimes=None, startTime=0.0, endTime=1.0, steps=10):
-        """l2 error of the KLE velocity against the case's exact fields at the times t = tau^2 / (4 nu) of the viscous times `tau`
-        (what the reference's convergence charts plot, base_problem.py:483-497)."""
+    def getKLEError(self, viscousTimes=None, startTime=0.0, endTime=1.0, steps=10, norm="l2"):
+        """error of the KLE velocity against the case's exact fields at the times t = tau^2 / (4 nu) of the viscous times `tau`.
+        norm "l2": the algebraic 2-norm of the nodal difference (what the reference's convergence charts plot,
+        base_problem.py:483-497; it grows like sqrt(N) with the node count); "L2": the integral norm over the mesh (dom.normL2);
+        "H1": the integral seminorm of the gradient; "lumped": the L2 norm with the lumped nodal weights (the reference's weighted
+        norm, custom_func.py:145)."""
+        if norm not in ("l2", "L2", "H1", "lumped"):
+            raise ValueError(f"getKLEError: norm {norm!r} is none of 'l2', 'L2', 'H1', 'lumped'")
         taus = np.linspace(startTime, endTime, steps, endpoint=False) if viscousTimes is None else np.asarray(viscousTimes, dtype=float)
         errors = []
         for t in taus ** 2 / (4.0 * self.nu):
             exactVel, exactVort = self.generateExactVecs(t)
             self.solveKLE(t, exactVort)
-            errors.append((exactVel - self.vel).norm(norm_type=2))
+            if norm == "l2":
+                errors.append((exactVel - self.vel).norm(norm_type=2))
+            elif norm == "H1":
+                errors.append(self.dom.seminormH1(exactVel, minus=self.vel))
+            else:
+                errors.append(self.dom.normL2(exactVel, minus=self.vel, rule="nodal" if norm == "lumped" else "gauss"))
         return errors
 
     def buildKLEMats(self):

@@ -557,6 +557,7 @@ static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
   c->d_probe_loc.reset();
   c->d_probe_tab.reset();
   c->probe_tab_ngl = c->probe_tab_dim = 0;
+  pyn_integrals_release(c);       // ... the tables and partials of the mesh integrals
   c->d_rowptr.reset();            // ... and the graph (the matrices go with the next pyn_csr_symbolic)
   c->d_colidx.reset();
   c->nnzb = 0;

@@ -433,6 +433,12 @@ struct pyn_ctx {
   DevBuf<int32_t> d_probe_loc;      // ... their local-order table ref_local_lattice(ngl, dim) [nn][dim] ...
   DevBuf<double> d_probe_tab;       // ... and the 1-D Lobatto nodes x[ngl] with the Lagrange denominators den[ngl], uploaded once for
   int probe_tab_ngl = 0, probe_tab_dim = 0;   // ... this order and dimension
+  // mesh integrals (pyn_integrals.hip): the 1-D tables w x B G of both rules and a_of_t of this order and dimension, uploaded on first
+  // use; the chunk partials (grown on demand), the result and the lowest cell with det J <= 0.  A new mesh releases all of it
+  DevBuf<double> d_int_tab[2], d_int_part, d_int_out;
+  DevBuf<int32_t> d_int_aoft;
+  DevBuf<int> d_int_bad;
+  int int_tab_ngl = 0, int_tab_dim = 0;
 
   // reduction / solver scratch
   DevBuf<double> d_part;       // [8][PYN_MAX_PARTIALS]
@@ -513,6 +519,7 @@ using ConnAt = std::function<int32_t(int64_t)>;
 int pyn_box_detect(pyn_ctx* c, const ConnAt& at);
 void ref_local_lattice(int n, int dim, std::vector<int>& out);
 void mesh_local_lattice(int ngl, int dim, std::vector<int>& loc);
+void pyn_integrals_release(pyn_ctx* c);   // pyn_integrals.hip: the tables and scratch of the mesh integrals
 // the three views of c->box, each next to its kernels (once per pyn_mesh_set, after pyn_box_detect)
 int pyn_lattice_view(pyn_ctx* c);   // pyn_assemble_lattice.hip
 bool pyn_q1_affine_tables_standard(const double* aff);

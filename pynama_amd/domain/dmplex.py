@@ -863,6 +863,28 @@ class DMPlexDom(object):
         from pynama_amd.domain.probe import Probe
         return Probe(self, points)
 
+    def integrate(self, vec, minus=None, rule="gauss", grad=False):
+        """Moments (pynama_amd/domain/integrals.py) of vec, or of vec - minus, over the mesh in one device pass; rule 'gauss'
+        (Gauss-Legendre, ngl + 1 points per axis) or 'nodal' (the lumped nodal weights); grad: also the gradient moments; one rank"""
+        from pynama_amd.domain import integrals
+        return integrals.integrate(self, vec, minus, rule, grad)
+
+    def normL2(self, vec, minus=None, rule="gauss"):
+        """sqrt(int |vec - minus|^2) over the mesh, all components"""
+        return float(np.sqrt(np.sum(self.integrate(vec, minus, rule).square)))
+
+    def seminormH1(self, vec, minus=None, rule="gauss"):
+        """sqrt(int |grad (vec - minus)|^2) over the mesh, all components"""
+        return float(np.sqrt(np.sum(self.integrate(vec, minus, rule, grad=True).grad2)))
+
+    def volume(self):
+        """int 1 over the mesh (area in 2-D)"""
+        v = getattr(self, "_volumeVec", None)       # `volume` does not depend on the field: any vector of the mesh's node count
+        if v is None or v.ctx is not self.ctx:      # will do; one scalar vector is kept for the repeated calls of a time loop
+            v = self._volumeVec = self.createGlobalVec(1)
+            v.set(0.0)
+        return self.integrate(v).volume
+
     def nodeSet(self, nodes):
         """NodeSet of the owned nodes among `nodes` (global ids: a set, a list, a range); every owned node -> the set -1"""
         if isinstance(nodes, NodeSet):
