@@ -379,6 +379,12 @@ int pyn_assemble_last(pyn_ctx* ctx, int64_t* info);
  * info[2]: [0] 0: another kernel, 1: one workgroup per x-line (PYNAMA_LATTICE_ROWS_ONESHOT), 2: the persistent form;
  *          [1] the workgroups it launched */
 int pyn_assemble_last_rows(pyn_ctx* ctx, int64_t* info);
+/* What the geometry pre-pass of the row-run kernels (lattices of order ngl 2 in 2-D and ngl 3) found on the current mesh, and the
+ * form the matrix-free KLE operator of a second-order lattice took from it.  info[3]:
+ *   [0] 1: every cell is a parallelogram / parallelepiped, 0: some cell is not, -1: the pass has not run on this mesh
+ *   [1] 1: ... and axis-aligned, so the kernels take the diagonal forms of J^-1 (unless PYNAMA_HO3_NO_DIAG); 0: full J^-1; -1 as [0]
+ *   [2] 1 / 0: the matrix-free KLE operator set on a second-order lattice uses the diagonal / the full form; -1: none is set */
+int pyn_ho3_geometry(pyn_ctx* ctx, int64_t* info);
 /* The rule that picks the family (host only: no context, no device, no environment) -- what every assembly applies, once, to its
  * request, the facts of the context and the PYNAMA_* switches of the moment.  The three arrays hold plain integers in the order
  * pyn_assemble_choose_layout writes into buf ("request:a,b,..;facts:..;knobs:.."): request = form, variant, which of K / Krhs / Rw /

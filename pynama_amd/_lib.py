@@ -15,7 +15,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _DEFAULT_LIB_PATH = os.path.join(_HERE, "libpynama_hip.so")
 LIB_PATH = os.environ.get("PYNAMA_LIB_PATH") or _DEFAULT_LIB_PATH   # (the override: A/B of two builds, tools/)
-_NEWER_SYMBOLS = ("pyn_assemble_last_rows",)   # diagnostics an older build under PYNAMA_LIB_PATH may lack (never the in-tree library)
+_NEWER_SYMBOLS = ("pyn_assemble_last_rows", "pyn_ho3_geometry")   # diagnostics an older build under PYNAMA_LIB_PATH may lack (never the in-tree library)
 CSRC = os.path.join(_HERE, "csrc")
 
 # enums of include/pynama_hip.h
@@ -136,6 +136,7 @@ SIGNATURES = {
     "pyn_product_choose": [_I] * 4 + [_L, _L] + [_I] * 7 + [_D, _I, _I] + [C.POINTER(_I)] * 4,
     "pyn_assemble_last": [_P, _pi64],
     "pyn_assemble_last_rows": [_P, _pi64],
+    "pyn_ho3_geometry": [_P, _pi64],
     "pyn_assemble_choose": [_pi64, _pi64, _pi64, _pi64],
     "pyn_assemble_choose_layout": [C.c_char_p, _I],
     "pyn_matfree_apply": [_P, _I, _I, _I],
@@ -726,6 +727,15 @@ class Context:
         else:                                # (an older build under PYNAMA_LIB_PATH)
             rows[:] = -1
         return dict({k: int(v) for k, v in zip(_ASM_LAST_KEYS, info)}, rows_form=int(rows[0]), rows_grid=int(rows[1]))
+
+    def ho3_geometry(self):
+        """what the row-run geometry pre-pass found on this mesh: {'affine', 'diag' (1 / 0; -1: the pass has not run), 'matfree_diag'
+        (form of the matrix-free KLE operator set on a second-order lattice; -1: none set)}; all -1 from an older build under
+        PYNAMA_LIB_PATH"""
+        info = np.full(3, -1, np.int64)
+        if hasattr(self.lib, "pyn_ho3_geometry"):
+            _check(self.lib.pyn_ho3_geometry(self.h, info))
+        return dict(zip(("affine", "diag", "matfree_diag"), (int(v) for v in info)))
 
     def mesh_ho_lattice(self):
         """(ngl, nx, ny, nz) when the mesh is a box lattice of order ngl >= 4 that the matrix-free KLE operator accepts

@@ -117,6 +117,12 @@ __global__ void __launch_bounds__(256) ho3_geom_kernel(const int32_t* __restrict
 #pragma unroll
     for (int x = 0; x < DIM; ++x) X[cn][x] = p[x];
   }
+  // relative to the first corner: the rows of HrsCoo sum to zero, so J is unchanged, and its sums round at eps h instead of eps |x|
+  // (far from the origin the products HrsCoo . X would otherwise cancel |x| / h of their digits); the checks below take differences
+#pragma unroll
+  for (int cn = NC - 1; cn >= 0; --cn)
+#pragma unroll
+    for (int x = 0; x < DIM; ++x) X[cn][x] -= X[0][x];
   // J = HrsCoo . X at the first point of the full rule (spectral.py:120); constant on a parallelepiped
   double J[DIM * DIM], Ji[DIM * DIM];
 #pragma unroll
@@ -1123,6 +1129,16 @@ int pyn_ho3_prepare(pyn_ctx* c) {
     L.affine = h[0] ? 0 : 1;
     L.diag = (h[0] || h[1]) ? 0 : 1;
   }
+  return PYN_OK;
+}
+
+extern "C" int pyn_ho3_geometry(pyn_ctx* c, int64_t* info) {
+  PYN_CHECK(c && info, "NULL argument");
+  const Ho3View& L = c->ho3;
+  const bool ran = L.valid && L.affine >= 0;
+  info[0] = ran ? L.affine : -1;
+  info[1] = ran ? L.diag : -1;
+  info[2] = L.valid && c->box.ngl == 3 && c->mf_set[PYN_MATFREE_KLE] ? c->mf_ho3.diag : -1;
   return PYN_OK;
 }
 

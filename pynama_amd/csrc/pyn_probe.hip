@@ -8,7 +8,8 @@
 //              lower cell
 //     path 1   every other mesh: a uniform bin grid over the bounding box holds, per bin, the cells whose corner bounding box overlaps
 //              it (count / scan / fill with integer atomics); every point walks the candidates of its bin with Newton from xi = 0
-//              (at most 16 steps, stop at |d xi|_inf < 1e-13), accepts a cell at |xi|_inf <= 1 + 1e-10 and keeps the LOWEST accepting
+//              on coordinates taken relative to the cell's first corner (the residual rounds at eps h, wherever the mesh lies;
+//              at most 16 steps, stop at |d xi|_inf < 1e-13), accepts a cell at |xi|_inf <= 1 + 1e-10 and keeps the LOWEST accepting
 //              cell index, so the result does not depend on the fill order of the bins; the accepted xi then takes two more steps with
 //              the residual in double-double, which leaves it at its own rounding (a field's gradient multiplies the error of xi)
 //   sampling   out[k][c] = sum_a phi_a(xi_k) u[conn[e_k][a]][c], phi_a = prod_d l_{t_a,d}(xi_d), t_a = ref_local_lattice(ngl, dim)[a],
@@ -243,6 +244,23 @@ __global__ void __launch_bounds__(256) probe_bin_kernel(ProbeBins G, int64_t n_e
       }
 }
 
+// Newton works from differences: the cell's first corner is taken off every corner and off the point.  Differences of nearby doubles
+// are exact (or exact to eps h), so the residual p - x(xi) rounds at eps h and not at eps |x|, and the stopping rule in reference
+// coordinates can be met at any distance from the origin.  N sums to one and dN to zero over the corners: x(xi) - p and J are unchanged
+template <int DIM>
+__device__ __forceinline__ void probe_recentre(double* Xc, const double* p, double* q) {
+  double o[DIM];
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    o[d] = Xc[d];
+    q[d] = p[d] - o[d];
+  }
+#pragma unroll
+  for (int c = 0; c < (1 << DIM); ++c)
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) Xc[c * DIM + d] -= o[d];
+}
+
 // double-double arithmetic for the residual of the refinement steps (error-free sums and products; one rounding per intrinsic)
 struct dd {
   double h, l;
@@ -380,13 +398,14 @@ __global__ void __launch_bounds__(256) probe_locate_kernel(ProbeBins G, ProbeCor
           if (!(p[d] >= lo[d] && p[d] <= hi[d])) in = false;
         if (!in) continue;
         ncand += 1;
-        double xi[DIM], dmax = 1.0, amax = 0.0;
+        double xi[DIM], pc[DIM], dmax = 1.0, amax = 0.0;
+        probe_recentre<DIM>(Xc, p, pc);
 #pragma unroll
         for (int d = 0; d < DIM; ++d) xi[d] = 0.0;
         int steps = 0;
         bool ok = true;
         while (ok && steps < PROBE_NEWTON_CAP) {
-          ok = probe_newton_step<DIM>(Cn, Xc, p, xi, &dmax);
+          ok = probe_newton_step<DIM>(Cn, Xc, pc, xi, &dmax);
           steps += 1;
           if (dmax < PROBE_NEWTON_TOL) break;
         }
@@ -400,11 +419,12 @@ __global__ void __launch_bounds__(256) probe_locate_kernel(ProbeBins G, ProbeCor
         for (int d = 0; d < DIM; ++d) bxi[d] = xi[d];
       }
       if (best >= 0) {   // the accepted cell: two steps with an exact residual (what a field's gradient multiplies is the error of xi)
-        double Xc[(1 << DIM) * DIM], lo[DIM], hi[DIM], dmax, xi[DIM];
+        double Xc[(1 << DIM) * DIM], lo[DIM], hi[DIM], dmax, xi[DIM], pc[DIM];
         probe_cell_box<DIM>(best, nn, conn, xyz, Xc, lo, hi);
+        probe_recentre<DIM>(Xc, p, pc);
 #pragma unroll
         for (int d = 0; d < DIM; ++d) xi[d] = bxi[d];
-        const bool ok = probe_newton_step<DIM, true>(Cn, Xc, p, xi, &dmax) && probe_newton_step<DIM, true>(Cn, Xc, p, xi, &dmax);
+        const bool ok = probe_newton_step<DIM, true>(Cn, Xc, pc, xi, &dmax) && probe_newton_step<DIM, true>(Cn, Xc, pc, xi, &dmax);
 #pragma unroll
         for (int d = 0; d < DIM; ++d) bxi[d] = fmin(1.0, fmax(-1.0, ok ? xi[d] : bxi[d]));
       }

@@ -42,8 +42,11 @@ def image(Xc, xi):
 
 def newton(Xc, p):
     """Newton from xi = 0 on x(xi) = p for the pairs (cell corners Xc [M, nc, dim], point p [M, dim]).  Returns the raw xi, the steps
-    taken, converged (|d xi|_inf < NEWTON_TOL within NEWTON_CAP steps) and ok (det J > 0 at every iterate)"""
+    taken, converged (|d xi|_inf < NEWTON_TOL within NEWTON_CAP steps) and ok (det J > 0 at every iterate).  As on the device, the
+    iteration runs on coordinates relative to the cell's first corner: the residual then rounds at eps h and not at eps |x|"""
     M, _, dim = Xc.shape
+    p = p - Xc[:, 0, :]
+    Xc = Xc - Xc[:, :1, :]
     xi = np.zeros((M, dim))
     steps = np.zeros(M, dtype=int)
     active, ok, conv = np.ones(M, bool), np.ones(M, bool), np.zeros(M, bool)
