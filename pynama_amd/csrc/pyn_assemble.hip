@@ -1230,7 +1230,7 @@ int asm_facts(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, AsmFacts* f) 
     PYN_TRY(pyn_mesh_all_affine(c, &all_aff));
   }
   f->mesh_affine = c->mesh_affine;
-  f->lat_std_ok = c->lat.std_ok;
+  f->lat_std_ok = c->lat_std_ok;
   return PYN_OK;
 }
 

@@ -1162,7 +1162,6 @@ int pyn_ho3_cell_facts(pyn_ctx* c, bool* affine, bool* diag, double (*hc)[8]) {
 // The ngl 2 / 3 view of c->box: structured meshes of tensor-product cells of order 1 or 2, whose corners sit where the device code has
 // them spelled out (CB2 / CB3)
 void pyn_ho3_view(pyn_ctx* c) {
-  c->ho3 = Ho3View();
   const BoxLattice& B = c->box;
   if (!B.valid || B.ngl > 3 || B.plane() > INT32_MAX / 4 || B.n_own < 1 || getenv("PYNAMA_NO_HO3")) return;
   const LocalOrder lo(B.dim, B.ngl);
@@ -1184,9 +1183,7 @@ int pyn_ho3_tables(pyn_ctx* c, int which, int ngp, const double* w, const double
   const int dd = dim * dim, n2 = nn * nn;
   const int ts = (2 * dd + 3 * dim + 1) & ~1;        // record per node pair (TabRec)
   const size_t total = (size_t)ts * n2;
-  if (c->ho3_tabs_nn != nn) {
-    c->ho3_tabs_ok[0] = c->ho3_tabs_ok[1] = c->ho3_tabs_ok[2] = false;
-    c->ho3_tabs_nn = 0;   // a failed allocation leaves no records: the next call allocates again
+  if (!c->ho3_tabs_nn) {   // the first rule of this element (a failed allocation leaves no records: the next call allocates again)
     PYN_HIP(c->d_ho3_tabs.alloc(total));
     PYN_HIP(hipMemsetAsync(c->d_ho3_tabs, 0, total * sizeof(double), c->stream));
     c->ho3_tabs_host.assign(total, 0.0);

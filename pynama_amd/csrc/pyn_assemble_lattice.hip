@@ -1997,7 +1997,6 @@ __global__ void lattice_symbolic_kernel(LatArgs T, int64_t n_rows, int32_t* __re
 // c->box at dim 3, ngl 2 (the detector's plane limit is this view's), + the z-neighbour planes of every plane in id order (zord)
 int pyn_lattice_view(pyn_ctx* c) {
   Lattice& L = c->lat;
-  L = Lattice();
   const BoxLattice& B = c->box;
   if (!B.valid || B.dim != 3 || B.ngl != 2 || getenv("PYNAMA_NO_LATTICE")) return PYN_OK;
   const std::vector<int32_t>& P = B.P;
@@ -2079,7 +2078,7 @@ static void lat_fill(const pyn_ctx* c, const AsmKnobs& k, LatArgs& T) {
   T.p_own0 = B.p_own0;
   T.n_own = B.n_own;
   T.bzs = 1;
-  T.std_lat = c->lat.std_ok == 1;
+  T.std_lat = c->lat_std_ok == 1;
   T.q.w = c->quad[0].w;
   T.q.hrs = c->quad[0].Hrs;
   T.q.hcoo = c->quad[0].HrsCoo;
@@ -2094,8 +2093,8 @@ int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k) {
   Lattice& L = c->lat;
   int mesh_aff = 0;
   PYN_TRY(pyn_mesh_all_affine(c, &mesh_aff));
-  if (L.std_ok < 0) {
-    L.std_ok = 0;
+  if (c->lat_std_ok < 0) {
+    c->lat_std_ok = 0;
     if (L.std_shape && !k.no_std_lattice) {
       DevTmp flag;
       PYN_HIP(flag.alloc(sizeof(int)));
@@ -2108,7 +2107,7 @@ int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k) {
       int h = 0;
       PYN_HIP(hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
       PYN_HIP(hipStreamSynchronize(c->stream));
-      L.std_ok = h;
+      c->lat_std_ok = h;
     }
   }
   return PYN_OK;

@@ -83,7 +83,6 @@ __global__ void box_conn_verify_kernel(const int32_t* __restrict__ conn, const i
 // guessed from O(element rows + layers) entries is checked against ALL of c->d_conn on the device.  Applies what every view asks for;
 // the views add their own limits.
 int pyn_box_detect(pyn_ctx* c, const ConnAt& at) {
-  c->box = BoxLattice();
   const int dim = c->dim, nn = c->nn, ngl = c->ngl;
   if (ngl < 2 || c->n_elem < 1) return PYN_OK;
   const int m = ngl - 1;

@@ -539,28 +539,12 @@ __global__ void box_xyz_kernel(BoxArgs B, double* __restrict__ xyz) {
 
 // what pyn_mesh_set / pyn_mesh_box share once c->d_conn and c->d_xyz hold the local mesh
 static int mesh_installed(pyn_ctx* c, const ConnAt& at) {
-  // first drop what belonged to the old mesh, so that a refusal below leaves nothing of it behind:
-  c->mesh_affine = -1;
-  c->lat.rect = -1;               // the axis tables of a rectilinear lattice belong to the old coordinates
-  c->lat.d_axes.reset();
-  c->lat.d_tilebc.reset();        // ... and the Dirichlet map of its tiles to the old lattice
-  c->lat.tilebc_stamp = -1;
-  c->lat.d_rowsmap.reset();       // ... and the words of its x-lines
-  c->lat.rowsmap_stamp = -1;
-  for (int k = 0; k < PYN_MATFREE_SLOTS; ++k) {   // the matrix-free operators
-    c->mf_mask[k].reset();
-    c->mf_set[k] = false;
-  }
-  c->ibm.reset();                 // ... the immersed-boundary marker set
-  for (auto& s : c->nodesets) s = DNodeSet();   // ... every node set (ids are not reused: the slots stay, dead)
-  for (auto& p : c->probes) p = DProbe();       // ... and every probe set, the same way, with the tables of their order
-  c->d_probe_loc.reset();
-  c->d_probe_tab.reset();
-  c->probe_tab_ngl = c->probe_tab_dim = 0;
-  pyn_integrals_release(c);       // ... the tables and partials of the mesh integrals
-  c->d_rowptr.reset();            // ... and the graph (the matrices go with the next pyn_csr_symbolic)
-  c->d_colidx.reset();
-  c->nnzb = 0;
+  // first end what belonged to the old mesh, so that a refusal below leaves nothing of it behind
+  PYN_HIP(hipStreamSynchronize(c->stream));     // nothing in flight may still read what is freed
+  static_cast<CtxMesh&>(*c) = CtxMesh();
+  static_cast<CtxGraph&>(*c) = CtxGraph();
+  for (auto& s : c->nodesets) s = DNodeSet();   // ids are not reused: the slots stay, dead
+  for (auto& p : c->probes) p = DProbe();
   {
     DevBuf<unsigned long long> d_bad;
     unsigned long long bad = ~0ull;
@@ -603,13 +587,17 @@ static int mesh_sizes(pyn_ctx* c, int dim, int nn, int64_t n_elem, int64_t n_nod
   }
   PYN_CHECK(c->n_owned + c->n_ghost == n_node, "n_node %lld != owned+ghost %lld", (long long)n_node,
             (long long)(c->n_owned + c->n_ghost));
+  PYN_HIP(hipSetDevice(c->device));
+  if (dim != c->dim || nn != c->nn) {   // another element: its tables end here; the same element keeps them
+    PYN_HIP(hipStreamSynchronize(c->stream));
+    static_cast<CtxElement&>(*c) = CtxElement();
+  }
   c->dim = dim;
   c->nn = nn;
   c->nc = simplex ? nn : 1 << dim;
   c->ngl = simplex ? 0 : ngl;
   c->n_elem = n_elem;
   c->n_node = n_node;
-  PYN_HIP(hipSetDevice(c->device));
   return PYN_OK;
 }
 

@@ -190,7 +190,6 @@ int pyn_ho_tab_upload(pyn_ctx* c, const pyn_ho::HoTab1D& T);
 // the general operator (pyn_matfree_ho_general.hip), reached through the backend of pyn_matfree_ho.hip
 int pyn_hog_set(pyn_ctx* c);
 int pyn_hog_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out);
-void pyn_hog_release(pyn_ctx* c);
 // what the two general operators share (pyn_matfree_ho_general.hip; `what` names the operator in the messages): a_of_t, the geometry
 // tables against the multilinear corner basis at the 1-D points of both rules, the device check of det J > 0 at the points
 // d_tab[tab_pts ...] (full rule [ngl], reduced rule [ngl - 1]), the node -> (cell, t) incidence list, the gather pass
@@ -202,5 +201,3 @@ int64_t pyn_hog_incidence_host(const int32_t* conn, int64_t n_elem, int nn, int6
 int pyn_hog_incidence(pyn_ctx* c, const std::vector<int32_t>& aoft, const char* what, DevBuf<int32_t>& d_inc_ptr, DevBuf<int32_t>& d_inc);
 int pyn_hog_gather(pyn_ctx* c, const int32_t* inc_ptr, const int32_t* inc, const double* ye, const uint8_t* mask, const double* x, double* y,
                    bool dot, int* grid_out);
-// the general operator of order ngl 3 (pyn_matfree_ho3_general.hip), its own backend (chosen by the id, pyn_krylov.hip)
-void pyn_h3g_release(pyn_ctx* c);

@@ -436,16 +436,6 @@ int integrate_tables(pyn_ctx* c) {
 
 }  // namespace
 
-void pyn_integrals_release(pyn_ctx* c) {
-  c->d_int_tab[0].reset();
-  c->d_int_tab[1].reset();
-  c->d_int_aoft.reset();
-  c->d_int_part.reset();
-  c->d_int_out.reset();
-  c->d_int_bad.reset();
-  c->int_tab_ngl = c->int_tab_dim = 0;
-}
-
 extern "C" int pyn_integrate_len(int dim, int bs, int with_grad) {
   if ((dim != 2 && dim != 3) || bs < 1 || bs > 6) return 0;
   return 1 + (with_grad ? 3 : 2) * bs + (with_grad && bs == dim ? 1 + (dim == 3 ? 3 : 1) : 0);

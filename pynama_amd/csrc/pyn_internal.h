@@ -239,9 +239,8 @@ struct BoxLattice {
 struct Lattice {
   bool valid = false;
   bool std_shape = false;      // ids follow the slab numbering: owned planes, ghost planes below, ghost planes above (one rank, or a rank's slab)
-  int std_ok = -1;             // closed-form row offsets verified against the graph (-1: not checked yet)
   DevBuf<int32_t> d_zord;      // [npl]: count | (dz+1) codes of the z-neighbour planes sorted by node id
-  int rect = -1;               // rectilinear: node (i, j, plane k) at (X[i], Y[j], Z[k]) bit for bit (-1: not checked yet; reset with the mesh)
+  int rect = -1;               // rectilinear: node (i, j, plane k) at (X[i], Y[j], Z[k]) bit for bit (-1: not checked yet)
   DevBuf<double> d_axes;       // ... its axis tables X | Y | Z, each with guard slots (lat_axis_slots, pyn_lattice.h); set iff rect == 1
   DevBuf<uint32_t> d_tilebc;   // one bit per tile of the scalar tile kernel: its node box holds an imposed node ...
   int64_t tilebc_stamp = -1;   // ... for this Dirichlet set (pyn_ctx::bc_stamp)
@@ -336,7 +335,109 @@ __device__ inline void block_partial(double acc, double* __restrict__ part) {
   if (threadIdx.x == 0) part[blockIdx.x] = sm_[0] + sm_[1] + sm_[2] + sm_[3];
 }
 
-struct pyn_ctx {
+// buffers of PYN_MATFREE_KLE_GENERAL (pyn_matfree_ho_general.hip), any quadrilateral / hexahedral mesh of orders ngl >= 4; it shares
+// d_ho_tab / d_ho_ye with the box-lattice operator
+struct HogState {
+  DevBuf<int32_t> aoft;         // [nn] local node at tensor position t (the inverse of mesh_local_lattice)
+  DevBuf<int32_t> inc_ptr;      // [n_node + 1] node -> (cell, t) incidence list in CSR form ...
+  DevBuf<int32_t> inc;          // ... [n_elem * nn] entries cell * nn + t, ascending within a row
+};
+// buffers of PYN_MATFREE_KLE_NGL3_GENERAL (pyn_matfree_ho3_general.hip), any quadrilateral / hexahedral mesh of order ngl 3
+struct H3gState {
+  DevBuf<double> tab;           // the 1-D tables of both rules: wf Bf Gf wr Br Gr xf xr
+  DevBuf<double> ye;            // the per-cell results between the two passes [n_elem][dim][nn]
+  DevBuf<int32_t> aoft, inc_ptr, inc;   // as in HogState
+};
+
+// ---- context state by lifetime -----------------------------------------------------------------------------------------------------
+// Every member of the context that is DERIVED from something installed lives in one of three scopes, base structs of pyn_ctx; each
+// scope is reset in exactly one place by assigning a fresh one, so a cache is dropped at the right moment by where it is declared.
+
+// Element scope, a function of (dim, nn).  Ends when a mesh of another (dim, nn) is installed (mesh_sizes, pyn_ctx.hip).
+struct CtxElement {
+  QuadTab quad[3];
+  bool aff_standard = false;     // the uploaded tables are those of the trilinear hexahedron in closed form
+  bool aff_rw_standard = false;  // ... and so is int N_a d N_b (affine Rw path)
+  bool q1_red_standard = false;    // reduced rule = the centroid, weight 8, trilinear tables (lean KLE kernel)
+  bool q1_gauss_standard = false;  // ... pointwise: 2x2x2 Gauss rule, unit weights (lean general-geometry kernels)
+  DevBuf<double> d_aff;     // Q1-hex affine tables: [6][36] reference matrices + [4][8] non-affine monomial signs + [3][3] S
+  // reference matrices of the ngl = 3 element in tensor (lattice) order, from the uploaded tables (pyn_elem_tables_set):
+  // Tf / Tr[r][s][a][b] = sum_g w Hrs_r[a] Hrs_s[b] (full / reduced rule), Uf / Ur[r][a][b] = sum_g w H[a] Hrs_r[b]
+  DevBuf<double> d_ho3_tabs;
+  std::vector<double> ho3_t1d_host;    // 1-D factors M, D, S of the three rules; the records are their tensor products when ho3_tens_ok
+  DevBuf<double> d_ho3_t1d;
+  bool ho3_tens_ok = false;
+  std::vector<double> ho3_tabs_host;   // host image of the records (the three rules arrive in separate pyn_elem_tables_set calls)
+  bool ho3_tabs_ok[3] = {false, false, false};   // full, reduced, nodal rule
+  int ho3_tabs_nn = 0;
+};
+
+// Mesh scope, a function of the connectivity and the coordinates.  Ends when a mesh is installed (mesh_installed, pyn_ctx.hip).
+struct CtxMesh {
+  int mesh_affine = -1;          // every element a parallelepiped? (-1: not checked yet)
+  BoxLattice box;   // structured topology, if the mesh has one, and the views of it that the kernel families admit:
+  Lattice lat;      // 3-D first-order cells (pyn_assemble_lattice.hip)
+  Ho3View ho3;      // ngl 2 and 3 (pyn_assemble_ho3.hip)
+  bool ho_valid = false;        // 4 <= ngl <= pyn_ho_matfree_max_ngl(dim) (pyn_matfree_ho.hip); pyn_mesh_topology says kind 0 for these
+  DevBuf<double> d_ho_tab;      // its matrix-free KLE operator: the 1-D tables of the order (set by pyn_matfree_set) ...
+  DevBuf<double> d_ho_ye;       // ... and the per-cell results between the two passes [n_elem][dim][nn]
+  HogState hog;
+  H3gState h3g;
+  // matrix-free operators (pyn_matfree_set), slot = PYN_MATFREE_*: the Dirichlet mask is SNAPSHOT at set time, so later
+  // pyn_bc_set calls (operator assembly, other matrices) do not change the operator
+  bool mf_set[PYN_MATFREE_SLOTS] = {};
+  DevBuf<uint8_t> mf_mask[PYN_MATFREE_SLOTS];   // null = no imposed DOF
+  double mf_alpha_d[PYN_MATFREE_SLOTS] = {}, mf_alpha_w[PYN_MATFREE_SLOTS] = {};   // penalty weights of each KLE operator's snapshot
+  Ho3MfBasis mf_ho3;     // the KLE operator on a second-order lattice (pyn_matfree_ho3.hip): its 1-D point bases, set with mf_set[KLE]
+  // boundary condition: [n_node * bc_ndof], so a new mesh has none until pyn_bc_set
+  int bc_ndof = 0;
+  DevBuf<uint8_t> d_bcmask;
+  // elements with an imposed node (the only ones that feed an imposed-column matrix), per Dirichlet set
+  DevBuf<int32_t> d_esel;
+  int64_t n_esel = 0, esel_stamp = -1;
+  // general-geometry KLE: off-diagonal element Laplacians [28][ne] between the pre-pass and the tile kernel (grown on demand)
+  DevBuf<double> d_kle_lel;
+  // point probes (pyn_probe.hip): the local-order table ref_local_lattice(ngl, dim) [nn][dim] ...
+  DevBuf<int32_t> d_probe_loc;
+  DevBuf<double> d_probe_tab;       // ... and the 1-D Lobatto nodes x[ngl] with the Lagrange denominators den[ngl], uploaded once for
+  int probe_tab_ngl = 0, probe_tab_dim = 0;   // ... this order and dimension
+  // mesh integrals (pyn_integrals.hip): the 1-D tables w x B G of both rules and a_of_t of this order and dimension, uploaded on first
+  // use; the chunk partials (grown on demand), the result and the lowest cell with det J <= 0
+  DevBuf<double> d_int_tab[2], d_int_part, d_int_out;
+  DevBuf<int32_t> d_int_aoft;
+  DevBuf<int> d_int_bad;
+  int int_tab_ngl = 0, int_tab_dim = 0;
+  std::unique_ptr<IbmState, IbmStateDelete> ibm;   // immersed-boundary marker set (pyn_ibm.hip): stencils, node-major spreading lists, A = H S and its LU
+};
+
+// Graph scope, a function of the node graph.  Ends when a mesh is installed (mesh_installed) and when pyn_csr_symbolic commits a new
+// graph (pyn_symbolic.hip), which moves the new rowptr / colidx / nnzb into a fresh scope.
+struct CtxGraph {
+  DevBuf<int32_t> d_rowptr;
+  DevBuf<int32_t> d_colidx;
+  int64_t nnzb = 0;
+  int lat_std_ok = -1;           // Q1 lattice: closed-form row offsets verified against this graph (-1: not checked yet)
+  // patch plans of the tiled assemblies (pyn_assemble_tiled.hip): [0] scalar forms, [1] KLE (3x3 blocks)
+  PatchPlan plan[2];
+  bool plan_unfit[2] = {false, false};  // the automatic plan did not fit this graph
+  // SELL-64 structures, one per block shape, + the node-level column-pattern dictionary (pyn_sell.hip)
+  std::vector<SellShape> sell_shapes;
+  DevBuf<int32_t> sell_pid;      // per-node column-pattern id (dictionary mode), else null
+  DevBuf<int32_t> sell_tab;      // [npat][32] relative node offsets
+  int sell_npat = 0;
+  bool sell_dict_built = false;
+  std::vector<DMat> mats;        // handles die with the graph: "invalid matrix handle"
+};
+
+static_assert(std::is_nothrow_move_assignable<CtxElement>::value && std::is_nothrow_move_assignable<CtxMesh>::value &&
+                  std::is_nothrow_move_assignable<CtxGraph>::value && !std::is_copy_constructible<CtxElement>::value &&
+                  !std::is_copy_constructible<CtxMesh>::value && !std::is_copy_constructible<CtxGraph>::value,
+              "a scope is reset by move-assigning a fresh one, never by a copy");
+
+// The context proper holds what is INSTALLED or belongs to no mesh: device, streams, communicator, halo plan, the mesh arrays and their
+// sizes, handles whose ids must stay stable, scratch.  A new cache is declared in the scope whose input it is computed from
+// (CtxElement / CtxMesh / CtxGraph above), never here: it is then dropped with that input, and needs no release function or reset line.
+struct pyn_ctx : CtxElement, CtxMesh, CtxGraph {
   pyn_ctx() = default;
   ~pyn_ctx();   // pyn_ctx.hip: drains the streams and destroys what is not memory; the members then free themselves
   int device = 0;
@@ -362,83 +463,18 @@ struct pyn_ctx {
   int64_t n_send = 0;
   bool halo_set = false;
 
-  // mesh
+  // mesh, as installed by pyn_mesh_set / pyn_mesh_box
   int dim = 0, nn = 0, nc = 0, ngl = 0;
   int64_t n_elem = 0, n_node = 0;
   DevBuf<int32_t> d_conn;
   DevBuf<double> d_xyz;
-  QuadTab quad[3];
-  int mesh_affine = -1;          // every element a parallelepiped? (-1: not checked yet; reset by pyn_mesh_set)
-  bool aff_rw_standard = false;  // ... and so is int N_a d N_b (affine Rw path)
-  bool aff_standard = false;  // the uploaded tables are those of the trilinear hexahedron in closed form
-  bool q1_red_standard = false;    // reduced rule = the centroid, weight 8, trilinear tables (lean KLE kernel)
-  bool q1_gauss_standard = false;  // ... pointwise: 2x2x2 Gauss rule, unit weights (lean general-geometry kernels)
-  DevBuf<double> d_aff;     // Q1-hex affine tables: [6][36] reference matrices + [4][8] non-affine monomial signs + [3][3] S
+  int64_t bc_stamp = 0;  // bumped by every pyn_bc_set; never reset, so that no stamp stored in a cache can come round again
 
-  // boundary condition
-  int bc_ndof = 0;
-  // matrix-free operators (pyn_matfree_set), slot = PYN_MATFREE_*: the Dirichlet mask is SNAPSHOT at set time, so later
-  // pyn_bc_set calls (operator assembly, other matrices) do not change the operator
-  bool mf_set[PYN_MATFREE_SLOTS] = {};
-  DevBuf<uint8_t> mf_mask[PYN_MATFREE_SLOTS];   // null = no imposed DOF
-  double mf_alpha_d[PYN_MATFREE_SLOTS] = {}, mf_alpha_w[PYN_MATFREE_SLOTS] = {};   // penalty weights of each KLE operator's snapshot
-  Ho3MfBasis mf_ho3;     // the KLE operator on a second-order lattice (pyn_matfree_ho3.hip): its 1-D point bases, set with mf_set[KLE]
-  int64_t bc_stamp = 0;  // bumped by every pyn_bc_set
-  DevBuf<uint8_t> d_bcmask;
-
-  // node graph
-  DevBuf<int32_t> d_rowptr;
-  DevBuf<int32_t> d_colidx;
-  int64_t nnzb = 0;
-
-  // patch plans of the tiled assemblies (pyn_assemble_tiled.hip): [0] scalar forms, [1] KLE (3x3 blocks)
-  PatchPlan plan[2];
-  bool plan_unfit[2] = {false, false};  // the automatic plan did not fit this graph (reset by pyn_csr_symbolic)
-  BoxLattice box;   // structured topology, if the mesh has one, and the views of it that the kernel families admit:
-  Lattice lat;      // 3-D first-order cells (pyn_assemble_lattice.hip)
-  Ho3View ho3;      // ngl 2 and 3 (pyn_assemble_ho3.hip)
-  bool ho_valid = false;        // 4 <= ngl <= pyn_ho_matfree_max_ngl(dim) (pyn_matfree_ho.hip); pyn_mesh_topology says kind 0 for these
-  DevBuf<double> d_ho_tab;      // its matrix-free KLE operator: the 1-D tables of the order (set by pyn_matfree_set) ...
-  DevBuf<double> d_ho_ye;       // ... and the per-cell results between the two passes [n_elem][dim][nn]
-  // PYN_MATFREE_KLE_GENERAL (pyn_matfree_ho_general.hip), any quadrilateral / hexahedral mesh of these orders; shares d_ho_tab / d_ho_ye
-  DevBuf<int32_t> d_hog_aoft;         // [nn] local node at tensor position t (the inverse of mesh_local_lattice)
-  DevBuf<int32_t> d_hog_inc_ptr;      // [n_node + 1] node -> (cell, t) incidence list in CSR form ...
-  DevBuf<int32_t> d_hog_inc;          // ... [n_elem * nn] entries cell * nn + t, ascending within a row
-  // PYN_MATFREE_KLE_NGL3_GENERAL (pyn_matfree_ho3_general.hip), any quadrilateral / hexahedral mesh of order ngl 3: buffers of its own
-  DevBuf<double> d_h3g_tab;           // the 1-D tables of both rules: wf Bf Gf wr Br Gr xf xr
-  DevBuf<double> d_h3g_ye;            // the per-cell results between the two passes [n_elem][dim][nn]
-  DevBuf<int32_t> d_h3g_aoft, d_h3g_inc_ptr, d_h3g_inc;   // as d_hog_aoft, d_hog_inc_ptr, d_hog_inc
-  // reference matrices of the ngl = 3 element in tensor (lattice) order, from the uploaded tables (pyn_elem_tables_set):
-  // Tf / Tr[r][s][a][b] = sum_g w Hrs_r[a] Hrs_s[b] (full / reduced rule), Uf / Ur[r][a][b] = sum_g w H[a] Hrs_r[b]
-  DevBuf<double> d_ho3_tabs;
-  std::vector<double> ho3_t1d_host;    // 1-D factors M, D, S of the three rules; the records are their tensor products when ho3_tens_ok
-  DevBuf<double> d_ho3_t1d;
-  bool ho3_tens_ok = false;
-  std::vector<double> ho3_tabs_host;   // host image of the records (the three rules arrive in separate pyn_elem_tables_set calls)
-  bool ho3_tabs_ok[3] = {false, false, false};   // full, reduced, nodal rule
-  int ho3_tabs_nn = 0;
-
-  // SELL-64 structures, one per block shape, + the node-level column-pattern dictionary (pyn_sell.hip)
-  std::vector<SellShape> sell_shapes;
-  DevBuf<int32_t> sell_pid;      // per-node column-pattern id (dictionary mode), else null
-  DevBuf<int32_t> sell_tab;      // [npat][32] relative node offsets
-  int sell_npat = 0;
-  bool sell_dict_built = false;
   int64_t prod_last[8] = {0};    // pyn_product_last: the most recent product launch (pyn_product_record)
 
-  std::vector<DMat> mats;
-  std::vector<DVec> vecs;
+  std::vector<DVec> vecs;           // outlive a mesh: a vector of the previous mesh is refused by its node count
   std::vector<DNodeSet> nodesets;   // ids are never reused: a released set stays dead (pyn_fields.hip)
   std::vector<DProbe> probes;       // point probes (pyn_probe.hip); ids are never reused either, and a new mesh kills every set
-  DevBuf<int32_t> d_probe_loc;      // ... their local-order table ref_local_lattice(ngl, dim) [nn][dim] ...
-  DevBuf<double> d_probe_tab;       // ... and the 1-D Lobatto nodes x[ngl] with the Lagrange denominators den[ngl], uploaded once for
-  int probe_tab_ngl = 0, probe_tab_dim = 0;   // ... this order and dimension
-  // mesh integrals (pyn_integrals.hip): the 1-D tables w x B G of both rules and a_of_t of this order and dimension, uploaded on first
-  // use; the chunk partials (grown on demand), the result and the lowest cell with det J <= 0.  A new mesh releases all of it
-  DevBuf<double> d_int_tab[2], d_int_part, d_int_out;
-  DevBuf<int32_t> d_int_aoft;
-  DevBuf<int> d_int_bad;
-  int int_tab_ngl = 0, int_tab_dim = 0;
 
   // reduction / solver scratch
   DevBuf<double> d_part;       // [8][PYN_MAX_PARTIALS]
@@ -454,14 +490,8 @@ struct pyn_ctx {
   // per-context kernel attributes (pyn_kernel_lds / pyn_kernel_occupancy): a second context on another device sets its own
   std::map<const void*, size_t> kern_lds;                      // dynamic-LDS limit this context has raised the kernel to
   std::map<std::pair<const void*, size_t>, int> kern_occ;      // workgroups per CU of (kernel, dynamic LDS)
-  // elements with an imposed node (the only ones that feed an imposed-column matrix), per Dirichlet set
-  DevBuf<int32_t> d_esel;
-  int64_t n_esel = 0, esel_stamp = -1;
-  // general-geometry KLE: off-diagonal element Laplacians [28][ne] between the pre-pass and the tile kernel (grown on demand)
-  DevBuf<double> d_kle_lel;
   // element-local scratch for pyn_elem_local
   DevBuf<double> d_eloc;
-  std::unique_ptr<IbmState, IbmStateDelete> ibm;   // immersed-boundary marker set (pyn_ibm.hip): stencils, node-major spreading lists, A = H S and its LU
 };
 
 inline int64_t n_local(const pyn_ctx* c) { return c->n_owned + c->n_ghost; }
@@ -506,7 +536,6 @@ inline int pyn_raw_grid(int64_t rows) { return (int)std::max<int64_t>(1, std::mi
 inline int pyn_spmv_raw(pyn_ctx* c, const DMat& A, const double* x, double* y) {
   return pyn_sell_spmv(c, A, PYN_RAW_PLAN, x, y, false, nullptr);
 }
-void pyn_sell_drop_structure(pyn_ctx* c);
 const SellShape* pyn_sell_shape(pyn_ctx* c, const DMat& A);
 // compact imposed-column matrices (pyn_rhs.hip)
 int pyn_rhs_ensure(pyn_ctx* c, DMat& M, bool relayout = false);   // row selection + storage (values zeroed when laid out); relayout: for the CURRENT Dirichlet set
@@ -519,7 +548,6 @@ using ConnAt = std::function<int32_t(int64_t)>;
 int pyn_box_detect(pyn_ctx* c, const ConnAt& at);
 void ref_local_lattice(int n, int dim, std::vector<int>& out);
 void mesh_local_lattice(int ngl, int dim, std::vector<int>& loc);
-void pyn_integrals_release(pyn_ctx* c);   // pyn_integrals.hip: the tables and scratch of the mesh integrals
 // the three views of c->box, each next to its kernels (once per pyn_mesh_set, after pyn_box_detect)
 int pyn_lattice_view(pyn_ctx* c);   // pyn_assemble_lattice.hip
 bool pyn_q1_affine_tables_standard(const double* aff);
@@ -681,7 +709,7 @@ int pyn_assemble_lattice_march(pyn_ctx* c, const AsmKnobs& k, void* lat_args, in
 int pyn_assemble_kle_lattice(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P);    // AK_KLE_LATTICE
 int pyn_assemble_patch(pyn_ctx* c, const AsmRequest& rq, const AsmKnobs& k, const AsmPlan& P);          // AK_PATCH
 int pyn_patch_plan_default(pyn_ctx* c, int kind);   // the automatic plan of a graph without one; leaves none where it does not apply or fit
-int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k);   // c->mesh_affine, c->lat.std_ok (once per mesh / graph)
+int pyn_lattice_checks(pyn_ctx* c, const AsmKnobs& k);   // c->mesh_affine, c->lat_std_ok (once per mesh / graph)
 int pyn_ho3_prepare(pyn_ctx* c);                         // geometry pre-pass of a row-run assembly (+ c->ho3.affine / diag, once per mesh)
 int pyn_ho3_run_length(int dim, int ngl, bool op, int knob);   // rows per run of the row-run kernels
 // per-context kernel attributes (pyn_ctx.hip): raise fn's dynamic-LDS limit unless this context already set at least `bytes` (kernels

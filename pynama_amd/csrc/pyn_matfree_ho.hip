@@ -557,10 +557,6 @@ extern "C" int pyn_mesh_ho_lattice(pyn_ctx* c, int* ngl, int* nx, int* ny, int* 
 // The ngl >= 4 view of c->box: the orders the kernels are instantiated for.  pyn_mesh_topology keeps reporting kind 0 for these meshes:
 // only the matrix-free operator uses the view.
 void pyn_ho_view(pyn_ctx* c) {
-  c->d_ho_tab.reset();   // the operator's tables and scratch belong to the mesh
-  c->d_ho_ye.reset();
-  pyn_hog_release(c);
-  pyn_h3g_release(c);
   const BoxLattice& B = c->box;
   c->ho_valid = B.valid && B.ngl >= 4 && B.ngl <= pyn_ho_matfree_max_ngl(B.dim) && B.plane() <= INT32_MAX / 4 && B.n_own >= 1 &&
                 c->n_elem < INT32_MAX && !getenv("PYNAMA_NO_HO_LATTICE");

@@ -295,9 +295,9 @@ H3gArgs h3g_args(const pyn_ctx* c) {
   A.conn = c->d_conn;
   A.xyz = c->d_xyz;
   A.mask = c->mf_mask[OP];
-  A.tab = c->d_h3g_tab;
-  A.aoft = c->d_h3g_aoft;
-  A.ye = c->d_h3g_ye;
+  A.tab = c->h3g.tab;
+  A.aoft = c->h3g.aoft;
+  A.ye = c->h3g.ye;
   A.n_cells = (int)c->n_elem;
   A.alpha_d = c->mf_alpha_d[OP];
   A.alpha_w = c->mf_alpha_w[OP];
@@ -354,7 +354,7 @@ int h3g_set(pyn_ctx* c, int op) {
   const H3gTab T;
   PYN_TRY(h3g_check_rules(c, T));
   PYN_TRY(pyn_hog_check_geometry_tables(c, T.xf, T.xr, WHAT));
-  pyn_h3g_release(c);
+  c->h3g = H3gState();
   c->mf_set[OP] = false;
   // built here, committed together at the end: a refused set leaves nothing behind
   DevBuf<double> d_tab, d_ye;
@@ -369,18 +369,18 @@ int h3g_set(pyn_ctx* c, int op) {
   PYN_TRY(pyn_hog_check_det(c, d_aoft, d_tab, H3gTab::XF, WHAT, "a point of the Gauss(3) or of the Gauss(2) rule"));
   PYN_TRY(pyn_hog_incidence(c, aoft, WHAT, d_inc_ptr, d_inc));
   PYN_HIP(d_ye.alloc((size_t)c->n_elem * nn * dim));
-  c->d_h3g_tab = std::move(d_tab);
-  c->d_h3g_ye = std::move(d_ye);
-  c->d_h3g_aoft = std::move(d_aoft);
-  c->d_h3g_inc_ptr = std::move(d_inc_ptr);
-  c->d_h3g_inc = std::move(d_inc);
+  c->h3g.tab = std::move(d_tab);
+  c->h3g.ye = std::move(d_ye);
+  c->h3g.aoft = std::move(d_aoft);
+  c->h3g.inc_ptr = std::move(d_inc_ptr);
+  c->h3g.inc = std::move(d_inc);
   return PYN_OK;
 }
 
 // y = K x under the mask snapshot of pyn_matfree_set.  dot: fused p.Ap partials into c->d_part (one per workgroup of the gather pass,
 // *grid_out of them).
 int h3g_spmv(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid_out) {
-  PYN_CHECK(op == OP && c->mf_set[OP] && c->d_h3g_tab && c->d_h3g_ye && c->d_h3g_aoft && c->d_h3g_inc_ptr && c->d_h3g_inc,
+  PYN_CHECK(op == OP && c->mf_set[OP] && c->h3g.tab && c->h3g.ye && c->h3g.aoft && c->h3g.inc_ptr && c->h3g.inc,
             "%s: pyn_matfree_set first", WHAT);
   const H3gArgs A = h3g_args(c);
   const int* flag = dot ? c->d_flag : nullptr;
@@ -388,21 +388,13 @@ int h3g_spmv(pyn_ctx* c, int op, const double* x, double* y, bool dot, int* grid
     PYN_TRY(launch_h3g_cells<3>(c, A, x, flag));
   else
     PYN_TRY(launch_h3g_cells<2>(c, A, x, flag));
-  return pyn_hog_gather(c, c->d_h3g_inc_ptr, c->d_h3g_inc, A.ye, A.mask, x, y, dot, grid_out);
+  return pyn_hog_gather(c, c->h3g.inc_ptr, c->h3g.inc, A.ye, A.mask, x, y, dot, grid_out);
 }
 
 bool h3g_mesh(const pyn_ctx*) { return false; }   // never chosen by the mesh: the operator id selects this backend
 int h3g_bs(const pyn_ctx* c, int) { return c->dim; }
 
 }  // namespace
-
-void pyn_h3g_release(pyn_ctx* c) {
-  c->d_h3g_tab.reset();
-  c->d_h3g_ye.reset();
-  c->d_h3g_aoft.reset();
-  c->d_h3g_inc_ptr.reset();
-  c->d_h3g_inc.reset();
-}
 
 const MfBackend* pyn_mf_h3g() {
   static const MfBackend b = {h3g_mesh, h3g_set, h3g_bs, h3g_spmv, nullptr};

@@ -458,7 +458,7 @@ HogArgs hog_args(const pyn_ctx* c) {
   A.xyz = c->d_xyz;
   A.mask = c->mf_mask[PYN_MATFREE_KLE_GENERAL];
   A.tab = c->d_ho_tab;
-  A.aoft = c->d_hog_aoft;
+  A.aoft = c->hog.aoft;
   A.ye = c->d_ho_ye;
   A.n_cells = (int)c->n_elem;
   A.alpha_d = c->mf_alpha_d[PYN_MATFREE_KLE_GENERAL];
@@ -497,12 +497,6 @@ int pyn_hog_check_geometry_tables(pyn_ctx* c, const std::vector<double>& pts_ful
   PYN_CHECK(worst <= 1e-11, "%s (ngl %d): the geometry tables are not the multilinear basis of the cell's %d corners at the points of "
                             "both rules (largest difference %.3e)", WHAT, ngl, nc, worst);
   return PYN_OK;
-}
-
-void pyn_hog_release(pyn_ctx* c) {
-  c->d_hog_aoft.reset();
-  c->d_hog_inc_ptr.reset();
-  c->d_hog_inc.reset();
 }
 
 // a_of_t: the local node at tensor position i + ngl (j + ngl k), the inverse of mesh_local_lattice
@@ -593,7 +587,7 @@ int pyn_hog_set(pyn_ctx* c) {
   PYN_TRY(pyn_ho_check_rules(c, T, WHAT));
   PYN_TRY(pyn_hog_check_geometry_tables(c, T.xl, T.xr, WHAT));
   PYN_TRY(pyn_ho_tab_upload(c, T));
-  pyn_hog_release(c);
+  c->hog = HogState();
   c->mf_set[PYN_MATFREE_KLE_GENERAL] = false;
   std::vector<int32_t> aoft;
   pyn_hog_aoft(ngl, dim, aoft);
@@ -603,9 +597,9 @@ int pyn_hog_set(pyn_ctx* c) {
   const int tab_pts = (int)(T.packed().size() - T.xl.size() - T.xr.size());
   PYN_TRY(pyn_hog_check_det(c, d_aoft, c->d_ho_tab, tab_pts, WHAT, "a Lobatto node or a Gauss point"));
   PYN_TRY(pyn_hog_incidence(c, aoft, WHAT, d_inc_ptr, d_inc));
-  c->d_hog_aoft = std::move(d_aoft);
-  c->d_hog_inc_ptr = std::move(d_inc_ptr);
-  c->d_hog_inc = std::move(d_inc);
+  c->hog.aoft = std::move(d_aoft);
+  c->hog.inc_ptr = std::move(d_inc_ptr);
+  c->hog.inc = std::move(d_inc);
   return PYN_OK;
 }
 
@@ -636,9 +630,9 @@ int pyn_hog_gather(pyn_ctx* c, const int32_t* inc_ptr, const int32_t* inc, const
 // y = K x under the mask snapshot of pyn_matfree_set.  dot: fused p.Ap partials into c->d_part (one per workgroup of the gather pass,
 // *grid_out of them).
 int pyn_hog_spmv(pyn_ctx* c, const double* x, double* y, bool dot, int* grid_out) {
-  PYN_CHECK(c->mf_set[PYN_MATFREE_KLE_GENERAL] && c->d_ho_tab && c->d_ho_ye && c->d_hog_aoft && c->d_hog_inc_ptr && c->d_hog_inc,
+  PYN_CHECK(c->mf_set[PYN_MATFREE_KLE_GENERAL] && c->d_ho_tab && c->d_ho_ye && c->hog.aoft && c->hog.inc_ptr && c->hog.inc,
             "%s: pyn_matfree_set first", WHAT);
   const HogArgs A = hog_args(c);
   PYN_TRY(launch_hog_cells_any(c, c->dim, c->ngl, A, x, dot ? c->d_flag : nullptr));
-  return pyn_hog_gather(c, c->d_hog_inc_ptr, c->d_hog_inc, A.ye, A.mask, x, y, dot, grid_out);
+  return pyn_hog_gather(c, c->hog.inc_ptr, c->hog.inc, A.ye, A.mask, x, y, dot, grid_out);
 }

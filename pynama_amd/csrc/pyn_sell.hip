@@ -1317,11 +1317,3 @@ int pyn_sell_spmv(pyn_ctx* c, const DMat& A, const ProductPlan& P, const double*
   const int64_t ns = (c->n_owned * A.br + SH - 1) / SH;
   return pyn_sell_spmv_range2(c, A, P, x, y, dot, 0, ns, ns, ns, 0, PYN_MAX_PARTIALS, c->stream, grid_out);
 }
-
-void pyn_sell_drop_structure(pyn_ctx* c) {
-  c->sell_shapes.clear();
-  c->sell_pid.reset();
-  c->sell_tab.reset();
-  c->sell_npat = 0;
-  c->sell_dict_built = false;
-}

@@ -31,15 +31,14 @@ __global__ void split_keys_kernel(const unsigned long long* __restrict__ keys, i
   }
 }
 
-// the patch plans, the SELL structures and all matrices are tied to the graph
-static int pyn_symbolic_reset_dependents(pyn_ctx* c) {
-  PYN_TRY(pyn_patch_plan_set_kind(c, 0, 0, nullptr, nullptr));
-  PYN_TRY(pyn_patch_plan_set_kind(c, 1, 0, nullptr, nullptr));
-  c->mats.clear();
-  c->esel_stamp = -1;
-  pyn_sell_drop_structure(c);
-  c->lat.std_ok = -1;  // closed-form row offsets are re-verified against the new graph
-  c->plan_unfit[0] = c->plan_unfit[1] = false;
+// A new graph (c->d_rowptr / d_colidx / nnzb just committed) ends the graph scope: the patch plans, the SELL structures, the closed-form
+// check and every matrix were built on the old one.  The stream is idle here.
+static int graph_installed(pyn_ctx* c) {
+  CtxGraph g;
+  g.d_rowptr = std::move(c->d_rowptr);
+  g.d_colidx = std::move(c->d_colidx);
+  g.nnzb = c->nnzb;
+  static_cast<CtxGraph&>(*c) = std::move(g);
   return PYN_OK;
 }
 
@@ -58,7 +57,7 @@ extern "C" int pyn_csr_symbolic(pyn_ctx* c) {
     float ms0 = 0;
     PYN_HIP(hipEventElapsedTime(&ms0, c->ev0, c->ev1));
     c->timers[PYN_T_SYMBOLIC] = ms0;
-    return pyn_symbolic_reset_dependents(c);
+    return graph_installed(c);
   }
   const int64_t total = c->n_elem * c->nn * c->nn;
   DevTmp tk0, tk1, tn, tmp, tcnt;
@@ -109,7 +108,7 @@ extern "C" int pyn_csr_symbolic(pyn_ctx* c) {
   c->d_rowptr = std::move(rowptr);   // the stream is idle: no kernel still reads the old graph
   c->d_colidx = std::move(colidx);
   c->nnzb = nuniq;
-  return pyn_symbolic_reset_dependents(c);
+  return graph_installed(c);
 }
 
 extern "C" int pyn_csr_info(pyn_ctx* c, int64_t* n_rows, int64_t* nnz_blocks) {
